@@ -305,38 +305,47 @@ def build_workload(args, pir_amd):
     return enc, pp, item_bytes
 
 
-BLOCK_LOG = []           # per measurement: the per-block elapsed seconds behind the reported median
+BLOCK_LOG = []           # per measurement: the elapsed seconds of its timed block
 
 
-def timed_steps(step, barrier, steps, warmup, dist, use_dist, torch, dev, min_seconds=1.0, max_blocks=9):
-    """The bench contract: W untimed steps, then exactly K steps between barrier + synchronise, MAX over ranks.
-    When that timed block is shorter than `min_seconds` (the driver's --steps 20 is 0.24 s at the headline config, and the
-    same kernel measures 0.195 / 0.207 ms in consecutive runs), the block of K steps is REPEATED -- every block
-    bracketed the same way -- and the median block is reported; the block count follows from the first block's
-    all-reduced time, so every rank runs the same number."""
-    def block():
-        barrier()
-        t0 = time.perf_counter()
-        for _ in range(steps):
-            step()
-        barrier()
-        el = time.perf_counter() - t0
-        if use_dist:
-            t = torch.tensor([el], dtype=torch.float64, device=dev if dist.get_backend() == "nccl" else "cpu")
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            el = float(t.item())
-        return el
-
+def timed_steps(step, barrier, steps, warmup, dist, use_dist, torch, dev):
+    """The bench contract: W untimed steps, then exactly K timed steps between barrier + synchronise, MAX over ranks.
+    Returns the seconds those K steps took; --steps alone sets how many steps are timed."""
     for _ in range(warmup):
         step()
-    times = [block()]
-    want = 1 if times[0] >= min_seconds else min(max_blocks, int(np.ceil(min_seconds / max(times[0], 1e-6))))
-    if want > 1 and want % 2 == 0:
-        want += 1                      # odd: the median is a measured block
-    while len(times) < want:
-        times.append(block())
-    BLOCK_LOG.append([round(t, 6) for t in times])
-    return float(np.median(times))
+    barrier()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        step()
+    barrier()
+    el = time.perf_counter() - t0
+    if use_dist:
+        t = torch.tensor([el], dtype=torch.float64, device=dev if dist.get_backend() == "nccl" else "cpu")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        el = float(t.item())
+    BLOCK_LOG.append([round(el, 6)])
+    return el
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(directory, replies, seed=0):
+    """--dump-outputs: the reply ciphertexts the last timed step handed its caller ([queries, reply cts, 2, k, N]
+    residues) as DIR/replies.npy in float64, exact because every residue is below 2^53.  When the whole batch exceeds
+    DUMP_LIMIT_BYTES, the replies of a fixed, seeded sample of its queries are written instead, and the sampled query
+    indices go to DIR/replies_query_index.npy."""
+    assert int(replies.max(initial=0)) < (1 << 53), "residues do not fit float64 exactly"
+    per_query = replies[0].size * 8
+    n = replies.shape[0]
+    keep = min(n, (DUMP_LIMIT_BYTES - 4096) // (per_query + 8))     # 4 KiB: room for the .npy headers
+    assert keep >= 1, "one query's replies (%d bytes) exceed the dump limit" % per_query
+    os.makedirs(directory, exist_ok=True)
+    if keep < n:
+        idx = np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+        replies = replies[idx]
+        np.save(os.path.join(directory, "replies_query_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(directory, "replies.npy"), replies.astype(np.float64))
 
 
 def batch_launch_block(bs, scan_bytes, info, k, N):
@@ -473,9 +482,17 @@ def main():
     ap.add_argument("--keep-staging", action="store_true",
                     help="keep the u64 staging copy of the database next to the operand-layout copy (default: "
                          "released for d >= 2, one copy of the database in HBM)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the replies of the last timed step to DIR/replies.npy (float64; "
+                         "at most 64 MB, a seeded sample of the queries when the batch is larger), to compare two builds "
+                         "output for output; the inputs are the same in every run with the same arguments (fixed seeds)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and (args.gpus > 1 or args.reference_sweep or os.environ.get("PIRGPU_FORCE_DIST")):
+        ap.error("--dump-outputs needs the single-GPU throughput run (--gpus 1, no --reference-sweep, no PIRGPU_FORCE_DIST)")
 
     # `python bench.py --gpus N` without a launcher environment: start the N ranks ourselves (fresh child processes,
     # before anything here touches a GPU), relay rank 0's JSON line, fail if any rank fails
@@ -686,7 +703,7 @@ def main():
             **({"backend": "gloo (ranks share one GPU: test facility, not a multi-GPU measurement)"} if share_gpu else {}),
             "hip_runtime": hip_runtime_in_use(),
             "steps": args.steps, "warmup": args.warmup,
-            # blocks of K timed steps behind ms_per_step (median block; one block when K steps last >= 1 s)
+            # the one timed block of exactly K steps behind ms_per_step
             "timed_blocks": len(headline_blocks), "timed_block_seconds": headline_blocks,
             "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "dtype": "u64", "data": "synthetic",
@@ -1336,6 +1353,8 @@ def main():
         forced_check = bool(np.array_equal(got, srv.fetch_batch()))
         print("forced-dist check: replies through the collective path equal plain replies: %s" % forced_check, file=sys.stderr)
     batch_replies = srv.fetch_batch() if world == 1 and not use_dist else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, batch_replies)
     # the database pass as it runs INSIDE the step just timed (roofline.kernel_ms above is the single-query launch on the
     # whole chip): HIP events around the batch pipeline's scan launches over a few more steps, outside the timed region
     batch_scan = None

@@ -223,10 +223,12 @@ def _rank(rank, world, port, items, per, out_q):
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("world,per", [(2, 9), (8, 2)])
+@pytest.mark.parametrize("world,per", [(2, 9), (4, 4)])
 def test_slots_step_with_real_servers_over_gloo(world, per):
     """`world` processes share the GPU, each with its slot-shard context of the real server; the all-to-alls run over
-    gloo through host memory (Comm) -- every line of the multi-GPU step except the RCCL calls themselves."""
+    gloo through host memory (Comm) -- every line of the multi-GPU step except the RCCL calls themselves.  At most four
+    ranks: with the test process, no more than five processes hold the GPU at once, so the suite can run on a GPU that
+    other jobs share; eight slot shards on one GPU are covered in one process above."""
     ctx = mp.get_context("spawn")
     out_q = ctx.Queue()
     port = _free_port()

@@ -139,8 +139,8 @@ def test_bench_output_stage_does_not_shadow_the_measurement_state():
 
 def test_bench_traffic_staleness_and_timed_blocks(tmp_path, monkeypatch):
     """roofline.traffic is a RECORDED figure -- bench.py says whether the scan kernel's source is
-    still the one the PMC passes profiled (`traffic_stale`), and a timed block shorter than a second is repeated and the
-    median block reported."""
+    still the one the PMC passes profiled (`traffic_stale`), and --steps K times exactly K steps after the W warm-up
+    steps, in one block, however short it is."""
     import hashlib
     import types
     sys.path.insert(0, ROOT)
@@ -154,14 +154,42 @@ def test_bench_traffic_staleness_and_timed_blocks(tmp_path, monkeypatch):
     monkeypatch.setattr(bench, "scan_source_sha16", lambda: "0" * 16)
     assert bench.recorded_traffic(3, 20, 1, True)[2] is True
     assert bench.recorded_traffic(3, 19, 1, True) == (None, None, None)        # another shape: nothing recorded
-    # timed blocks: 10 ms steps x 5 = 50 ms per block -> repeated up to 9 times (odd), median reported
-    calls = []
-    t = bench.timed_steps(lambda: (calls.append(1), time.sleep(0.01)), lambda: None, 5, 1, None, False, None, "cpu")
-    assert len(bench.BLOCK_LOG[-1]) == 9 and len(calls) == 1 + 9 * 5
-    assert 0.045 < t < 0.2 and abs(t - sorted(bench.BLOCK_LOG[-1])[4]) < 1e-5
-    # a block of a second or more is not repeated
+    # timed steps: 10 ms steps, W = 1, K = 5 -> 6 calls, one block of the 5 timed ones (50 ms: short, not repeated)
+    calls, barriers = [], []
+    t = bench.timed_steps(lambda: (calls.append(1), time.sleep(0.01)), lambda: barriers.append(len(calls)), 5, 1, None,
+                          False, None, "cpu")
+    assert len(calls) == 1 + 5 and barriers == [1, 6]           # the bracket holds exactly the K timed steps
+    assert len(bench.BLOCK_LOG[-1]) == 1 and abs(t - bench.BLOCK_LOG[-1][0]) < 1e-5
+    assert 0.045 < t < 0.5
+    # a longer block: one block as well
     t = bench.timed_steps(lambda: time.sleep(0.26), lambda: None, 4, 0, None, False, None, "cpu")
     assert len(bench.BLOCK_LOG[-1]) == 1 and t >= 1.0
+
+
+def test_bench_dump_outputs_is_exact_and_bounded(tmp_path, monkeypatch):
+    """--dump-outputs DIR: the replies of the last timed step as DIR/replies.npy in float64, every residue exact; a batch
+    larger than the limit is written as the replies of a fixed, seeded sample of its queries, the indices beside them."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(3)
+    replies = rng.integers(0, 1 << 52, size=(6, 4, 2, 2, 64), dtype=np.uint64)
+    replies[0, 0, 0, 0, 0] = (1 << 53) - 1
+    bench.dump_outputs(str(tmp_path / "all"), replies)
+    got = np.load(tmp_path / "all" / "replies.npy")
+    assert got.dtype == np.float64 and np.array_equal(got.astype(np.uint64), replies)
+    assert sorted(os.listdir(tmp_path / "all")) == ["replies.npy"]
+    # room for 2.x queries' replies: a sample of 2, the same in every run, within the limit
+    per_query = replies[0].size * 8
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096 + 2 * (per_query + 8) + per_query // 2)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), replies)
+    idx = np.load(tmp_path / "s1" / "replies_query_index.npy")
+    assert idx.dtype == np.float64 and len(idx) == 2 and np.array_equal(idx, np.load(tmp_path / "s2" / "replies_query_index.npy"))
+    got = np.load(tmp_path / "s1" / "replies.npy")
+    assert np.array_equal(got.astype(np.uint64), replies[idx.astype(np.int64)])
+    assert np.array_equal(got, np.load(tmp_path / "s2" / "replies.npy"))
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")) <= bench.DUMP_LIMIT_BYTES
 
 
 def test_bench_withholds_a_stale_valu_table(tmp_path, monkeypatch):
