@@ -52,7 +52,8 @@ typedef struct pirgpu_ctx pirgpu_ctx;
 /* What PIRContext + PIRParameters carry (reference context.h:36-84,
  * pir/proto/payload.proto:45-69), flattened. */
 typedef struct pirgpu_params {
-  uint32_t poly_modulus_degree;            /* N: 2048, 4096, 8192 or 16384 */
+  uint32_t poly_modulus_degree;            /* N: 2048, 4096, 8192, 16384 or 32768 (32768: integer NTTs; an explicit
+                                              coefficient modulus of at most PIRGPU_MAX_PRIMES data primes) */
   uint32_t num_data_primes;                /* k: ciphertext level (first_context_data) */
   uint64_t coeff_modulus[PIRGPU_MAX_PRIMES]; /* q_0..q_{k-1} */
   uint64_t special_prime;                  /* key-switching prime p (last of SEAL's coeff_modulus) */

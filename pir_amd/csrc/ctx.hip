@@ -429,6 +429,9 @@ void build_tables(pirgpu_ctx* c) {
     int want = atoi(v);
     if (want == kNttInt || (want == kNttF64Wide && c->mode != kNttInt) || want == c->mode) c->mode = want;
   }
+  // N = 32768 has the integer flavour only (ntt_ring32k.hip: two-pass transforms through HBM, no fused fp64 kernels),
+  // whatever the moduli; a PIRGPU_NTT_MODE asking for an fp64 flavour is ignored there
+  if (c->logN >= 15) c->mode = kNttInt;
   hp.ntt_mode = c->mode;
   hp.f64_lazy_inv = (64 - (uint32_t)__builtin_clzll(qmax)) + c->logN <= 52 ? 1u : 0u;
   if (const char* v = pirgpu_env("PIRGPU_F64_LAZY_INV")) hp.f64_lazy_inv = atoi(v) ? hp.f64_lazy_inv : 0u;
@@ -622,6 +625,9 @@ void ensure_workspace(pirgpu_ctx* c) {
     c->head_levels = std::min<uint32_t>(env_u32("PIRGPU_HEAD_LEVELS", c->head_levels), 8);
     c->head_mode = std::min<uint32_t>(env_u32("PIRGPU_HEAD_MODE", c->head_mode), 2);
     c->split_upper = env_u32("PIRGPU_SPLIT_UPPER", c->logN >= 14 ? 1 : 0) != 0 && c->mode != kNttInt;
+    // N = 32768: always the split form, in its integer version (upper_ntt + launch_upper_mac_int) -- that degree's table
+    // has no upper_fused
+    if (c->logN >= 15) c->split_upper = true;
     c->split_upper_words = (uint64_t)env_u32("PIRGPU_SPLIT_UPPER_MB", 3072) * (1ull << 20) / 8;
     c->loop_transforms = env_u32("PIRGPU_LOOP_TRANSFORMS", 1) != 0 && c->mode != kNttInt;
     // (loop_min_sources: swept 512 - 4096 in round 4, 1 024 stays: a constant since round 5)
@@ -636,6 +642,7 @@ void ensure_workspace(pirgpu_ctx* c) {
       int want = (int)env_u32("PIRGPU_PACK_BYTES", (uint32_t)need);
       if (want < need) want = need;
       if (c->mode == kNttInt && want != 5) want = 8;
+      if (c->logN >= 15) want = 8;   // N = 32768: the integer kernels there keep their intermediates as u64
       if (want > 7) c->pack40 = false;
       c->pack_bytes = c->pack40 ? want : 5;
       // (N = 16384 with 7-byte residues: the combine kernel that also reads and writes the TREE packed needs 68 bytes of
@@ -1160,9 +1167,14 @@ void post_scan_stage(pirgpu_ctx* c, const Stage& sg, Worker* profiled) {
       for (uint32_t b0 = 0; b0 < nd; b0 += blk) {
         HIP_TRY(c->ops->upper_ntt(st, c->mode, c->dp, k, c->E, sg.lvl[l + 1], *sg.up_scratch, (uint32_t)rows, c->dims[l],
                                   (uint32_t)nch, (uint32_t)C, b0, blk, sg.n, c->lvl_cts[l + 1] * ctw, c->loop_transforms));
-        HIP_TRY(launch_upper_mac(st, c->dp, *sg.up_scratch, sg.sel, sg.pt_buf, sg.lvl[l], sg.n, (uint32_t)rows, (uint32_t)C,
-                                 c->E, k, N, sv_first, b0, blk, nd, b0 == 0, b0 + blk >= nd, c->pt_words,
-                                 c->lvl_cts[l] * ctw));
+        if (c->mode == kNttInt)   // N = 32768
+          HIP_TRY(launch_upper_mac_int(st, c->dp, *sg.up_scratch, sg.sel, sg.pt_buf, sg.lvl[l], sg.n, (uint32_t)rows,
+                                       (uint32_t)C, c->E, k, N, sv_first, b0, blk, nd, b0 == 0, b0 + blk >= nd, c->pt_words,
+                                       c->lvl_cts[l] * ctw));
+        else
+          HIP_TRY(launch_upper_mac(st, c->dp, *sg.up_scratch, sg.sel, sg.pt_buf, sg.lvl[l], sg.n, (uint32_t)rows, (uint32_t)C,
+                                   c->E, k, N, sv_first, b0, blk, nd, b0 == 0, b0 + blk >= nd, c->pt_words,
+                                   c->lvl_cts[l] * ctw));
       }
       if (l == 0 && profiled) record(c, *profiled, PH_FINAL);
     } else {
@@ -1244,8 +1256,8 @@ int pirgpu_create(const pirgpu_params* p, pirgpu_ctx** out) {
   try {
     c->prm = *p;
     const uint32_t N = p->poly_modulus_degree, k = p->num_data_primes;
-    if (N < 2048 || N > 16384 || (N & (N - 1)))
-      return bail(PIRGPU_INVALID_ARGUMENT, "poly_modulus_degree must be 2048, 4096, 8192 or 16384");
+    if (N < 2048 || N > 32768 || (N & (N - 1)))
+      return bail(PIRGPU_INVALID_ARGUMENT, "poly_modulus_degree must be 2048, 4096, 8192, 16384 or 32768");
     if (k < 1 || k > PIRGPU_MAX_PRIMES) return bail(PIRGPU_INVALID_ARGUMENT, "invalid number of data primes");
     if (p->use_ciphertext_multiplication)
       return bail(PIRGPU_UNIMPLEMENTED,
@@ -1308,7 +1320,7 @@ int pirgpu_create(const pirgpu_params* p, pirgpu_ctx** out) {
     c->use_device();
     HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     c->ops = ntt_ops_for(N);
-    if (!c->ops) return bail(PIRGPU_INVALID_ARGUMENT, "poly_modulus_degree must be 2048, 4096, 8192 or 16384");
+    if (!c->ops) return bail(PIRGPU_INVALID_ARGUMENT, "poly_modulus_degree must be 2048, 4096, 8192, 16384 or 32768");
     build_tables(c);
     HIP_TRY(c->ops->configure(c->mode));
     c->reply_cts = 1;

@@ -21,7 +21,9 @@ constexpr int kMaxScanQueries = 4;       // queries sharing one database pass in
 #ifdef PIRGPU_LOG_EPT_ALL   // prototypes only (tools/ntt_short_proto.hip): every degree with 2^PIRGPU_LOG_EPT_ALL residues per thread
 constexpr int ntt_log_ept(int) { return PIRGPU_LOG_EPT_ALL; }
 #else
-constexpr int ntt_log_ept(int logN) { return logN >= 14 ? PIRGPU_LOG_EPT14 : 4; }
+// N = 32768 (logN 15): 0 -- the device order is SEAL's own order there.  No workgroup holds a whole polynomial at that
+// degree; its two-pass transform (ntt_ring32k.hip) ends on contiguous blocks of 256 and writes them in place.
+constexpr int ntt_log_ept(int logN) { return logN >= 15 ? 0 : (logN >= 14 ? PIRGPU_LOG_EPT14 : 4); }
 #endif
 
 #include "env_gate.h"

@@ -45,7 +45,7 @@ struct KeyPtrs {
 };
 
 // Kernels that contain an NTT, for one ring degree (ntt_kernels.hip is compiled once
-// per degree).  `mode` is an NttMode.
+// per degree; N = 32768 has its own translation unit, ntt_ring32k.hip, integer flavour only).  `mode` is an NttMode.
 struct NttOps {
   hipError_t (*configure)(int mode);
   hipError_t (*ntt_batch)(hipStream_t st, int mode, const DevParams* P, uint64_t* data, uint64_t n_polys,
@@ -115,6 +115,7 @@ struct NttOps {
 };
 
 // pack_bytes: width of the packed key-switch intermediates the kernels are built for (5, 6 or 7; ntt_kernels.hip)
+// (N = 32768: one table whatever the width -- its integer kernels never store packed intermediates)
 const NttOps* ntt_ops_for(uint32_t N, int pack_bytes = 5);  // nullptr for unsupported degrees
 
 hipError_t launch_ntt_reorder(hipStream_t st, uint32_t N, const uint64_t* in, uint64_t* out, uint64_t n_polys,
@@ -143,6 +144,13 @@ hipError_t launch_reduce_splits(hipStream_t st, const DevParams* P, const uint64
                                 uint64_t words, uint64_t* out, uint32_t n_queries = 1, uint64_t part_qstride = 0,
                                 uint64_t out_qstride = 0);
 
+
+// the same for the integer flavour at N = 32768 (ntt_ring32k.hip): scratch holds canonical u64 residues (upper_ntt of
+// that degree), `acc` canonical partial sums
+hipError_t launch_upper_mac_int(hipStream_t st, const DevParams* P, const uint64_t* scratch, const MfmaPtrs& svq,
+                                uint64_t* acc, uint64_t* out, uint32_t n_queries, uint32_t n_rows, uint32_t C,
+                                uint32_t enc_count, uint32_t k, uint32_t N, uint32_t sv_first, uint32_t b0, uint32_t blk,
+                                uint32_t n_dim, bool first, bool last, uint64_t acc_qstride, uint64_t out_qstride);
 
 // split upper level, part 2: acc[query][slot][comp][jt][i] (+)= sum over the block's children of
 // scratch (.) selector, elementwise; `first` starts the sums, `last` writes canonical u64 residues to `out`

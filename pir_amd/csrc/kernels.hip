@@ -790,11 +790,13 @@ static inline uint32_t log2u(uint32_t N) {
 #define PIRGPU_DECL_OPS(L) const NttOps* ntt_ops_##L(); const NttOps* ntt_ops_##L##_p6(); const NttOps* ntt_ops_##L##_p7();
 PIRGPU_DECL_OPS(11) PIRGPU_DECL_OPS(12) PIRGPU_DECL_OPS(13) PIRGPU_DECL_OPS(14)
 #undef PIRGPU_DECL_OPS
+const NttOps* ntt_ops_15();   // N = 32768: two-pass transforms, integer flavour (ntt_ring32k.hip)
 
 const NttOps* ntt_ops_for(uint32_t N, int pack_bytes) {
 #define PIRGPU_PICK(L) case L: return pack_bytes == 6 ? ntt_ops_##L##_p6() : (pack_bytes == 7 ? ntt_ops_##L##_p7() : ntt_ops_##L());
   switch (log2u(N)) {
     PIRGPU_PICK(11) PIRGPU_PICK(12) PIRGPU_PICK(13) PIRGPU_PICK(14)
+    case 15: return ntt_ops_15();
     default: return nullptr;
   }
 #undef PIRGPU_PICK

@@ -110,6 +110,12 @@ def generate_encryption_params(poly_modulus_degree: int = 4096, plain_mod_bit_si
                                coeff_modulus: Optional[Sequence[int]] = None,
                                plain_modulus: Optional[int] = None) -> EncryptionParams:
     if coeff_modulus is None:
+        if poly_modulus_degree not in BFV_DEFAULT:
+            # N = 32768: SEAL's default chain has 16 primes -- k = 15 data primes, more than the 8 the server holds
+            # (PIRGPU_MAX_PRIMES).  Such a ring needs an explicit modulus (the reference's coeff_opt,
+            # parameters.cpp:40-53) of at most 8 data primes plus the special prime.
+            raise ValueError("no default coefficient modulus for poly_modulus_degree %d: pass coeff_modulus explicitly "
+                             "(at most 8 data primes followed by the special prime)" % poly_modulus_degree)
         coeff_modulus = BFV_DEFAULT[poly_modulus_degree]
     if plain_modulus is None:
         plain_modulus = plain_modulus_batching(poly_modulus_degree, plain_mod_bit_size)
