@@ -117,6 +117,27 @@ uint64_t pirgpu_db_size(const pirgpu_ctx* ctx);
  * padding) and cannot be reloaded (FailedPrecondition); pirgpu_db_read_plaintext keeps working.
  * No reference counterpart (the reference keeps one vector<Plaintext>, database.h:126-133). */
 int pirgpu_db_finalize(pirgpu_ctx* ctx, int release_staging);
+/* In-place updates of a fully loaded database (FailedPrecondition before that: the first load is populate); no
+ * reference counterpart (database.cpp:84-110 only repopulates).  Afterwards the context is indistinguishable from one
+ * populated from scratch with the updated raw database: plaintexts, zero-plaintext count and every query path.  Work
+ * and device scratch follow the number of touched plaintexts: only they are re-encoded, and only their columns of the
+ * operand-layout copy are rewritten (no repack).  Works with the staging copy kept and after
+ * pirgpu_db_finalize(ctx, 1).  The call first waits for all device work queued on the context, then applies the
+ * update under the context's lock: no reply mixes old and new plaintexts, and a request made after the call returns
+ * sees only the new database.  Argument errors (InvalidArgument) are found before anything changes.  n = 0: no-op.
+ *
+ * Replace items: item_indices[i] < params.num_items; items = n x bytes_per_item (== params.bytes_per_item), row i is
+ * the new value of item item_indices[i].  A later entry wins over an earlier one with the same index.  Indices outside
+ * this context's row shard are skipped (every rank of a row-sharded server can be given the same full list).  Every
+ * other bit of a touched plaintext -- other items, padding, coefficient bits a coefficient load set -- is kept.
+ * A slot shard (slot_begin / slot_end) with released staging returns FailedPrecondition: it holds 1 / G of each
+ * plaintext and cannot recover the items it must keep. */
+int pirgpu_db_update_items(pirgpu_ctx* ctx, uint64_t n, const uint64_t* item_indices, const uint8_t* items,
+                           uint32_t bytes_per_item);
+/* Replace whole plaintexts given as coefficient rows (each < t; the pirgpu_db_load_coeffs analogue of the above, for
+ * any index set): pt_indices[i] < num_pt, coeffs = n x N.  A later entry wins; indices outside the row shard are
+ * skipped.  Works on slot shards in every state (it needs no old content). */
+int pirgpu_db_update_plaintexts(pirgpu_ctx* ctx, uint64_t n, const uint64_t* pt_indices, const uint64_t* coeffs);
 /* SEAL's default build throws logic_error("result ciphertext is transparent") from multiply_plain when a
  * database plaintext is identically zero, which the reference surfaces as InternalError for every query
  * (database.cpp:308-315).  Default (allow == 0): same status.  allow != 0: return the mathematically defined

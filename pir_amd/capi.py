@@ -78,6 +78,8 @@ SIGNATURES = {
     "pirgpu_db_size": (C.c_uint64, [C.c_void_p]),
     "pirgpu_db_read_plaintext": (C.c_int, [C.c_void_p, C.c_uint64, u64p]),
     "pirgpu_db_finalize": (C.c_int, [C.c_void_p, C.c_int]),
+    "pirgpu_db_update_items": (C.c_int, [C.c_void_p, C.c_uint64, u64p, u8p, C.c_uint32]),
+    "pirgpu_db_update_plaintexts": (C.c_int, [C.c_void_p, C.c_uint64, u64p, u64p]),
     "pirgpu_set_transparent_policy": (C.c_int, [C.c_void_p, C.c_int]),
     "pirgpu_zero_plaintexts": (C.c_uint64, [C.c_void_p]),
     "pirgpu_set_remote_zero_plaintexts": (C.c_int, [C.c_void_p, C.c_uint64]),

@@ -1654,6 +1654,189 @@ int pirgpu_db_read_plaintext(pirgpu_ctx* c, uint64_t pt_index, uint64_t* out) {
   });
 }
 
+// In-place updates (pirgpu_db_update_items / _plaintexts).  The touched plaintexts (sorted by local index) go through
+// the device in chunks: [fetch residue 0 of the old NTT form (staging row, or db_gather from the operand layout) ->
+// inverse NTT -> db_splice] (item updates only) -> lift + forward NTT (db_encode) into a compact [n][k][N] buffer ->
+// staging rows and the touched columns of the operand layout (db_pack_update).  No repack: packed_valid is kept.
+}  // extern "C"
+
+namespace {
+
+struct DevScratch {
+  void* p = nullptr;
+  ~DevScratch() {
+    if (p) (void)hipFree(p);
+  }
+  template <typename T>
+  T* get(size_t bytes) {
+    HIP_TRY(hipMalloc(&p, std::max<size_t>(bytes, 1)));
+    return static_cast<T*>(p);
+  }
+};
+
+struct PtUpdate {
+  uint64_t local;                                     // local plaintext index
+  const uint64_t* coeffs = nullptr;                   // update_plaintexts: its new coefficient row
+  std::vector<std::pair<uint32_t, uint64_t>> items;   // update_items: (item slot in the plaintext, row of `items`)
+};
+
+// Waits for every queued use of the database (as pirgpu_db_finalize does before it frees the staging copy).
+void quiesce(pirgpu_ctx* c) {
+  sync_batch_streams(c);
+  HIP_TRY(hipStreamSynchronize(c->stream));
+}
+
+void require_loaded(pirgpu_ctx* c) {
+  if (c->n_loaded != c->pt_end - c->pt_begin || c->pt_end == c->pt_begin)
+    throw Fail{PIRGPU_FAILED_PRECONDITION, "database not fully loaded (the first load is pirgpu_db_load_items / _coeffs)"};
+}
+
+void apply_update(pirgpu_ctx* c, const std::vector<PtUpdate>& pts, const uint8_t* items, uint32_t item_bytes) {
+  const uint32_t N = c->N, kN = c->k * c->N;
+  const bool splice = items != nullptr;
+  const uint64_t ipp = splice ? c->prm.items_per_plaintext : 0, bpp = ipp * item_bytes;
+  const bool to_packed = c->mfma_on && c->packed_valid && c->d_dbp;
+  // chunks of at most 64 MB of device scratch (pirgpu_db_load_items' upload size) and 65535 units (grid.y)
+  const uint64_t per_pt = (uint64_t)N * 8 + (uint64_t)kN * 8 + bpp + ipp + 8 + 4 + sizeof(DbUnit);
+  const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>((64ull << 20) / per_pt, 65535));
+  const uint64_t cap = std::min<uint64_t>(chunk, pts.size());
+  DevScratch s_coef, s_enc, s_loc, s_units, s_img, s_upd, s_nz;
+  uint64_t* d_coef = s_coef.get<uint64_t>(cap * N * 8);
+  uint64_t* d_enc = s_enc.get<uint64_t>(cap * kN * 8);
+  uint64_t* d_loc = s_loc.get<uint64_t>(cap * 8);
+  DbUnit* d_units = s_units.get<DbUnit>(cap * sizeof(DbUnit));
+  uint8_t* d_img = splice ? s_img.get<uint8_t>(cap * bpp) : nullptr;
+  uint8_t* d_upd = splice ? s_upd.get<uint8_t>(cap * ipp) : nullptr;
+  uint32_t* d_nz = splice ? s_nz.get<uint32_t>(cap * 4) : nullptr;
+  std::vector<uint64_t> loc, coef_rows;
+  std::vector<DbUnit> units;
+  std::vector<uint8_t> img, upd;
+  std::vector<uint32_t> nz;
+  for (uint64_t b = 0; b < pts.size(); b += chunk) {
+    const uint64_t n = std::min<uint64_t>(chunk, pts.size() - b);
+    loc.resize(n);
+    units.clear();
+    for (uint64_t i = 0; i < n; ++i) {
+      const uint64_t l = pts[b + i].local;
+      loc[i] = l;
+      if (!to_packed) continue;
+      const uint32_t r = (uint32_t)(l / c->scan_cols), col = (uint32_t)(l % c->scan_cols), kg = col / 16;
+      if (units.empty() || units.back().r != r || units.back().kg != kg) units.push_back(DbUnit{r, kg, 0u, (uint32_t)i});
+      units.back().mask |= 1u << (col % 16);
+    }
+    HIP_TRY(hipMemcpyAsync(d_loc, loc.data(), n * 8, hipMemcpyHostToDevice, c->stream));
+    if (!units.empty())
+      HIP_TRY(hipMemcpyAsync(d_units, units.data(), units.size() * sizeof(DbUnit), hipMemcpyHostToDevice, c->stream));
+    if (splice) {
+      img.assign(n * bpp, 0);
+      upd.assign(n * ipp, 0);
+      for (uint64_t i = 0; i < n; ++i)
+        for (const auto& it : pts[b + i].items) {
+          memcpy(&img[i * bpp + (uint64_t)it.first * item_bytes], items + it.second * item_bytes, item_bytes);
+          upd[i * ipp + it.first] = 1;
+        }
+      HIP_TRY(hipMemcpyAsync(d_img, img.data(), n * bpp, hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(hipMemcpyAsync(d_upd, upd.data(), n * ipp, hipMemcpyHostToDevice, c->stream));
+      // (1) residue 0 of the old NTT form
+      if (c->d_db)
+        HIP_TRY(launch_copy_rows(c->stream, c->d_db, d_coef, d_loc, nullptr, n, N, kN, N));
+      else
+        HIP_TRY(launch_db_gather(c->stream, c->dp, c->mg, c->d_dbp, d_units, (uint32_t)units.size(), d_coef, N));
+      // (2) back to coefficients (residues < t < q_0 carry the plaintext exactly), (3) splice
+      HIP_TRY(c->ops->ntt_batch(c->stream, c->mode, c->dp, d_coef, n, 1, 0, true));
+      HIP_TRY(launch_db_splice(c->stream, c->dp, d_coef, N, d_img, d_upd, n, bpp, item_bytes, c->bits, d_nz));
+    } else {
+      coef_rows.resize(n * N);
+      for (uint64_t i = 0; i < n; ++i) memcpy(&coef_rows[i * N], pts[b + i].coeffs, (size_t)N * 8);
+      HIP_TRY(hipMemcpyAsync(d_coef, coef_rows.data(), n * N * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    // (4) lift + forward NTT, (5) write back
+    HIP_TRY(c->ops->db_encode(c->stream, c->mode, c->dp, c->k, d_coef, nullptr, 0, 0, c->bits, n, d_enc));
+    if (c->d_db) HIP_TRY(launch_copy_rows(c->stream, d_enc, c->d_db, nullptr, d_loc, n, kN, kN, kN));
+    if (to_packed)
+      HIP_TRY(launch_db_pack_update(c->stream, c->dp, c->mg, d_enc, d_units, (uint32_t)units.size(), c->d_dbp, kN,
+                                    c->slot0, c->nslots));
+    if (splice) {
+      nz.resize(n);
+      HIP_TRY(hipMemcpyAsync(nz.data(), d_nz, n * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint64_t i = 0; i < n; ++i)
+      note_plaintext(c, loc[i],
+                     splice ? nz[i] == 0
+                            : all_zero_bytes(reinterpret_cast<const uint8_t*>(pts[b + i].coeffs), (size_t)N * 8));
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int pirgpu_db_update_items(pirgpu_ctx* c, uint64_t n, const uint64_t* item_indices, const uint8_t* items,
+                           uint32_t bytes_per_item) {
+  return guarded(c, [&]() -> int {
+    const pirgpu_params& p = c->prm;
+    require_loaded(c);
+    if (bytes_per_item != p.bytes_per_item || p.items_per_plaintext == 0)
+      return fail(c, PIRGPU_INVALID_ARGUMENT, "item size does not match parameters");
+    if (!n) return PIRGPU_OK;
+    if (!item_indices || !items) return fail(c, PIRGPU_INVALID_ARGUMENT, "null item indices or items");
+    for (uint64_t i = 0; i < n; ++i)
+      if (item_indices[i] >= p.num_items)
+        return fail(c, PIRGPU_INVALID_ARGUMENT, "item index " + std::to_string(item_indices[i]) + " out of range (" +
+                                                    std::to_string(p.num_items) + " items)");
+    if (c->slot_sharded && !c->d_db)
+      return fail(c, PIRGPU_FAILED_PRECONDITION,
+                  "this slot shard released its staging copy: it holds too little of each plaintext to keep the items "
+                  "an update does not replace (pirgpu_db_update_plaintexts still works)");
+    const uint64_t ipp = p.items_per_plaintext;
+    std::map<uint64_t, uint64_t> last;   // item -> row of `items` (a later entry wins)
+    for (uint64_t i = 0; i < n; ++i) {
+      const uint64_t pt = item_indices[i] / ipp;
+      if (pt >= c->pt_begin && pt < c->pt_end) last[item_indices[i]] = i;   // other row shards' items are skipped
+    }
+    std::vector<PtUpdate> pts;
+    for (const auto& e : last) {
+      const uint64_t local = e.first / ipp - c->pt_begin;
+      if (pts.empty() || pts.back().local != local) pts.push_back(PtUpdate{local});
+      pts.back().items.emplace_back((uint32_t)(e.first % ipp), e.second);
+    }
+    if (pts.empty()) return PIRGPU_OK;
+    quiesce(c);
+    apply_update(c, pts, items, bytes_per_item);
+    return PIRGPU_OK;
+  });
+}
+
+int pirgpu_db_update_plaintexts(pirgpu_ctx* c, uint64_t n, const uint64_t* pt_indices, const uint64_t* coeffs) {
+  return guarded(c, [&]() -> int {
+    require_loaded(c);
+    if (!n) return PIRGPU_OK;
+    if (!pt_indices || !coeffs) return fail(c, PIRGPU_INVALID_ARGUMENT, "null plaintext indices or coefficients");
+    const uint64_t t = c->prm.plain_modulus;
+    for (uint64_t i = 0; i < n; ++i) {
+      if (pt_indices[i] >= c->P)
+        return fail(c, PIRGPU_INVALID_ARGUMENT, "plaintext index " + std::to_string(pt_indices[i]) + " out of range (" +
+                                                    std::to_string(c->P) + " plaintexts)");
+      const uint64_t* row = coeffs + i * c->N;
+      for (uint32_t x = 0; x < c->N; ++x)
+        if (row[x] >= t) return fail(c, PIRGPU_INVALID_ARGUMENT, "coefficient not below the plain modulus");
+    }
+    std::map<uint64_t, uint64_t> last;   // local plaintext -> row of `coeffs` (a later entry wins)
+    for (uint64_t i = 0; i < n; ++i)
+      if (pt_indices[i] >= c->pt_begin && pt_indices[i] < c->pt_end) last[pt_indices[i] - c->pt_begin] = i;
+    std::vector<PtUpdate> pts;
+    for (const auto& e : last) {
+      pts.push_back(PtUpdate{e.first});
+      pts.back().coeffs = coeffs + e.second * c->N;
+    }
+    if (pts.empty()) return PIRGPU_OK;
+    quiesce(c);
+    apply_update(c, pts, nullptr, 0);
+    return PIRGPU_OK;
+  });
+}
+
 // ======================================================================================================================
 // [6] C ABI: Galois keys and per-client key sets
 // ======================================================================================================================

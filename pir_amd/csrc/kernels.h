@@ -120,6 +120,17 @@ const NttOps* ntt_ops_for(uint32_t N, int pack_bytes = 5);  // nullptr for unsup
 
 hipError_t launch_ntt_reorder(hipStream_t st, uint32_t N, const uint64_t* in, uint64_t* out, uint64_t n_polys,
                               bool to_device, bool as_f64);
+// rows of `words` words: dst[dst_idx ? dst_idx[i] : i] = src[src_idx ? src_idx[i] : i] for i < n (rows src_stride /
+// dst_stride words apart) -- the staging copy's touched plaintexts in and out of an update's compact buffers
+hipError_t launch_copy_rows(hipStream_t st, const uint64_t* src, uint64_t* dst, const uint64_t* src_idx,
+                            const uint64_t* dst_idx, uint64_t n, uint64_t words, uint64_t src_stride, uint64_t dst_stride);
+// coefficient-level splice of an item update: coef[n][N] holds residue 0 of the touched plaintexts in coefficient form;
+// the plain lift is undone, the bits [8 o, 8 o + 8 item_bytes) of every updated item (upd[i][s] != 0: item slot s of
+// plaintext i, new bytes at img[i][s * item_bytes ..]) are replaced in the MSB-first bits-wide coefficient stream, every
+// other bit is kept.  coef receives the coefficients (< t), nonzero[i] whether plaintext i has a non-zero one.
+hipError_t launch_db_splice(hipStream_t st, const DevParams* P, uint64_t* coef, uint32_t N, const uint8_t* img,
+                            const uint8_t* upd, uint64_t n, uint64_t bytes_per_pt, uint32_t item_bytes, uint32_t bits,
+                            uint32_t* nonzero);
 // u64 residues < 2^40 <-> 5 bytes each (4 words <-> 5 dwords); words must be a multiple of 4
 hipError_t launch_pack40x4(hipStream_t st, const uint64_t* in, uint32_t* out, uint64_t words);
 hipError_t launch_unpack40x4(hipStream_t st, const uint32_t* in, uint64_t* out, uint64_t words);
@@ -181,6 +192,20 @@ hipError_t launch_db_pack(hipStream_t st, const DevParams* P, const MfmaGeom& gm
                           uint32_t rows, uint32_t cols, uint32_t kN, uint32_t slot0 = 0, uint32_t nslots = 0);
 hipError_t launch_db_unpack(hipStream_t st, const DevParams* P, const MfmaGeom& gm, const uint8_t* dbp, uint64_t* out,
                             uint32_t row, uint32_t col, uint32_t kN);
+// In-place database updates (pirgpu_db_update_*).  One unit = one touched (row, column group) of the operand layout:
+// `mask` holds its touched columns (bit c: column 16 kg + c); the touched plaintexts of a unit are numbered out0,
+// out0 + 1, ... in column order (the plaintext rows of the update's compact buffers).
+struct DbUnit {
+  uint32_t r, kg, mask, out0;
+};
+// residue 0 (slots [0, N)) of every touched plaintext back from the operand layout: out[plaintext][N], in [0, q_0)
+hipError_t launch_db_gather(hipStream_t st, const DevParams* P, const MfmaGeom& gm, const uint8_t* dbp,
+                            const DbUnit* units, uint32_t n_units, uint64_t* out, uint32_t N);
+// the partial twin of launch_db_pack: enc[plaintext][kN] (device order) into the touched columns of the operand layout,
+// slots [slot0, slot0 + nslots) only; every other byte keeps its value
+hipError_t launch_db_pack_update(hipStream_t st, const DevParams* P, const MfmaGeom& gm, const uint64_t* enc,
+                                 const DbUnit* units, uint32_t n_units, uint8_t* dbp, uint32_t kN, uint32_t slot0,
+                                 uint32_t nslots);
 // map: the output cut into per-rank pieces by slot ranges (nullptr: one piece)
 hipError_t launch_sel_pack(hipStream_t st, const DevParams* P, const MfmaGeom& gm, const MfmaPtrs& sv, uint32_t nq,
                            uint8_t* selp, uint32_t cols, uint32_t kN, bool sel_f64 = false, const SliceMap* map = nullptr);

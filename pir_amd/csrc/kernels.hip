@@ -1020,4 +1020,75 @@ hipError_t launch_reduce_splits(hipStream_t st, const DevParams* P, const uint64
   return hipSuccess;
 }
 
+// ------------------------------------------------------------------ in-place database updates (pirgpu_db_update_*)
+
+// grid = rows (capped, grid-stride), block 256: one row of `words` words per workgroup pass
+__global__ void __launch_bounds__(256)
+copy_rows_kernel(const uint64_t* __restrict__ src, uint64_t* __restrict__ dst, const uint64_t* __restrict__ src_idx,
+                 const uint64_t* __restrict__ dst_idx, uint64_t n, uint64_t words, uint64_t src_stride,
+                 uint64_t dst_stride) {
+  for (uint64_t i = blockIdx.x; i < n; i += gridDim.x) {
+    const uint64_t* s = src + (src_idx ? src_idx[i] : i) * src_stride;
+    uint64_t* d = dst + (dst_idx ? dst_idx[i] : i) * dst_stride;
+    for (uint64_t w = threadIdx.x; w < words; w += 256) d[w] = s[w];
+  }
+}
+
+// One workgroup per touched plaintext.  Coefficient c holds the bits [c bits, (c + 1) bits) of the plaintext's MSB-first
+// bit stream (db_encode_kernel); byte b of the stream belongs to item slot b / item_bytes.  Bits of bytes at or past
+// bytes_per_pt (the padding behind the last item slot) and coefficient bits at or above `bits` are never touched.
+__global__ void __launch_bounds__(256)
+db_splice_kernel(const DevParams* __restrict__ P, uint64_t* __restrict__ coef, uint32_t N,
+                 const uint8_t* __restrict__ img, const uint8_t* __restrict__ upd, uint64_t bytes_per_pt,
+                 uint32_t item_bytes, uint32_t bits, uint32_t* __restrict__ nonzero) {
+  const uint64_t i = blockIdx.x;
+  const uint64_t ipp = bytes_per_pt / item_bytes;
+  uint64_t* cp = coef + i * N;
+  const uint8_t* im = img + i * bytes_per_pt;
+  const uint8_t* up = upd + i * ipp;
+  const uint64_t q0 = P->mod[0].q, t = P->t, thr = P->plain_thr;
+  const uint64_t end_bit = bytes_per_pt * 8;
+  int nz = 0;
+  for (uint32_t c = threadIdx.x; c < N; c += 256) {
+    const uint64_t r = cp[c];
+    // undo the plain lift of db_encode_kernel: m >= thr was stored as m + (q_0 - t), which is >= thr as well
+    uint64_t v = r >= thr ? r - (q0 - t) : r;
+    const uint64_t b0 = (uint64_t)c * bits, b1 = b0 + bits;
+    const uint64_t e1 = b1 < end_bit ? b1 : end_bit;
+    for (uint64_t by = b0 >> 3; by * 8 < e1; ++by) {
+      if (!up[by / item_bytes]) continue;
+      const uint64_t lo = by * 8 > b0 ? by * 8 : b0, hi = by * 8 + 8 < e1 ? by * 8 + 8 : e1;
+      const uint32_t len = (uint32_t)(hi - lo), sh = (uint32_t)(b1 - hi);
+      const uint64_t m = ((1ull << len) - 1) << sh;
+      const uint64_t val = (uint64_t)((im[by] >> (by * 8 + 8 - hi)) & ((1u << len) - 1)) << sh;
+      v = (v & ~m) | val;
+    }
+    cp[c] = v;
+    nz |= v != 0;
+  }
+  nz = __syncthreads_or(nz);
+  if (threadIdx.x == 0) nonzero[i] = nz ? 1u : 0u;
+}
+
+hipError_t launch_copy_rows(hipStream_t st, const uint64_t* src, uint64_t* dst, const uint64_t* src_idx,
+                            const uint64_t* dst_idx, uint64_t n, uint64_t words, uint64_t src_stride, uint64_t dst_stride) {
+  if (!n || !words) return hipSuccess;
+  const uint32_t grid = (uint32_t)(n < 65536 ? n : 65536);
+  hipLaunchKernelGGL(copy_rows_kernel, dim3(grid), dim3(256), 0, st, src, dst, src_idx, dst_idx, n, words, src_stride,
+                     dst_stride);
+  PIRGPU_LAUNCH_CHECK();
+  return hipSuccess;
+}
+
+hipError_t launch_db_splice(hipStream_t st, const DevParams* P, uint64_t* coef, uint32_t N, const uint8_t* img,
+                            const uint8_t* upd, uint64_t n, uint64_t bytes_per_pt, uint32_t item_bytes, uint32_t bits,
+                            uint32_t* nonzero) {
+  if (!n) return hipSuccess;
+  if (!item_bytes || !bits || bits > 64 || n > 0x7fffffffull) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(db_splice_kernel, dim3((uint32_t)n), dim3(256), 0, st, P, coef, N, img, upd, bytes_per_pt,
+                     item_bytes, bits, nonzero);
+  PIRGPU_LAUNCH_CHECK();
+  return hipSuccess;
+}
+
 }  // namespace pirgpu

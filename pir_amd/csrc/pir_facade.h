@@ -136,6 +136,23 @@ class PIRDatabase {
                                                      rawdb.size(), params_->bytes_per_item));
   }
 
+  // No reference counterpart (database.cpp:84-110 only repopulates): items[i] replaces item indices[i] in place
+  // (pirgpu_db_update_items); a later entry wins, items outside this context's row shard are skipped.
+  Status update_items(const std::vector<uint64_t>& indices, const std::vector<std::string>& items) {
+    if (indices.size() != items.size())
+      return InvalidArgumentError(std::to_string(items.size()) + " items for " + std::to_string(indices.size()) +
+                                  " indices");
+    std::string flat;
+    flat.reserve(items.size() * params_->bytes_per_item);
+    for (const auto& s : items) {
+      if (s.size() != params_->bytes_per_item) return InvalidArgumentError("item size does not match parameters");
+      flat += s;
+    }
+    return detail::FromRc(ctx_, pirgpu_db_update_items(ctx_, indices.size(), indices.data(),
+                                                       reinterpret_cast<const uint8_t*>(flat.data()),
+                                                       params_->bytes_per_item));
+  }
+
   // database.cpp:290-316 (selection vector in coefficient form; it is not mutated here)
   StatusOr<std::vector<Ciphertext>> multiply(const std::vector<Ciphertext>& selection_vector) const {
     const size_t words = CtWords();

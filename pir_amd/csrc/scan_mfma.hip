@@ -217,6 +217,107 @@ db_unpack_kernel(const DevParams* __restrict__ P, const uint8_t* __restrict__ db
   out[j] = v < 0 ? (uint64_t)(v + (int64_t)q) : (uint64_t)v;
 }
 
+// byte c (0..15) of a 16-byte digit row held as four dwords / nibble c of an 8-byte TOP4 row (pack_top4's order)
+__device__ __forceinline__ int row_byte(const uint32_t (&w)[4], int c) { return (int8_t)(w[c >> 2] >> (8 * (c & 3))); }
+__device__ __forceinline__ int row_nibble(const uint32_t (&w)[2], int c) {
+  const int nib = (int)(w[c >> 3] >> (8 * (c & 3) + ((c & 4) ? 4 : 0))) & 0xF;
+  return nib >= 8 ? nib - 16 : nib;
+}
+
+// Residue 0 of many plaintexts back from the operand layout (in-place updates with the staging copy released): one
+// thread per (unit, slot j < N) reads the unit's L digit rows -- 16 bytes each, 8 for the TOP4 nibble row -- once and
+// extracts every touched column from them (db_unpack_kernel reads one byte per digit and slot for ONE plaintext).
+// grid = (N / 256, units); out[out0 + rank][j], rank = the column's place among the unit's touched columns.
+template <int L, bool TOP4>
+__global__ void __launch_bounds__(256)
+db_gather_kernel(const DevParams* __restrict__ P, const uint8_t* __restrict__ dbp, const DbUnit* __restrict__ units,
+                 uint64_t* __restrict__ out, uint32_t N, uint32_t RT, uint32_t KG, uint32_t GC) {
+  constexpr uint32_t TB = tile_bytes(L, TOP4);
+  constexpr int LF = TOP4 ? L - 1 : L;
+  const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= N) return;
+  const DbUnit u = units[blockIdx.y];
+  const uint64_t q = P->mod[0].q;
+  const uint8_t* blk = dbp + db_tile_offset(j, u.r >> 4, u.kg, 0, TB, RT, KG, GC);
+  const uint32_t r16 = u.r & 15;
+  uint32_t w[LF][4];
+#pragma unroll
+  for (int a = 0; a < LF; ++a) {
+    const v4i v = *reinterpret_cast<const v4i*>(blk + (size_t)a * 256 + r16 * 16);
+#pragma unroll
+    for (int x = 0; x < 4; ++x) w[a][x] = (uint32_t)v[x];
+  }
+  uint32_t w4[2] = {0, 0};
+  if constexpr (TOP4) {
+    const v2i v = *reinterpret_cast<const v2i*>(blk + (size_t)(L - 1) * 256 + r16 * 8);
+    w4[0] = (uint32_t)v[0];
+    w4[1] = (uint32_t)v[1];
+  }
+  uint32_t rank = 0;
+#pragma unroll
+  for (int cc = 0; cc < 16; ++cc) {
+    if (!((u.mask >> cc) & 1)) continue;
+    int64_t v = TOP4 ? row_nibble(w4, cc) : row_byte(w[L - 1], cc);
+#pragma unroll
+    for (int a = L - 2; a >= 0; --a) v = v * 256 + row_byte(w[a], cc);
+    out[(size_t)(u.out0 + rank) * N + j] = v < 0 ? (uint64_t)(v + (int64_t)q) : (uint64_t)v;
+    ++rank;
+  }
+}
+
+// The partial twin of db_pack_kernel: one thread per (unit, local slot) reads the unit's digit rows, replaces the
+// touched columns with the digits of enc[out0 + rank][j] and writes the rows back.  A unit is one (row, column group) and
+// a thread one slot, so no byte -- a TOP4 byte holds columns i and i + 4 -- is written by two threads.
+// grid = (nslots / 256, units); slots [slot0, slot0 + nslots) at local index j - slot0.
+template <int L, bool TOP4>
+__global__ void __launch_bounds__(256)
+db_pack_update_kernel(const DevParams* __restrict__ P, const uint64_t* __restrict__ enc, const DbUnit* __restrict__ units,
+                      uint8_t* __restrict__ dbp, uint32_t kN, uint32_t slot0, uint32_t nslots, uint32_t RT, uint32_t KG,
+                      uint32_t GC) {
+  constexpr uint32_t TB = tile_bytes(L, TOP4);
+  constexpr int LF = TOP4 ? L - 1 : L;
+  const uint32_t jl = blockIdx.x * 256 + threadIdx.x;
+  if (jl >= nslots) return;
+  const uint32_t j = slot0 + jl;
+  const DbUnit u = units[blockIdx.y];
+  const uint64_t q = P->mod[j >> P->logN].q;
+  uint8_t* blk = dbp + db_tile_offset(jl, u.r >> 4, u.kg, 0, TB, RT, KG, GC);
+  const uint32_t r16 = u.r & 15;
+  uint32_t w[LF][4];
+#pragma unroll
+  for (int a = 0; a < LF; ++a) {
+    const v4i v = *reinterpret_cast<const v4i*>(blk + (size_t)a * 256 + r16 * 16);
+#pragma unroll
+    for (int x = 0; x < 4; ++x) w[a][x] = (uint32_t)v[x];
+  }
+  uint32_t w4[2] = {0, 0};
+  if constexpr (TOP4) {
+    const v2i v = *reinterpret_cast<const v2i*>(blk + (size_t)(L - 1) * 256 + r16 * 8);
+    w4[0] = (uint32_t)v[0];
+    w4[1] = (uint32_t)v[1];
+  }
+  uint32_t rank = 0;
+#pragma unroll
+  for (int cc = 0; cc < 16; ++cc) {
+    if (!((u.mask >> cc) & 1)) continue;
+    int8_t d[L];
+    to_digits<L, TOP4>(enc[(size_t)(u.out0 + rank) * kN + j], q, d);
+    ++rank;
+    const uint32_t sh = 8 * (cc & 3);
+#pragma unroll
+    for (int a = 0; a < LF; ++a) w[a][cc >> 2] = (w[a][cc >> 2] & ~(0xFFu << sh)) | ((uint32_t)(uint8_t)d[a] << sh);
+    if constexpr (TOP4) {
+      const uint32_t ns = sh + ((cc & 4) ? 4 : 0);
+      w4[cc >> 3] = (w4[cc >> 3] & ~(0xFu << ns)) | (((uint32_t)d[L - 1] & 0xFu) << ns);
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < LF; ++a)
+    *reinterpret_cast<v4i*>(blk + (size_t)a * 256 + r16 * 16) = v4i{(int)w[a][0], (int)w[a][1], (int)w[a][2], (int)w[a][3]};
+  if constexpr (TOP4)
+    *reinterpret_cast<v2i*>(blk + (size_t)(L - 1) * 256 + r16 * 8) = v2i{(int)w4[0], (int)w4[1]};
+}
+
 __device__ __forceinline__ v4i load_tile(const uint8_t* p) {
   return __builtin_nontemporal_load(reinterpret_cast<const v4i*>(p));
 }
@@ -546,6 +647,55 @@ hipError_t launch_db_unpack(hipStream_t st, const DevParams* P, const MfmaGeom& 
     case 7: hipLaunchKernelGGL((db_unpack_kernel<7, false>), grid, dim3(256), 0, st, P, dbp, out, row, col, kN, gm.RT, gm.KG, gm.GC); break;
     default: return hipErrorInvalidValue;
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_db_gather(hipStream_t st, const DevParams* P, const MfmaGeom& gm, const uint8_t* dbp,
+                            const DbUnit* units, uint32_t n_units, uint64_t* out, uint32_t N) {
+  if (!n_units) return hipSuccess;
+  if (n_units > 65535) return hipErrorInvalidValue;
+  const dim3 grid((N + 255) / 256, n_units);
+#define PIRGPU_DBGATHER(L_, T_) \
+  hipLaunchKernelGGL((db_gather_kernel<L_, T_>), grid, dim3(256), 0, st, P, dbp, units, out, N, gm.RT, gm.KG, gm.GC)
+  switch (gm.L) {
+    case 5:
+      if (gm.top4) PIRGPU_DBGATHER(5, true);
+      else PIRGPU_DBGATHER(5, false);
+      break;
+    case 6:
+      if (gm.top4) PIRGPU_DBGATHER(6, true);
+      else PIRGPU_DBGATHER(6, false);
+      break;
+    case 7: PIRGPU_DBGATHER(7, false); break;
+    default: return hipErrorInvalidValue;
+  }
+#undef PIRGPU_DBGATHER
+  return hipGetLastError();
+}
+
+hipError_t launch_db_pack_update(hipStream_t st, const DevParams* P, const MfmaGeom& gm, const uint64_t* enc,
+                                 const DbUnit* units, uint32_t n_units, uint8_t* dbp, uint32_t kN, uint32_t slot0,
+                                 uint32_t nslots) {
+  if (!n_units) return hipSuccess;
+  if (nslots == 0) nslots = kN - slot0;
+  if (n_units > 65535 || slot0 % 16 || nslots % 16 || slot0 + nslots > kN) return hipErrorInvalidValue;
+  const dim3 grid((nslots + 255) / 256, n_units);
+#define PIRGPU_DBPACKUPD(L_, T_)                                                                                    \
+  hipLaunchKernelGGL((db_pack_update_kernel<L_, T_>), grid, dim3(256), 0, st, P, enc, units, dbp, kN, slot0, nslots, \
+                     gm.RT, gm.KG, gm.GC)
+  switch (gm.L) {
+    case 5:
+      if (gm.top4) PIRGPU_DBPACKUPD(5, true);
+      else PIRGPU_DBPACKUPD(5, false);
+      break;
+    case 6:
+      if (gm.top4) PIRGPU_DBPACKUPD(6, true);
+      else PIRGPU_DBPACKUPD(6, false);
+      break;
+    case 7: PIRGPU_DBPACKUPD(7, false); break;
+    default: return hipErrorInvalidValue;
+  }
+#undef PIRGPU_DBPACKUPD
   return hipGetLastError();
 }
 

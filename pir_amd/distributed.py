@@ -231,6 +231,15 @@ def sync_zero_plaintexts(server, dist, world: int, comm: Optional[Comm] = None, 
     return total
 
 
+def update_items(server, indices, items, dist, world: int, comm: Optional[Comm] = None, torch=None, device=None) -> int:
+    """In-place item update of a row-sharded database (PIRDatabase.update_items): every rank passes the SAME full list,
+    the library skips the items outside the rank's shard; then the zero-plaintext counts are exchanged again
+    (sync_zero_plaintexts), so that all ranks keep taking the same transparent-ciphertext decision.  Collective: every
+    rank must call it.  Returns the total zero plaintexts."""
+    server.db.update_items(indices, items)
+    return sync_zero_plaintexts(server, dist, world, comm=comm, torch=torch, device=device)
+
+
 def run_batch_query_parallel(server, sv_all, replies, dist, rank: int, world: int, comm: Optional[Comm] = None) -> None:
     """One step over a staged batch on `world` GPUs holding row shards, exchanging whole u64 selection vectors
     (any d, any scan kernel; 2 k N 8 dim_sum bytes per query to every rank):

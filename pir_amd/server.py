@@ -44,6 +44,18 @@ def _ptr(a: np.ndarray):
     return a.ctypes.data_as(capi.u64p)
 
 
+def _indices(indices) -> np.ndarray:
+    """1-D array of non-negative integer indices as uint64 (never empty: the ABI is given a valid pointer)."""
+    a = np.asarray(indices)
+    if a.ndim != 1 or (a.size and a.dtype.kind not in "ui"):
+        raise PirGpuError(3, "indices must be a 1-D sequence of integers")
+    if a.size and a.min() < 0:
+        raise PirGpuError(3, "indices must be non-negative")
+    out = np.zeros(max(a.size, 1), dtype=np.uint64)
+    out[: a.size] = a.astype(np.uint64)
+    return out[: a.size] if a.size else out[:0]
+
+
 class PIRDatabase:
     """reference database.h:37-133.  Owns the device context and the HBM-resident encoded database."""
 
@@ -137,6 +149,45 @@ class PIRDatabase:
     def finalize(self, release_staging: bool = False) -> None:
         """Pack the operand-layout copy now; optionally free the u64 staging copy (no reloads afterwards)."""
         self._check(self.lib.pirgpu_db_finalize(self._h, 1 if release_staging else 0))
+
+    def update_items(self, indices, items) -> None:
+        """Replace items in place (pirgpu_db_update_items; no reference counterpart): items[i] is the new value of item
+        indices[i], as a uint8 array [n, bytes_per_item] or a sequence of n byte strings.  A later entry wins; indices
+        outside this context's row shard are skipped.  Only the touched plaintexts are re-encoded."""
+        idx = _indices(indices)
+        width = self.params.bytes_per_item
+        if isinstance(items, np.ndarray):
+            if items.dtype != np.uint8 or items.ndim != 2 or items.shape != (idx.shape[0], width):
+                raise PirGpuError(3, "items must be a uint8 array of shape [%d, %d], got %s %s"
+                                  % (idx.shape[0], width, items.dtype, list(items.shape)))
+            buf = np.ascontiguousarray(items)
+        else:
+            rows = list(items)
+            if len(rows) != idx.shape[0]:
+                raise PirGpuError(3, "%d items for %d indices" % (len(rows), idx.shape[0]))
+            if any(len(it) != width for it in rows):
+                raise PirGpuError(3, "item size does not match parameters")
+            buf = np.frombuffer(b"".join(bytes(it) for it in rows), dtype=np.uint8)
+        if buf.size == 0:
+            buf = np.zeros(1, dtype=np.uint8)
+        self._check(self.lib.pirgpu_db_update_items(self._h, idx.shape[0], _ptr(idx), buf.ctypes.data_as(capi.u8p),
+                                                    width))
+
+    def update_plaintexts(self, pt_indices, coeffs) -> None:
+        """Replace whole plaintexts given as coefficient rows (< t, zero padded to N; pirgpu_db_update_plaintexts)."""
+        idx = _indices(pt_indices)
+        rows = list(coeffs)
+        if len(rows) != idx.shape[0]:
+            raise PirGpuError(3, "%d coefficient rows for %d plaintext indices" % (len(rows), idx.shape[0]))
+        arr = np.zeros((max(len(rows), 1), self.N), dtype=np.uint64)
+        for i, row in enumerate(rows):
+            row = np.asarray(row)
+            if row.ndim != 1 or row.shape[0] > self.N:
+                raise PirGpuError(3, "a coefficient row must be 1-D with at most %d entries" % self.N)
+            if row.size and (row.dtype.kind not in "ui" or row.min() < 0):
+                raise PirGpuError(3, "coefficients must be non-negative integers")
+            arr[i, : row.shape[0]] = row.astype(np.uint64)
+        self._check(self.lib.pirgpu_db_update_plaintexts(self._h, idx.shape[0], _ptr(idx), _ptr(arr)))
 
     def read_plaintext(self, index: int) -> np.ndarray:
         out = np.empty((self.k, self.N), dtype=np.uint64)
