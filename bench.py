@@ -10,11 +10,16 @@ queries are expanded together and share one pass over the database (the digit-sl
 int8-MFMA scan serves 8 queries per pass); two groups alternate on two lanes so the
 bandwidth-bound scan of one overlaps the compute-bound expansion of the other; every
 query does the full work.  `value` = queries/s over the timed steps (defaults: 200 steps of 64 queries,
-about 2.3 s of GPU time); the single-query latency (`--batch 1` behaviour, what benchmark.cpp:71-79 times per
-request) is measured as well and reported as `latency_ms_single_query`, and the scan kernel's roofline comes from
-those single-query runs (one scan launch per query, HIP events on the library's stream).
+about 2.3 s of GPU time).
 Workload = BASELINE.json configs[2]: N=4096, 2 RNS primes, DB = 2^20 x 288 B, d=2 (the
 reference's own benchmark parameters, benchmark.cpp:17-23).
+
+A plain run does only what the headline needs: set-up, the W warm-up steps, the K timed steps, --dump-outputs, the
+line.  `--full` adds everything else, in the same line: the single-query latency (`--batch 1` behaviour, what
+benchmark.cpp:71-79 times per request) as `latency_ms_single_query`, the scan kernel's roofline from those
+single-query runs (one scan launch per query, HIP events on the library's stream), the batch scan launch's timings,
+the wire-level, multi-client and reference-benchmark legs, the reference sweep, the CPU baseline, and with several
+GPUs the serial phase times of the sharded step and the replica / hybrid reference legs.
 
 Multi-GPU (launched by torch.distributed.run, one rank per GPU).  The headline `value` is ALWAYS the
 north-star mode: the database SHARDED across the GPUs ("scaling": "strong" -- the same 64 queries per
@@ -42,7 +47,7 @@ and the fastest is the headline (`exchange_autotune`, `config.exchange`):
 DESIGN.md section 7 has the byte counts of the exchange and what bounds each mode.
 
 The GPU leg uses synthetic inputs of the right shape (uniform residues); the
-cpu_baseline leg (rank 0, N=1 only) times the CPU oracle -- the restatement of the
+cpu_baseline leg (--full; rank 0, N=1 only) times the CPU oracle -- the restatement of the
 reference algorithm, built natively on this host -- on the same database / keys /
 query and checks the GPU reply against it bit for bit.
 """
@@ -450,9 +455,15 @@ def main():
                                                          "expansion groups full")
     ap.add_argument("--workers", type=int, default=0, help="queries in flight on one GPU (0 = min(batch, 16): two "
                                                            "groups of 8 share one database pass each and overlap)")
-    ap.add_argument("--latency-runs", type=int, default=30, help="single-query runs for latency + roofline")
+    ap.add_argument("--latency-runs", type=int, default=30, help="single-query runs for latency + roofline (--full)")
     ap.add_argument("--log-items", type=int, default=20, help="database = 2^log_items x 288 B")
     ap.add_argument("--dims", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, everything else the benchmark measures or checks: single-query latency "
+                         "and the scan kernel's roofline, the batch scan launch's timings, the wire-level, multi-client "
+                         "and reference-benchmark legs, the reference sweep, the CPU baseline (--no-cpu-baseline drops "
+                         "it), and with several GPUs the serial phase times and the replica / hybrid reference legs; "
+                         "without it a run does set-up, warm-up, the timed steps, --dump-outputs and the line only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--dist-mode", choices=["both", "rows", "queries"],
                     default=os.environ.get("PIRGPU_DIST_MODE", "both"),
@@ -582,7 +593,7 @@ def main():
     # two groups of 8 alternate on two lanes: 16 working sets, whatever the number of queries this rank expands
     workers = args.workers if args.workers > 0 else (16 if use_dist else min(batch, 16))
     run_rows = (not use_dist) or args.dist_mode in ("both", "rows")
-    run_replicas = use_dist and (world > 1 or force_env == "both") and args.dist_mode in ("both", "queries")
+    run_replicas = args.full and use_dist and (world > 1 or force_env == "both") and args.dist_mode in ("both", "queries")
     # same database, keys and queries on every rank (fixed seeds): query i of the batch is the same everywhere
     raw, keys, queries = synthetic_inputs(pp, n_queries=batch)
     query = queries[0]
@@ -639,24 +650,26 @@ def main():
         if args.exchange == "auto" and world == 2 and not autotune:
             exchange = "replicated"
 
-    # ---- (1) single-query latency + scan-kernel roofline (one scan launch per query)
-    srv.stage_query(query)
-    for _ in range(3):
-        srv.run_staged()
-        if use_dist:
-            D.all_reduce_reply(srv, red1, dist, comm)
-    srv.set_profiling(True)
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.latency_runs):
-        srv.run_staged()
-        if use_dist:
-            D.all_reduce_reply(srv, red1, dist, comm)
-    barrier()
-    latency_ms = (time.perf_counter() - t0) / args.latency_runs * 1e3
-    timings = srv.last_timings()
-    srv.set_profiling(False)
-    single_reply = srv.fetch_reply() if world == 1 else None
+    # ---- (1) --full: single-query latency + scan-kernel roofline (one scan launch per query)
+    latency_ms = timings = single_reply = None
+    if args.full:
+        srv.stage_query(query)
+        for _ in range(3):
+            srv.run_staged()
+            if use_dist:
+                D.all_reduce_reply(srv, red1, dist, comm)
+        srv.set_profiling(True)
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(args.latency_runs):
+            srv.run_staged()
+            if use_dist:
+                D.all_reduce_reply(srv, red1, dist, comm)
+        barrier()
+        latency_ms = (time.perf_counter() - t0) / args.latency_runs * 1e3
+        timings = srv.last_timings()
+        srv.set_profiling(False)
+        single_reply = srv.fetch_reply() if world == 1 else None
 
     # The line is assembled by emit(): at the very end normally, or by the watchdog below if a reference leg stalls
     emit_lock, emitted = threading.Lock(), [False]
@@ -673,12 +686,6 @@ def main():
 
     def emit_line(note):
         ms_per_step = elapsed / args.steps * 1e3
-        u64_bytes = pp.num_pt * k * N * 8          # B_q = num_pt * k * N * 8
-        scan_ms = timings["scan_ms"]
-        achieved = scan_bytes / (scan_ms * 1e-3) / 1e9 if scan_ms > 0 else 0.0
-        import glob
-        traffic, traffic_src, traffic_stale = recorded_traffic(args.config, args.log_items, world, info["single_query_mfma"])
-        compute = recorded_compute()   # VALU-issue roofline of the transform kernels (recorded; withheld when stale)
         if world == 1:
             parallelism = "single GPU" + (" (collective code path forced with one rank)" if use_dist else "")
         elif exchange == "slots":
@@ -707,6 +714,7 @@ def main():
             "timed_blocks": len(headline_blocks), "timed_block_seconds": headline_blocks,
             "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "dtype": "u64", "data": "synthetic",
+            "full": args.full,          # false: the headline only; --full adds the figures and legs below
             "config": {"workload": "N=%d, %d RNS data primes (%s bit | special %d bit), t=24 bit, DB=2^%d x %dB, "
                                    "d=%d, dims=%s, num_pt=%d, %d queries/step (whole job), %d in flight per GPU "
                                    "(BASELINE.json configs[%d])"
@@ -718,53 +726,61 @@ def main():
                        "exchange": exchange, "parallelism": parallelism,
                        "database_copies_in_hbm": "operand layout only (u64 staging released)"
                        if args.dims > 1 and not args.keep_staging else "u64 staging" + (" + operand layout" if info["mfma"] else "")},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS,
-                         "frac_definition": "bytes the kernel must read (packed operand layout) / HIP-event duration / 8 TB/s",
-                         "traffic": traffic,
-                         "traffic_source": traffic_src,
-                         # true: scan_mfma.hip has changed since the PMC passes were taken -- the figure describes an
-                         # older kernel; null: the PMC file carries no source stamp
-                         "traffic_stale": traffic_stale,
-                         "kernel": ("scan_mfma_kernel<%d digits, %d k-steps> (int8 MFMA digit products, 1 query; "
-                                    "the same pass serves up to 8)" % (info["digits"], info["ksteps"])) if info["single_query_mfma"]
-                         else ("scan_mq_kernel<4 rows/wave, 1 query>" if args.dims > 1
-                               else "scan_kernel + reduce_splits (column split)"),
-                         "kernel_ms": scan_ms, "algorithmic_bytes": scan_bytes,
-                         # stored bytes per database residue: L signed base-256 digits, the top one a nibble when the
-                         # moduli allow (36-bit residues: 4.5 instead of 5 -- round 3: 10 % fewer bytes per pass, the
-                         # single-query pass 5-10 % shorter on the same box)
-                         **({"bytes_per_residue": info["digits"] - (0.5 if info.get("top_digit_nibble") else 0.0)}
-                            if info["single_query_mfma"] else {}),
-                         "algorithmic_bytes_definition": "packed operand-layout bytes of this GPU's shard = what one "
-                                                         "launch must read (DESIGN.md section 5)",
-                         "launches_averaged": timings["runs"],
-                         # the launch that serves the headline step: `workgroups` persistent workgroups beside the other
-                         # lane's transform kernels, 8 queries per pass -- bound per CU (loads in flight), not by HBM;
-                         # bytes = the same stored database + the group's packed selectors + its row sums
-                         **({"batch_launch": batch_launch_block(batch_scan, scan_bytes, info, k, N)} if batch_scan else {}),
-                         # d = 1: the selection vector (one ciphertext per plaintext = 2x the database in u64) is read
-                         # by the same launch; SURVEY 8(d)'s B_q leaves it out, so `frac` is a lower bound there
-                         **({"d1_selector_bytes": pp.num_pt * 2 * k * N * 8,
-                             "frac_incl_selectors": (scan_bytes + pp.num_pt * 2 * k * N * 8) / (scan_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
-                             if scan_ms > 0 else 0.0} if args.dims == 1 else {}),
-                         # SURVEY 8(d) prices the scan in u64 residues (num_pt*k*N*8 per query) whatever the stored
-                         # layout; both figures side by side, named
-                         "frac_survey_8d_u64": (u64_bytes / max(world, 1)) / (scan_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if scan_ms > 0 else 0.0,
-                         "survey_8d_u64_equivalent": {
-                             "B_q": u64_bytes,
-                             "single_query_launch_GBps": (u64_bytes / max(world, 1)) / (scan_ms * 1e-3) / 1e9 if scan_ms > 0 else 0.0,
-                             "batched_B_q_times_qps_per_gpu_GBps": u64_bytes * qps / max(world, 1) / 1e9,
-                             "batched_frac_of_one_read_per_query_bound": u64_bytes * qps / max(world, 1) / 1e9 / HBM_PEAK_GBS,
-                             "note": "u64-equivalent rates (SURVEY 8(d) formula); they can exceed the packed-bytes "
-                                     "figure because the operand layout stores L <= 7 bytes per residue and one "
-                                     "pass serves up to 8 queries"}},
-            "roofline_compute": compute,
-            "latency_ms_single_query": round(latency_ms, 4),
-            "single_query_qps": round(1e3 / latency_ms, 1),
-            "phases_ms_single_query": {kk: round(v, 4) for kk, v in timings.items() if kk.endswith("_ms")},
             "db_populate_s": round(t_populate, 2),
         }
+        if args.full:
+            u64_bytes = pp.num_pt * k * N * 8          # B_q = num_pt * k * N * 8
+            scan_ms = timings["scan_ms"]
+            achieved = scan_bytes / (scan_ms * 1e-3) / 1e9 if scan_ms > 0 else 0.0
+            traffic, traffic_src, traffic_stale = recorded_traffic(args.config, args.log_items, world, info["single_query_mfma"])
+            compute = recorded_compute()   # VALU-issue roofline of the transform kernels (recorded; withheld when stale)
+            out.update({
+                "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS,
+                             "frac_definition": "bytes the kernel must read (packed operand layout) / HIP-event duration / 8 TB/s",
+                             "traffic": traffic,
+                             "traffic_source": traffic_src,
+                             # true: scan_mfma.hip has changed since the PMC passes were taken -- the figure describes an
+                             # older kernel; null: the PMC file carries no source stamp
+                             "traffic_stale": traffic_stale,
+                             "kernel": ("scan_mfma_kernel<%d digits, %d k-steps> (int8 MFMA digit products, 1 query; "
+                                        "the same pass serves up to 8)" % (info["digits"], info["ksteps"])) if info["single_query_mfma"]
+                             else ("scan_mq_kernel<4 rows/wave, 1 query>" if args.dims > 1
+                                   else "scan_kernel + reduce_splits (column split)"),
+                             "kernel_ms": scan_ms, "algorithmic_bytes": scan_bytes,
+                             # stored bytes per database residue: L signed base-256 digits, the top one a nibble when the
+                             # moduli allow (36-bit residues: 4.5 instead of 5 -- round 3: 10 % fewer bytes per pass, the
+                             # single-query pass 5-10 % shorter on the same box)
+                             **({"bytes_per_residue": info["digits"] - (0.5 if info.get("top_digit_nibble") else 0.0)}
+                                if info["single_query_mfma"] else {}),
+                             "algorithmic_bytes_definition": "packed operand-layout bytes of this GPU's shard = what one "
+                                                             "launch must read (DESIGN.md section 5)",
+                             "launches_averaged": timings["runs"],
+                             # the launch that serves the headline step: `workgroups` persistent workgroups beside the other
+                             # lane's transform kernels, 8 queries per pass -- bound per CU (loads in flight), not by HBM;
+                             # bytes = the same stored database + the group's packed selectors + its row sums
+                             **({"batch_launch": batch_launch_block(batch_scan, scan_bytes, info, k, N)} if batch_scan else {}),
+                             # d = 1: the selection vector (one ciphertext per plaintext = 2x the database in u64) is read
+                             # by the same launch; SURVEY 8(d)'s B_q leaves it out, so `frac` is a lower bound there
+                             **({"d1_selector_bytes": pp.num_pt * 2 * k * N * 8,
+                                 "frac_incl_selectors": (scan_bytes + pp.num_pt * 2 * k * N * 8) / (scan_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
+                                 if scan_ms > 0 else 0.0} if args.dims == 1 else {}),
+                             # SURVEY 8(d) prices the scan in u64 residues (num_pt*k*N*8 per query) whatever the stored
+                             # layout; both figures side by side, named
+                             "frac_survey_8d_u64": (u64_bytes / max(world, 1)) / (scan_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if scan_ms > 0 else 0.0,
+                             "survey_8d_u64_equivalent": {
+                                 "B_q": u64_bytes,
+                                 "single_query_launch_GBps": (u64_bytes / max(world, 1)) / (scan_ms * 1e-3) / 1e9 if scan_ms > 0 else 0.0,
+                                 "batched_B_q_times_qps_per_gpu_GBps": u64_bytes * qps / max(world, 1) / 1e9,
+                                 "batched_frac_of_one_read_per_query_bound": u64_bytes * qps / max(world, 1) / 1e9 / HBM_PEAK_GBS,
+                                 "note": "u64-equivalent rates (SURVEY 8(d) formula); they can exceed the packed-bytes "
+                                         "figure because the operand layout stores L <= 7 bytes per residue and one "
+                                         "pass serves up to 8 queries"}},
+                "roofline_compute": compute,
+                "latency_ms_single_query": round(latency_ms, 4),
+                "single_query_qps": round(1e3 / latency_ms, 1),
+                "phases_ms_single_query": {kk: round(v, 4) for kk, v in timings.items() if kk.endswith("_ms")},
+            })
         out.update(out_extra)
         if forced_check is not None:
             out["forced_dist_replies_equal_plain"] = forced_check
@@ -780,7 +796,7 @@ def main():
                                         "reduce (reduce-scatter + mod q) of one step with a host wait after every phase; "
                                         "the timed steps run them pipelined (exchange of step s under the multiply of "
                                         "step s-1 and the expansion of step s+1, no host waits): ms_per_step"}
-        if world == 1 and not use_dist and args.config == 3 and not skip_wire:
+        if args.full and world == 1 and not use_dist and args.config == 3 and not skip_wire:
             # wire-level ProcessRequest (what benchmark.cpp:71-79 times): serialized pir.Request in host
             # memory -> serialized pir.Response, incl. parsing, H2D of keys + query, D2H, serialisation.  The requests
             # come from the product client library (pir_amd.PIRClient, CPU): real keys, a real query ciphertext.
@@ -894,7 +910,7 @@ def main():
                     out["reference_sweep"]["seconds"] = round(time.perf_counter() - t0, 2)
                 except Exception as e:   # measurement extra only
                     out["reference_sweep"] = {"error": repr(e)}
-        if world == 1 and not use_dist and args.config == 3 and not skip_wire:
+        if args.full and world == 1 and not use_dist and args.config == 3 and not skip_wire:
             # several CLIENTS at once (the reference's keys are per request, server.cpp:46-48): `batch` clients with
             # different Galois keys, one query each, through the same batch pipeline -- every group of 8 holds 8
             # different clients' queries, each switched with its own client's resident key set
@@ -1059,7 +1075,7 @@ def main():
                                                         "= one thread using the begin / end form" % (n_w, callers)}
             except Exception as e:   # measurement extra only
                 out["wire_multi_client_qps"] = {"error": repr(e)}
-        if world == 1 and not use_dist and not args.no_cpu_baseline:
+        if args.full and world == 1 and not use_dist and not args.no_cpu_baseline:
             out["batch_reply0_equals_single_query_reply"] = bool(np.array_equal(batch_replies[0], single_reply))
             out["cpu_baseline"] = cpu_baseline(pp, raw, keys, query, single_reply)
             out["speedup_vs_cpu_baseline"] = qps / out["cpu_baseline"]["value"]
@@ -1163,14 +1179,15 @@ def main():
         active[0] = form
         if use_dist and form == "packed":
             bufs = D.PackedBuffers(srv, batch, rank, world, torch, dev)
-            # serial phase times from the synchronous form of the step (every phase followed by a host wait) ...
-            for _ in range(2):
-                D.run_batch_rows_packed(srv, bufs, dist, rank, world, comm)
-            acc = None
-            for _ in range(5):
-                ph = D.run_batch_rows_packed(srv, bufs, dist, rank, world, comm)
-                acc = ph if acc is None else {kk: acc[kk] + v for kk, v in ph.items()}
-            serial_phases = {kk: round(v / 5, 4) for kk, v in acc.items()}
+            # --full: serial phase times from the synchronous form of the step (every phase followed by a host wait) ...
+            if args.full:
+                for _ in range(2):
+                    D.run_batch_rows_packed(srv, bufs, dist, rank, world, comm)
+                acc = None
+                for _ in range(5):
+                    ph = D.run_batch_rows_packed(srv, bufs, dist, rank, world, comm)
+                    acc = ph if acc is None else {kk: acc[kk] + v for kk, v in ph.items()}
+                serial_phases = {kk: round(v / 5, 4) for kk, v in acc.items()}
             # ... and the pipelined form for the timed steps: exchange of step s under the multiply of step s - 1 and
             # the expansion of step s + 1, streams ordered by events, no host waits (PIRGPU_ROWS_PIPELINE=0: synchronous)
             if os.environ.get("PIRGPU_ROWS_PIPELINE", "1") != "0":
@@ -1207,13 +1224,15 @@ def main():
             ssrv.stage_batch(queries)
             sbarrier = barrier_for(ssrv)
             sb = D.SlotsBuffers(ssrv, batch, rank, world, torch, dev)
-            for _ in range(2):
-                D.run_batch_slots(ssrv, sb, dist, rank, world, comm)
-            acc = None
-            for _ in range(5):
-                ph = D.run_batch_slots(ssrv, sb, dist, rank, world, comm)
-                acc = ph if acc is None else {kk: acc[kk] + v for kk, v in ph.items()}
-            phases = {kk: round(v / 5, 4) for kk, v in acc.items()}
+            phases = None
+            if args.full:        # serial phase times: runs of their own
+                for _ in range(2):
+                    D.run_batch_slots(ssrv, sb, dist, rank, world, comm)
+                acc = None
+                for _ in range(5):
+                    ph = D.run_batch_slots(ssrv, sb, dist, rank, world, comm)
+                    acc = ph if acc is None else {kk: acc[kk] + v for kk, v in ph.items()}
+                phases = {kk: round(v / 5, 4) for kk, v in acc.items()}
             per_q = sb.exchange_bytes_per_query(world)
             del sb
             # The timed steps: the pipelined form, with the row sums crossing the links as u64 or in 5 bytes per residue
@@ -1261,7 +1280,8 @@ def main():
                     slots_replies[0] = spipe.replies(spipe.step - 1).cpu().numpy().view(np.uint64).copy()
                     slots_blocks[0] = BLOCK_LOG[-1]
                 del spipe
-            slots_details = {"pipelined": True, "phases_ms_serial": phases, "serial_sum_ms": round(sum(phases.values()), 4),
+            slots_details = {"pipelined": True, "phases_ms_serial": phases,
+                             "serial_sum_ms": round(sum(phases.values()), 4) if phases else None,
                              "row_sums_on_the_links": rowsums,
                              "exchange_bytes_received_per_query_per_gpu": per_q,
                              "database_bytes_per_gpu": ssrv.scan_bytes(), "slots_per_gpu": cuts[rank + 1] - cuts[rank],
@@ -1355,10 +1375,10 @@ def main():
     batch_replies = srv.fetch_batch() if world == 1 and not use_dist else None
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, batch_replies)
-    # the database pass as it runs INSIDE the step just timed (roofline.kernel_ms above is the single-query launch on the
+    # --full: the database pass as it runs INSIDE the step just timed (roofline.kernel_ms is the single-query launch on the
     # whole chip): HIP events around the batch pipeline's scan launches over a few more steps, outside the timed region
     batch_scan = None
-    if world == 1 and not use_dist and info["mfma"]:
+    if args.full and world == 1 and not use_dist and info["mfma"]:
         try:
             srv.set_profiling(True)
             for _ in range(6):
@@ -1404,7 +1424,7 @@ def main():
     # headline".  Every group of S ranks holds the whole database row-sharded S ways and serves batch / R of the
     # step's queries with the same pipelined step, its collectives confined to the group's own process group.
     hyb_R = int(os.environ.get("PIRGPU_HYBRID_GROUPS", "2"))
-    run_hybrid = (use_dist and world > 1 and args.dist_mode == "both" and args.dims == 2 and hyb_R >= 1
+    run_hybrid = (args.full and use_dist and world > 1 and args.dist_mode == "both" and args.dims == 2 and hyb_R >= 1
                   and world % hyb_R == 0 and batch % world == 0
                   and (world // hyb_R >= 2 or os.environ.get("PIRGPU_HYBRID_FORCE") == "1"))
     def hybrid_leg():

@@ -271,8 +271,8 @@ def test_batch_replies_downloaded_group_by_group():
 def test_bench_four_ranks_sharing_one_gpu():
     """`bench.py --gpus 4` end to end at world size 4 on ONE GPU (PIRGPU_BENCH_SHARE_GPU=1: all ranks use device 0, the
     collectives go over gloo): the launcher, four row shards of 20 / 21 rows of an 81 x 81 matrix (uneven, n0 % 4 != 0),
-    one full group of 8 queries per rank, every form of the sharded step timed and the fastest one reported, the
-    replica and hybrid 2 x 2 reference legs.  Not a multi-GPU measurement (the line says so) -- a rehearsal of every
+    one full group of 8 queries per rank, every form of the sharded step timed and the fastest one reported, and (--full)
+    the replica and hybrid 2 x 2 reference legs.  Not a multi-GPU measurement (the line says so) -- a rehearsal of every
     line of the driver's multi-GPU run except the RCCL calls themselves.  Four ranks, not eight: with the test process,
     no more than five processes hold the GPU at once, so the suite can run on a GPU that other jobs share (the
     eight-rank shapes run on the CPU in tests/test_distributed_world8.py and tests/test_launcher.py)."""
@@ -283,7 +283,7 @@ def test_bench_four_ranks_sharing_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env["PIRGPU_BENCH_SHARE_GPU"] = "1"
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--log-items", "18", "--steps", "2",
-                        "--warmup", "1", "--latency-runs", "2", "--batch", "32", "--no-cpu-baseline"], env=env,
+                        "--warmup", "1", "--latency-runs", "2", "--batch", "32", "--no-cpu-baseline", "--full"], env=env,
                        capture_output=True, text=True, timeout=1200)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]

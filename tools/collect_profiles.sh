@@ -12,10 +12,10 @@ python3 tools/valu_roofline.py ${R}e $O/${R}_valu_roofline.json > $O/valu_table.
 cp gpurun_out/pmc_${R}e.json $O/${R}_pmc_counters.json
 cp $O/${R}_valu_roofline.json profiles/${R}_valu_roofline.json
 rm -rf gpurun_out/pmc_${R}e_valu gpurun_out/pmc_${R}e_lds gpurun_out/pmc_${R}e_fetch gpurun_out/pmc_${R}e_write
-python3 bench.py > $O/${R}_bench.json 2> $O/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o ${R} -- python3 bench.py > $O/${R}_bench_profiled.json 2> $O/bench_prof.err
+python3 bench.py --full > $O/${R}_bench.json 2> $O/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o ${R} -- python3 bench.py --full > $O/${R}_bench_profiled.json 2> $O/bench_prof.err
 cp $(find $O/prof -name "*kernel_stats.csv" | head -1) $O/${R}_kernel_stats.csv
 python3 tools/trace_summary.py $(find $O/prof -name "*kernel_trace.csv" | head -1) 1000 > $O/${R}_trace_summary.txt
 rm -rf $O/prof
-for c in 2 4 5; do python3 bench.py --config $c --batch 16 --steps 10 --no-cpu-baseline > $O/${R}_bench_cfg${c}_reference.json 2> $O/cfg$c.err; done
+for c in 2 4 5; do python3 bench.py --config $c --full --batch 16 --steps 10 --no-cpu-baseline > $O/${R}_bench_cfg${c}_reference.json 2> $O/cfg$c.err; done
 ls -la $O

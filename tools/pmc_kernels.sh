@@ -8,7 +8,7 @@ export PIRGPU_ALLOW_ENV=1   # the library reads PIRGPU_* knobs only behind this 
 export TMPDIR=/tmp
 TAG=${1:-r02}
 shift
-ARGS=${@:---no-cpu-baseline --steps 3 --warmup 1 --latency-runs 4}
+ARGS=${@:---full --no-cpu-baseline --steps 3 --warmup 1 --latency-runs 4}
 declare -A CGRP
 CGRP[valu]="SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVES"
 CGRP[lds]="SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_INST_LDS"

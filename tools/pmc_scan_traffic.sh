@@ -7,7 +7,7 @@ export PIRGPU_ALLOW_ENV=1   # the library reads PIRGPU_* knobs only behind this 
 # gfx950 correction (MI355X_MICROARCH.md, HBM section): FETCH_SIZE reports half the bytes of a 16 B/lane coalesced
 # streaming read -> x2; WRITE_SIZE as reported.
 export TMPDIR=/tmp
-# only the workload's own launches: the wire legs and the reference sweep of the default line run the same kernel on other
+# only the workload's own launches: the wire legs and the reference sweep of the --full line run the same kernel on other
 # (tiny) databases -- their full-grid launches with the smallest write volume would be mistaken for the single-query pass
 export PIRGPU_BENCH_SKIP_WIRE=1 PIRGPU_BENCH_SKIP_SWEEP=1
 OUT=${1:-gpurun_out/pmc_scan_traffic.json}
@@ -19,7 +19,7 @@ for cfg in $CFGS; do
     d=gpurun_out/pmc_scan_cfg${cfg}_$(echo $c | tr A-Z a-z | cut -d_ -f1)
     rm -rf $d
     rocprofv3 --pmc $c --kernel-trace --output-format csv -d $d -o pmc -- \
-      python3 bench.py --config $cfg --no-cpu-baseline --batch 8 --workers 8 --steps 1 --warmup 1 --latency-runs 4 > $d.json 2> $d.err
+      python3 bench.py --config $cfg --full --no-cpu-baseline --batch 8 --workers 8 --steps 1 --warmup 1 --latency-runs 4 > $d.json 2> $d.err
   done
 done
 python3 - "$OUT" "$COMMIT" $CFGS <<'PY'
@@ -29,7 +29,7 @@ out_path, commit, cfgs = sys.argv[1], sys.argv[2], sys.argv[3:]
 # when they differ; tools/check_pmc_fresh.py refuses a file whose stamp is not the committed source
 src_sha = hashlib.sha256(open("pir_amd/csrc/scan_mfma.hip", "rb").read()).hexdigest()[:16]
 out = {"collection": "bash tools/pmc_scan_traffic.sh: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE in separate passes with "
-                     "--kernel-trace over `bench.py --config C --batch 8 --steps 1 --latency-runs 4`; the single-query "
+                     "--kernel-trace over `bench.py --config C --full --batch 8 --steps 1 --latency-runs 4`; the single-query "
                      "launches are the ones with the smallest WRITE_SIZE",
        "correction": "FETCH_SIZE x2 on gfx950 for 16 B/lane coalesced streaming reads (MI355X_MICROARCH.md, HBM "
                      "section); WRITE_SIZE as reported; both in KB", "commit": commit, "scan_source_sha16": src_sha, "configs": {}}

@@ -17,7 +17,7 @@ for limb, rows, block, nsplit in configs:
     env = dict(os.environ, PIRGPU_SCAN_MQ_SINGLE="0", PIRGPU_SCAN_ROWS=str(rows), PIRGPU_SCAN_BLOCK=str(block), PIRGPU_SCAN_NSPLIT=str(nsplit),
                PIRGPU_SCAN_LIMB=str(limb))
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3",
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True)
+                        "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True)
     try:
         j = json.loads(r.stdout.strip().splitlines()[-1])
         print(limb, rows, block, nsplit, "%.4f" % j["roofline"]["kernel_ms"], "%.0f" % j["roofline"]["achieved"],
