@@ -46,7 +46,9 @@ const char* pirclient_create_error(void);
 int pirclient_create_request(pirclient* c, const uint64_t* indexes, size_t n_indexes, uint8_t** request,
                              size_t* request_len);
 /* PIRClient::ProcessResponse(indexes, response) -- client.cpp:160-185: serialized pir.Response ->
- * n_indexes items of bytes_per_item bytes each, written back to back into items_out. */
+ * n_indexes items of bytes_per_item bytes each, written back to back into items_out.  Wide items (params.
+ * plaintexts_per_item > 1, not in the reference): every reply holds the planes' ciphertexts back to back; plane j is
+ * decoded like a reference reply and gives bytes [j B, min((j + 1) B, bytes_per_item)) of the item. */
 int pirclient_process_response(pirclient* c, const uint64_t* indexes, size_t n_indexes, const uint8_t* response,
                                size_t response_len, uint8_t* items_out, size_t items_cap);
 /* PIRClient::ProcessResponseInteger(response) -- client.cpp:146-158 (IntegerEncoder::decode_int64 per reply). */
@@ -77,9 +79,10 @@ int pirclient_create_query(pirclient* c, uint64_t index, uint64_t* query_out, si
  * (must be one of generate_galois_elts(N)); key_out [k][2][k+1][N]. */
 int pirclient_galois_key(const pirclient* c, uint32_t elt, uint64_t* key_out);
 /* PIRClient::ProcessReply -- client.cpp:187-255 (ProcessReplyCiphertextDecomp: decrypt, CiphertextReencoder::Decode,
- * repeat once per dimension).  reply [n_cts][2][k][N] -> plaintext_out [N]. */
+ * repeat once per dimension).  reply [n_cts][2][k][N] -> plaintext_out [N].  With wide items (plaintexts_per_item > 1)
+ * a whole reply of planes x that many ciphertexts gives plaintext_out [planes][N], one plane's ciphertexts one [N]. */
 int pirclient_process_reply(pirclient* c, const uint64_t* reply, size_t n_cts, uint64_t* plaintext_out);
-/* expected reply size: (2 * ExpansionRatio)^(d-1) (client.cpp:224-226) */
+/* expected reply size: (2 * ExpansionRatio)^(d-1) (client.cpp:224-226), times params.plaintexts_per_item */
 uint64_t pirclient_reply_ct_count(const pirclient* c);
 
 /* ---- the SEAL objects PIRClientTest reaches through friend access (client_test.cpp:55-58) ---- */

@@ -84,6 +84,16 @@ typedef struct pirgpu_params {
    * database larger than one GPU's memory (that needs the encode + pack in row blocks). */
   uint32_t slot_begin;
   uint32_t slot_end;
+  /* Wide items (not in the reference, whose CreatePIRParameters refuses an item larger than one plaintext,
+   * parameters.cpp:81-85): an item of up to plaintexts_per_item x B bytes, B = N * bits_per_coeff / 8 rounded down, is
+   * stored as `planes` = plaintexts_per_item plaintexts, plane j holding bytes [j B, min((j + 1) B, bytes_per_item)) of
+   * it.  Every plane is a database of num_pt plaintexts with these dimensions; one query is expanded once and answered
+   * on all planes: the reply is planes x (the usual count) ciphertexts, plane-major, plane j's part being bit-identical
+   * to the reference's answer on plane j alone.  0 and 1 both mean 1 (the reference's behaviour).  planes > 1 needs
+   * items_per_plaintext == 1 and (planes - 1) B < bytes_per_item <= planes B, and serves one GPU only (no row or slot
+   * shard).  Plaintext indices at this ABI are plane-major then: plane * num_pt + pt (pirgpu_db_load_coeffs,
+   * pirgpu_db_read_plaintext, pirgpu_db_update_plaintexts; pirgpu_db_size and pirgpu_zero_plaintexts count all planes). */
+  uint32_t plaintexts_per_item;
 } pirgpu_params;
 
 /* PIRContext::Create + PIRDatabase::Create(params) (reference context.cpp:37-50,
@@ -97,6 +107,8 @@ const char* pirgpu_last_error(const pirgpu_ctx* ctx);
 void pirgpu_set_error(pirgpu_ctx* ctx, const char* message);
 /* The parameters the context was created with (shard range resolved). */
 int pirgpu_get_params(const pirgpu_ctx* ctx, pirgpu_params* out);
+/* Plaintexts per item of the context (pirgpu_params.plaintexts_per_item resolved: at least 1). */
+uint32_t pirgpu_planes(const pirgpu_ctx* ctx);
 /* last error of a failed pirgpu_create (no context to ask) */
 const char* pirgpu_create_error(void);
 
@@ -109,7 +121,7 @@ int pirgpu_db_load_items(pirgpu_ctx* ctx, const uint8_t* items, uint64_t num_ite
  * reference database.cpp:60-82): coeffs = n_pt x N coefficients, each < t,
  * zero padded; plaintext indices [first_pt, first_pt + n_pt). */
 int pirgpu_db_load_coeffs(pirgpu_ctx* ctx, uint64_t first_pt, uint64_t n_pt, const uint64_t* coeffs);
-/* PIRDatabase::size() (reference database.h:97) -- plaintexts loaded so far. */
+/* PIRDatabase::size() (reference database.h:97) -- plaintexts loaded so far (wide items: over all planes). */
 uint64_t pirgpu_db_size(const pirgpu_ctx* ctx);
 /* Optional: bring the scan's operand-layout copy of the database up to date now (otherwise done lazily
  * by the first query after a load).  With release_staging != 0 (d >= 2 only) the u64 staging copy that
@@ -131,7 +143,9 @@ int pirgpu_db_finalize(pirgpu_ctx* ctx, int release_staging);
  * this context's row shard are skipped (every rank of a row-sharded server can be given the same full list).  Every
  * other bit of a touched plaintext -- other items, padding, coefficient bits a coefficient load set -- is kept.
  * A slot shard (slot_begin / slot_end) with released staging returns FailedPrecondition: it holds 1 / G of each
- * plaintext and cannot recover the items it must keep. */
+ * plaintext and cannot recover the items it must keep.
+ * Wide items (plaintexts_per_item > 1): every plane of a listed item is replaced (an item owns its plaintexts whole, so
+ * nothing has to be kept and nothing of the old plaintexts is read). */
 int pirgpu_db_update_items(pirgpu_ctx* ctx, uint64_t n, const uint64_t* item_indices, const uint8_t* items,
                            uint32_t bytes_per_item);
 /* Replace whole plaintexts given as coefficient rows (each < t; the pirgpu_db_load_coeffs analogue of the above, for
@@ -151,7 +165,7 @@ int pirgpu_set_transparent_policy(pirgpu_ctx* ctx, int allow);
 uint64_t pirgpu_zero_plaintexts(const pirgpu_ctx* ctx);
 int pirgpu_set_remote_zero_plaintexts(pirgpu_ctx* ctx, uint64_t count);
 int pirgpu_check_ready(pirgpu_ctx* ctx);
-/* Test hook: read back one encoded plaintext [k][N] (NTT form) from HBM. */
+/* Test hook: read back one encoded plaintext [k][N] (NTT form) from HBM (wide items: pt_index = plane * num_pt + pt). */
 int pirgpu_db_read_plaintext(pirgpu_ctx* ctx, uint64_t pt_index, uint64_t* out);
 
 /* What SEALDeserialize<GaloisKeys> yields per request (reference server.cpp:46-48):
@@ -199,7 +213,7 @@ int pirgpu_keyset_stats(pirgpu_ctx* ctx, uint64_t stats[4]);
  * (coefficient form).  reply_capacity is in ciphertexts. */
 int pirgpu_process_query(pirgpu_ctx* ctx, const uint64_t* query, uint32_t nq, uint64_t* reply,
                          uint64_t reply_capacity, uint64_t* reply_count);
-/* (2 * ExpansionRatio)^(d-1) (reference client.cpp:224-226, ct_reencoder.cpp:29-38) */
+/* (2 * ExpansionRatio)^(d-1) (reference client.cpp:224-226, ct_reencoder.cpp:29-38), times plaintexts_per_item */
 uint64_t pirgpu_reply_ct_count(const pirgpu_ctx* ctx);
 /* CiphertextReencoder::ExpansionRatio (reference ct_reencoder.cpp:29-38) */
 uint32_t pirgpu_expansion_ratio(const pirgpu_ctx* ctx);

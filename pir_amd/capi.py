@@ -34,6 +34,7 @@ class Params(C.Structure):
         ("shard_end", C.c_uint32),
         ("slot_begin", C.c_uint32),
         ("slot_end", C.c_uint32),
+        ("plaintexts_per_item", C.c_uint32),
     ]
 
 
@@ -56,6 +57,7 @@ def make_params(params, device: int = 0, shard=None, slots=None) -> Params:
     p.items_per_plaintext = params.items_per_plaintext
     p.bits_per_coeff = params.bits_per_coeff
     p.use_ciphertext_multiplication = 1 if params.use_ciphertext_multiplication else 0
+    p.plaintexts_per_item = getattr(params, "plaintexts_per_item", 1)
     p.device = device
     if shard is not None:
         b, e = int(shard[0]), int(shard[1])
@@ -166,6 +168,7 @@ SIGNATURES = {
     "pirgpu_last_timings": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "pirgpu_set_error": (None, [C.c_void_p, C.c_char_p]),
     "pirgpu_get_params": (C.c_int, [C.c_void_p, C.POINTER(Params)]),
+    "pirgpu_planes": (C.c_uint32, [C.c_void_p]),
     "pirgpu_reply_copy_to_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "pirgpu_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),
     "pirgpu_batch_scan_timings": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

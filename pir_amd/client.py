@@ -152,9 +152,11 @@ class PIRClient:
         return {g: self.galois_key(g) for g in generate_galois_elts(self.N)}
 
     def process_reply(self, reply: np.ndarray) -> np.ndarray:
-        """client.cpp:187-255 -> plaintext coefficients [N]."""
+        """client.cpp:187-255 -> plaintext coefficients [N]; a whole reply for wide items -> [planes, N]."""
         r = _u64(reply)
-        out = np.empty(self.N, dtype=np.uint64)
+        planes = self.params.planes
+        wide = planes > 1 and r.shape[0] == self.reply_ct_count
+        out = np.empty((planes, self.N) if wide else self.N, dtype=np.uint64)
         self._check(self.lib.pirclient_process_reply(self._h, _ptr(r), r.shape[0], _ptr(out)))
         return out
 

@@ -582,11 +582,16 @@ struct pirclient {
     return s;
   }
   uint32_t query_ct_count() const { return (uint32_t)(dim_sum() / N + 1); }
-  uint64_t reply_ct_count() const {
+  // wide items (pirgpu_params.plaintexts_per_item, not in the reference): an item is spread over `planes` plaintexts, the
+  // server answers one query on every plane and the reply carries the planes' ciphertexts back to back
+  uint32_t planes() const { return prm.plaintexts_per_item > 1 ? prm.plaintexts_per_item : 1; }
+  uint64_t plane_bytes() const { return (uint64_t)N * bits_per_coeff / 8; }   // StringEncoder::max_bytes_per_plaintext
+  uint64_t plane_reply_ct_count() const {
     uint64_t n = 1;
     for (uint32_t d = 1; d < prm.num_dimensions; ++d) n *= 2ull * exp_ratio;
     return n;
   }
+  uint64_t reply_ct_count() const { return planes() * plane_reply_ct_count(); }
   // PIRDatabase::calculate_indices (database.cpp:112-131)
   std::vector<uint64_t> calculate_indices(uint64_t index) const {
     uint64_t pt_index = index / prm.items_per_plaintext;
@@ -649,7 +654,7 @@ struct pirclient {
       return;
     }
     const size_t ratio = (size_t)exp_ratio * 2;
-    if (n_cts != reply_ct_count())
+    if (n_cts != plane_reply_ct_count())   // one plane's reply: what the reference's client gets
       throw Err{PIRGPU_INVALID_ARGUMENT, "Number of ciphertexts in reply does not match expected"};
     std::vector<uint64_t> cts(reply, reply + n_cts * ct_words()), pts;
     size_t n = n_cts;
@@ -664,12 +669,14 @@ struct pirclient {
   }
 
   // StringEncoder::decode (string_encoder.cpp:124-163), same shift/or sequence on 8-bit chars
-  void string_decode(const uint64_t* pt, size_t length, size_t byte_offset, uint8_t* out) const {
+  // trim = false (the planes of a wide item, which are not the reference's): all N coefficients count, so a chunk that
+  // ends in zero bytes decodes to those zero bytes instead of failing the reference's bound
+  void string_decode(const uint64_t* pt, size_t length, size_t byte_offset, uint8_t* out, bool trim = true) const {
     const size_t bpc = bits_per_coeff;
     // pt.coeff_count() of a decrypted SEAL plaintext: Decryptor::decrypt trims the result to its significant
     // coefficients (at least one), and the reference's bound (string_encoder.cpp:126) is taken on that count
     size_t coeff_count = N;
-    while (coeff_count > 1 && !pt[coeff_count - 1]) --coeff_count;
+    while (trim && coeff_count > 1 && !pt[coeff_count - 1]) --coeff_count;
     if (byte_offset + length > coeff_count * bpc / 8)
       throw Err{PIRGPU_INVALID_ARGUMENT, "Requested decode beyond end of data in polynomial"};
     if (length == 0) return;
@@ -868,9 +875,24 @@ int pirclient_process_response(pirclient* c, const uint64_t* indexes, size_t n_i
     if (items_cap < n_indexes * item || (!items_out && n_indexes * item != 0))
       throw Err{PIRGPU_INVALID_ARGUMENT, "items_out too small"};
     std::vector<uint64_t> pt(c->N);
+    std::vector<uint64_t> cts;
     for (size_t i = 0; i < n_indexes; ++i) {
-      c->reply_plaintext(replies[i], pt.data());
-      c->string_decode(pt.data(), item, c->calculate_item_offset(indexes[i]), items_out + i * item);
+      if (c->planes() == 1) {
+        c->reply_plaintext(replies[i], pt.data());
+        c->string_decode(pt.data(), item, c->calculate_item_offset(indexes[i]), items_out + i * item);
+        continue;
+      }
+      // wide item: plane j of the reply decodes to bytes [j B, min((j + 1) B, item)) of it
+      const uint32_t n = wire::load_query(c->sh, replies[i].first, replies[i].second, cts);
+      if (n != c->reply_ct_count())
+        throw Err{PIRGPU_INVALID_ARGUMENT, "Number of ciphertexts in reply does not match expected"};
+      const uint64_t B = c->plane_bytes(), R = c->plane_reply_ct_count();
+      for (uint32_t pl = 0; pl < c->planes(); ++pl) {
+        const uint64_t off = pl * B;
+        if (off >= item) throw Err{PIRGPU_INVALID_ARGUMENT, "plaintexts_per_item does not match bytes_per_item"};
+        c->process_reply(cts.data() + (size_t)pl * R * c->ct_words(), R, pt.data());
+        c->string_decode(pt.data(), std::min<uint64_t>(B, item - off), 0, items_out + i * item + off, false);
+      }
     }
   });
 }
@@ -914,7 +936,15 @@ int pirclient_galois_key(const pirclient* cc, uint32_t elt, uint64_t* key_out) {
 
 int pirclient_process_reply(pirclient* c, const uint64_t* reply, size_t n_cts, uint64_t* plaintext_out) {
   if (!c || !reply || !plaintext_out) return PIRGPU_INVALID_ARGUMENT;
-  return guarded(c, [&] { c->process_reply(reply, n_cts, plaintext_out); });
+  return guarded(c, [&] {
+    if (c->planes() > 1 && n_cts == c->reply_ct_count()) {   // a wide reply: planes x N coefficients, plane-major
+      const uint64_t R = c->plane_reply_ct_count();
+      for (uint32_t pl = 0; pl < c->planes(); ++pl)
+        c->process_reply(reply + (size_t)pl * R * c->ct_words(), R, plaintext_out + (size_t)pl * c->N);
+      return;
+    }
+    c->process_reply(reply, n_cts, plaintext_out);
+  });
 }
 
 int pirclient_encrypt(pirclient* c, const uint64_t* plaintext, size_t n_coeffs, uint64_t* ct_out) {

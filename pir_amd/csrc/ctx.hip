@@ -65,6 +65,19 @@ struct Fail {
 
 enum Phase { PH_EXPAND = 0, PH_SVNTT, PH_SCAN, PH_UPPER, PH_FINAL, PH_COUNT };
 
+// device scratch of one call, freed on every way out
+struct DevScratch {
+  void* p = nullptr;
+  ~DevScratch() {
+    if (p) (void)hipFree(p);
+  }
+  template <typename T>
+  T* get(size_t bytes) {
+    HIP_TRY(hipMalloc(&p, std::max<size_t>(bytes, 1)));
+    return static_cast<T*>(p);
+  }
+};
+
 }  // namespace
 
 // ======================================================================================================================
@@ -212,6 +225,13 @@ struct pirgpu_ctx {
   bool slot_sharded = false;
   hipEvent_t ev_after = nullptr;   // pirgpu_slots_*: the position of the caller's `after` stream
   uint64_t pt_begin = 0, pt_end = 0;  // plaintext range held by this context
+  // wide items (pirgpu_params.plaintexts_per_item): `planes` databases of P plaintexts each behind one query.  A plane is
+  // an outermost dimension that is not selected: in HBM plane j occupies the rows [j, j + 1) * plane_pad of d_db, every
+  // plane padded with zero plaintexts to the full dims[0] x ... x dims[d-1] box so that all planes have the same shape at
+  // every recursion level (zero plaintexts add nothing to any sum); the scan and every upper level run over planes x
+  // their usual rows with the same selectors, and level 0 keeps `planes` rows -- the reply -- instead of one
+  uint32_t planes = 1;
+  uint64_t plane_pad = 0;             // plaintext rows of d_db per plane (planes > 1)
   uint32_t bits = 0;           // bits per coefficient for item packing
 
   int device = 0;
@@ -340,6 +360,17 @@ struct pirgpu_ctx {
 };
 
 BatchSet& pirgpu_ctx::bs() { return sets[t_batch_set]; }
+
+// plaintexts this context must hold before it answers queries (all planes)
+static inline uint64_t held_pts(const pirgpu_ctx* c) { return (uint64_t)c->planes * (c->pt_end - c->pt_begin); }
+// plaintext rows of the matrix the scan and the upper levels walk: the shard, or planes x the padded plane
+static inline uint64_t matrix_pts(const pirgpu_ctx* c) {
+  return c->planes > 1 ? (uint64_t)c->planes * c->plane_pad : c->pt_end - c->pt_begin;
+}
+// ABI plaintext index (plane-major: plane * num_pt + pt) -> row of d_db
+static inline uint64_t db_row(const pirgpu_ctx* c, uint64_t index) {
+  return c->planes > 1 ? index / c->P * c->plane_pad + index % c->P : index - c->pt_begin;
+}
 
 namespace {
 
@@ -541,7 +572,7 @@ void ensure_workspace(pirgpu_ctx* c) {
   const uint64_t m_max = std::min<uint64_t>(N, hm::next_power_two(std::max<uint32_t>(c->dim_sum, 1)));
   c->m_max = m_max;
   // per-level node counts inside this shard and result buffers
-  const uint64_t shard_pts = c->pt_end - c->pt_begin;
+  const uint64_t shard_pts = matrix_pts(c);
   c->upper_blocks = (uint32_t)std::max<int64_t>(1, option(c, "UPPER_BLOCKS", c->upper_blocks));
   c->upper_blocks_batch = (uint32_t)std::max<int64_t>(1, option(c, "UPPER_BLOCKS_BATCH", c->upper_blocks_batch));
   c->scan_wgs_batch = (uint32_t)std::max<int64_t>(0, option(c, "SCAN_MFMA_WGS_BATCH", c->scan_wgs_batch));
@@ -550,7 +581,7 @@ void ensure_workspace(pirgpu_ctx* c) {
   c->lvl_cts.assign(d, 0);
   uint64_t pt_words = 0;
   for (uint32_t l = 0; l < d; ++l) {
-    uint64_t rows = l == 0 ? 1 : ceil_div(shard_pts, c->stride[l]);
+    uint64_t rows = l == 0 ? c->planes : ceil_div(shard_pts, c->stride[l]);
     uint64_t C = 1;
     for (uint32_t x = l; x + 1 < d; ++x) C *= c->E;
     c->lvl_rows[l] = rows;
@@ -565,8 +596,8 @@ void ensure_workspace(pirgpu_ctx* c) {
   c->pt_words = pt_words;
   // base-level scan geometry
   if (d == 1) {
-    c->scan_rows = 1;
-    c->scan_cols = (uint32_t)shard_pts;
+    c->scan_rows = c->planes;
+    c->scan_cols = (uint32_t)(shard_pts / c->planes);
   } else {
     c->scan_cols = c->dims[d - 1];
     c->scan_rows = (uint32_t)ceil_div(shard_pts, c->scan_cols);
@@ -1016,6 +1047,13 @@ bool mq_usable(pirgpu_ctx* c) { return c->scan_nsplit == 1 && c->scan_rows >= 1 
 size_t dbp_bytes(const pirgpu_ctx* c) { return (size_t)c->nslots * c->mg.RT * c->mg.KG * c->mg.tile_bytes; }
 
 // A slot shard holds 1 / G of every plaintext: it serves the pirgpu_slots_* step only.
+// Wide items are served by one GPU: the multi-GPU steps (packed row-shard exchange, slot shards) do not know planes.
+void refuse_wide(const pirgpu_ctx* c) {
+  if (c->planes > 1)
+    throw Fail{PIRGPU_FAILED_PRECONDITION, "this context holds wide items (plaintexts_per_item > 1): the multi-GPU entry "
+                                           "points do not serve them"};
+}
+
 void refuse_slot_shard(const pirgpu_ctx* c) {
   if (c->slot_sharded)
     throw Fail{PIRGPU_FAILED_PRECONDITION, "this context is a slot shard: it serves the pirgpu_slots_* entry points only"};
@@ -1083,7 +1121,7 @@ void scan_on_device(pirgpu_ctx* c, Worker& w) {
   const uint32_t N = c->N, k = c->k, d = c->d;
   const size_t ctw = c->ctw;
   refuse_slot_shard(c);
-  if (c->n_loaded != c->pt_end - c->pt_begin)
+  if (c->n_loaded != held_pts(c))
     throw Fail{PIRGPU_FAILED_PRECONDITION, "database not fully loaded"};
   check_transparent(c);
   if (c->pt_end == c->pt_begin) return;
@@ -1113,7 +1151,7 @@ void scan_on_device(pirgpu_ctx* c, Worker& w) {
 void post_scan_stage(pirgpu_ctx* c, const Stage& sg, Worker* profiled) {
   const uint32_t N = c->N, k = c->k, d = c->d;
   const size_t ctw = c->ctw;
-  const uint64_t shard_pts = c->pt_end - c->pt_begin;
+  const uint64_t shard_pts = matrix_pts(c);
   hipStream_t st = sg.stream;
   if (shard_pts == 0) {
     HIP_TRY(hipMemsetAsync(sg.lvl[0], 0, (size_t)sg.n * c->reply_cts * ctw * 8, st));
@@ -1136,7 +1174,8 @@ void post_scan_stage(pirgpu_ctx* c, const Stage& sg, Worker* profiled) {
     const uint64_t per_chunk = rows * C * c->E * k;
     const uint32_t target = sg.n > 1 || c->in_batch ? c->upper_blocks_batch : c->upper_blocks;
     // children one output row actually has in this shard: dims[l], or -- at the top level of a row shard -- only the
-    // shard's rows (a 20-row shard of 162 used to leave three of its four chunks empty)
+    // shard's rows (a 20-row shard of 162 used to leave three of its four chunks empty; wide items have planes rows at
+    // the top level, each with all dims[0] children: they are never row-sharded)
     const uint64_t kids = rows == 1 ? std::min<uint64_t>(c->dims[l], std::max<uint64_t>(nch, 1)) : c->dims[l];
     uint32_t n_chunks = (uint32_t)std::min<uint64_t>(kids, std::max<uint64_t>(1, ceil_div(target, per_chunk)));
     const uint32_t chunk_len = (uint32_t)ceil_div(kids, n_chunks);
@@ -1312,6 +1351,21 @@ int pirgpu_create(const pirgpu_params* p, pirgpu_ctx** out) {
     const uint32_t bdef = hm::bits_per_coeff(p->plain_modulus);
     if (p->bits_per_coeff > bdef) return bail(PIRGPU_INVALID_ARGUMENT, "Bits per coefficient greater than max");
     c->bits = p->bits_per_coeff ? p->bits_per_coeff : bdef;
+    c->planes = std::max<uint32_t>(1, p->plaintexts_per_item);
+    if (c->planes > 1) {
+      const uint64_t B = (uint64_t)N * c->bits / 8;   // StringEncoder::max_bytes_per_plaintext (string_encoder.cpp:29-31)
+      if (p->items_per_plaintext != 1)
+        return bail(PIRGPU_INVALID_ARGUMENT, "plaintexts_per_item > 1 needs items_per_plaintext == 1");
+      if (p->bytes_per_item <= (c->planes - 1) * B || p->bytes_per_item > c->planes * B)
+        return bail(PIRGPU_INVALID_ARGUMENT, "bytes_per_item " + std::to_string(p->bytes_per_item) + " does not need exactly " +
+                                                 std::to_string(c->planes) + " plaintexts of " + std::to_string(B) + " bytes");
+      if (c->sb != 0 || c->se != c->dims[0] || c->slot_sharded)
+        return bail(PIRGPU_INVALID_ARGUMENT, "wide items (plaintexts_per_item > 1) are served by one GPU: row and slot "
+                                             "shards of them are not supported");
+      if (c->P > c->stride[0] || c->P == 0 || c->planes > 4096)
+        return bail(PIRGPU_INVALID_ARGUMENT, "plaintexts_per_item > 1 needs 0 < num_pt <= the product of the dimensions");
+      c->plane_pad = c->stride[0];
+    }
     c->device = p->device;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
@@ -1323,16 +1377,18 @@ int pirgpu_create(const pirgpu_params* p, pirgpu_ctx** out) {
     if (!c->ops) return bail(PIRGPU_INVALID_ARGUMENT, "poly_modulus_degree must be 2048, 4096, 8192, 16384 or 32768");
     build_tables(c);
     HIP_TRY(c->ops->configure(c->mode));
-    c->reply_cts = 1;
+    c->reply_cts = c->planes;   // every plane answers with its own (2 ExpansionRatio)^(d-1) ciphertexts
     for (uint32_t l = 1; l < c->d; ++l) c->reply_cts *= c->E;
     const uint64_t shard_pts = c->pt_end - c->pt_begin;
     // rows are padded with zero plaintexts to full length so the scan kernels are branch-free
     const uint64_t cols_last = c->dims[c->d - 1];
-    const uint64_t padded = c->d == 1 ? shard_pts : ceil_div(shard_pts, cols_last) * cols_last;
+    const uint64_t padded = c->planes > 1 ? matrix_pts(c) : c->d == 1 ? shard_pts : ceil_div(shard_pts, cols_last) * cols_last;
     c->d_db = c->dalloc<uint64_t>(padded * k * N);
-    if (padded > shard_pts)
+    if (c->planes > 1)   // every plane is padded to the whole box of its dimensions
+      HIP_TRY(hipMemset(c->d_db, 0, padded * k * N * 8));
+    else if (padded > shard_pts)
       HIP_TRY(hipMemset(c->d_db + shard_pts * k * N, 0, (padded - shard_pts) * k * N * 8));
-    c->loaded.assign(shard_pts, 0);
+    c->loaded.assign(held_pts(c), 0);   // per ABI plaintext index - pt_begin (plane-major)
   } catch (const Fail& e) {
     return bail(e.code, e.msg);
   } catch (const std::exception& e) {
@@ -1480,7 +1536,7 @@ int pirgpu_set_remote_zero_plaintexts(pirgpu_ctx* c, uint64_t n) {
 
 int pirgpu_check_ready(pirgpu_ctx* c) {
   return guarded(c, [&]() -> int {
-    if (c->n_loaded != c->pt_end - c->pt_begin) return fail(c, PIRGPU_FAILED_PRECONDITION, "database not fully loaded");
+    if (c->n_loaded != held_pts(c)) return fail(c, PIRGPU_FAILED_PRECONDITION, "database not fully loaded");
     check_transparent(c);
     return PIRGPU_OK;
   });
@@ -1495,6 +1551,7 @@ int pirgpu_get_params(const pirgpu_ctx* c, pirgpu_params* out) {
 }
 
 uint64_t pirgpu_db_size(const pirgpu_ctx* c) { return c ? c->n_loaded : 0; }
+uint32_t pirgpu_planes(const pirgpu_ctx* c) { return c ? c->planes : 0; }
 uint64_t pirgpu_reply_ct_count(const pirgpu_ctx* c) { return c ? c->reply_cts : 0; }
 uint32_t pirgpu_expansion_ratio(const pirgpu_ctx* c) { return c ? c->er : 0; }
 uint64_t pirgpu_scan_bytes(const pirgpu_ctx* cc) {
@@ -1507,7 +1564,7 @@ uint64_t pirgpu_scan_bytes(const pirgpu_ctx* cc) {
     return 0;
   }
   // bytes a single-query pass over the database must read: the operand-layout copy when that pass is the MFMA scan
-  return c->mfma_on && c->mfma_single ? (uint64_t)dbp_bytes(c) : (c->pt_end - c->pt_begin) * c->k * c->N * 8;
+  return c->mfma_on && c->mfma_single ? (uint64_t)dbp_bytes(c) : held_pts(c) * c->k * c->N * 8;
 }
 
 int pirgpu_ntt_mode(const pirgpu_ctx* c) { return c ? c->mode : -1; }
@@ -1542,6 +1599,31 @@ int pirgpu_db_load_items(pirgpu_ctx* c, const uint8_t* items, uint64_t num_items
     if (c->staging_released)
       return fail(c, PIRGPU_FAILED_PRECONDITION, "database staging was released by pirgpu_db_finalize; it cannot be reloaded");
     c->packed_valid = false;
+    if (c->planes > 1) {
+      // wide items: item i is uploaded once and the encode kernel cuts it into its planes -- plane j reads bytes
+      // [j B, min((j + 1) B, bytes_per_item)) of it and writes plaintext row j * plane_pad + i
+      if (num_items > c->P) return fail(c, PIRGPU_INVALID_ARGUMENT, "more items than plaintexts");
+      const uint64_t B = (uint64_t)c->N * c->bits / 8;
+      const uint64_t chunk_items = std::max<uint64_t>(1, (64ull << 20) / bytes_per_item);
+      DevScratch s_bytes;
+      uint8_t* d_bytes = s_bytes.get<uint8_t>(chunk_items * bytes_per_item);
+      for (uint64_t it = 0; it < c->P; it += chunk_items) {
+        const uint64_t n = std::min<uint64_t>(chunk_items, c->P - it);
+        const uint64_t have = it < num_items ? std::min<uint64_t>(n, num_items - it) : 0;   // plaintexts past the items: zero
+        if (have)
+          HIP_TRY(hipMemcpyAsync(d_bytes, items + it * bytes_per_item, have * bytes_per_item, hipMemcpyHostToDevice, c->stream));
+        for (uint32_t pl = 0; pl < c->planes; ++pl) {
+          const uint64_t off = pl * B, len = std::min<uint64_t>(B, bytes_per_item - off);
+          for (uint64_t i = 0; i < n; ++i)
+            note_plaintext(c, pl * c->P + it + i,
+                           it + i >= num_items || all_zero_bytes(items + (it + i) * bytes_per_item + off, len));
+        }
+        HIP_TRY(c->ops->db_encode(c->stream, c->mode, c->dp, c->k, nullptr, d_bytes, bytes_per_item, have * bytes_per_item,
+                                  c->bits, n, c->d_db + it * c->k * c->N, c->planes, B, c->plane_pad));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+      }
+      return PIRGPU_OK;
+    }
     // StringEncoder::calc_num_coeff (reference string_encoder.cpp:88-95)
     if ((uint64_t)std::ceil((double)(bytes_per_pt * 8) / c->bits) > c->N)
       return fail(c, PIRGPU_INVALID_ARGUMENT, "Number of coefficients needed greater than poly modulus degree");
@@ -1562,7 +1644,7 @@ int pirgpu_db_load_items(pirgpu_ctx* c, const uint8_t* items, uint64_t num_items
           note_plaintext(c, pt - c->pt_begin + i, all_zero_bytes(items + p0, p1 - p0));
         }
         HIP_TRY(c->ops->db_encode(c->stream, c->mode, c->dp, c->k, nullptr, d_bytes, bytes_per_pt, b1 - b0, c->bits,
-                                  n, c->d_db + (pt - c->pt_begin) * c->k * c->N));
+                                  n, c->d_db + (pt - c->pt_begin) * c->k * c->N, 1, 0, 0));
         HIP_TRY(hipStreamSynchronize(c->stream));
       }
     } catch (...) {
@@ -1576,8 +1658,11 @@ int pirgpu_db_load_items(pirgpu_ctx* c, const uint8_t* items, uint64_t num_items
 
 int pirgpu_db_load_coeffs(pirgpu_ctx* c, uint64_t first_pt, uint64_t n_pt, const uint64_t* coeffs) {
   return guarded(c, [&]() -> int {
-    if (first_pt + n_pt > c->P || (!coeffs && n_pt)) return fail(c, PIRGPU_INVALID_ARGUMENT, "plaintext range out of bounds");
-    const uint64_t lo = std::max(first_pt, c->pt_begin), hi = std::min(first_pt + n_pt, c->pt_end);
+    if (first_pt + n_pt > c->planes * c->P || (!coeffs && n_pt))
+      return fail(c, PIRGPU_INVALID_ARGUMENT, "plaintext range out of bounds");
+    // (wide items: pt_begin = 0, pt_end = P, and the index runs over all planes, plane-major)
+    const uint64_t lo = std::max(first_pt, c->pt_begin);
+    const uint64_t hi = c->planes > 1 ? first_pt + n_pt : std::min(first_pt + n_pt, c->pt_end);
     if (lo >= hi) return PIRGPU_OK;
     if (c->staging_released)
       return fail(c, PIRGPU_FAILED_PRECONDITION, "database staging was released by pirgpu_db_finalize; it cannot be reloaded");
@@ -1586,8 +1671,9 @@ int pirgpu_db_load_coeffs(pirgpu_ctx* c, uint64_t first_pt, uint64_t n_pt, const
     uint64_t* d_coeffs = nullptr;
     HIP_TRY(hipMalloc((void**)&d_coeffs, chunk * c->N * 8));
     try {
-      for (uint64_t pt = lo; pt < hi; pt += chunk) {
-        const uint64_t n = std::min<uint64_t>(chunk, hi - pt);
+      for (uint64_t pt = lo; pt < hi;) {
+        // a piece never crosses a plane boundary: the rows of one plane are contiguous in d_db
+        const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(chunk, hi - pt), c->planes > 1 ? c->P - pt % c->P : chunk);
         HIP_TRY(hipMemcpyAsync(d_coeffs, coeffs + (pt - first_pt) * c->N, n * c->N * 8, hipMemcpyHostToDevice,
                                c->stream));
         for (uint64_t i = 0; i < n; ++i)
@@ -1595,8 +1681,9 @@ int pirgpu_db_load_coeffs(pirgpu_ctx* c, uint64_t first_pt, uint64_t n_pt, const
                          all_zero_bytes(reinterpret_cast<const uint8_t*>(coeffs + (pt - first_pt + i) * c->N),
                                         (size_t)c->N * 8));
         HIP_TRY(c->ops->db_encode(c->stream, c->mode, c->dp, c->k, d_coeffs, nullptr, 0, 0, c->bits, n,
-                                  c->d_db + (pt - c->pt_begin) * c->k * c->N));
+                                  c->d_db + db_row(c, pt) * c->k * c->N, 1, 0, 0));
         HIP_TRY(hipStreamSynchronize(c->stream));
+        pt += n;
       }
     } catch (...) {
       (void)hipFree(d_coeffs);
@@ -1610,7 +1697,7 @@ int pirgpu_db_load_coeffs(pirgpu_ctx* c, uint64_t first_pt, uint64_t n_pt, const
 int pirgpu_db_finalize(pirgpu_ctx* c, int release_staging) {
   return guarded(c, [&]() -> int {
     ensure_workspace(c);
-    if (c->n_loaded != c->pt_end - c->pt_begin) return fail(c, PIRGPU_FAILED_PRECONDITION, "database not fully loaded");
+    if (c->n_loaded != held_pts(c)) return fail(c, PIRGPU_FAILED_PRECONDITION, "database not fully loaded");
     ensure_packed(c);
     if (release_staging && c->mfma_on && c->d_db) {
       sync_batch_streams(c);
@@ -1628,15 +1715,15 @@ int pirgpu_db_finalize(pirgpu_ctx* c, int release_staging) {
 
 int pirgpu_db_read_plaintext(pirgpu_ctx* c, uint64_t pt_index, uint64_t* out) {
   return guarded(c, [&]() -> int {
-    if (pt_index < c->pt_begin || pt_index >= c->pt_end || !out)
+    if (pt_index < c->pt_begin || pt_index >= (c->planes > 1 ? c->planes * c->P : c->pt_end) || !out)
       return fail(c, PIRGPU_INVALID_ARGUMENT, "plaintext index outside this shard");
     uint64_t* stage = nullptr;
     HIP_TRY(hipMalloc((void**)&stage, (size_t)2 * c->k * c->N * 8));
     try {
-      const uint64_t* src = c->d_db ? c->d_db + (pt_index - c->pt_begin) * c->k * c->N : nullptr;
+      const uint64_t* src = c->d_db ? c->d_db + db_row(c, pt_index) * c->k * c->N : nullptr;
       if (!src) {  // staging released: gather the digits of this plaintext from the operand layout
         refuse_slot_shard(c);   // ... which a slot shard holds only 1 / G of
-        const uint64_t local = pt_index - c->pt_begin;
+        const uint64_t local = db_row(c, pt_index);
         uint64_t* tmp = stage + (size_t)c->k * c->N;
         HIP_TRY(launch_db_unpack(c->stream, c->dp, c->mg, c->d_dbp, tmp, (uint32_t)(local / c->scan_cols),
                                  (uint32_t)(local % c->scan_cols), c->k * c->N));
@@ -1662,20 +1749,8 @@ int pirgpu_db_read_plaintext(pirgpu_ctx* c, uint64_t pt_index, uint64_t* out) {
 
 namespace {
 
-struct DevScratch {
-  void* p = nullptr;
-  ~DevScratch() {
-    if (p) (void)hipFree(p);
-  }
-  template <typename T>
-  T* get(size_t bytes) {
-    HIP_TRY(hipMalloc(&p, std::max<size_t>(bytes, 1)));
-    return static_cast<T*>(p);
-  }
-};
-
 struct PtUpdate {
-  uint64_t local;                                     // local plaintext index
+  uint64_t local;                                     // ABI plaintext index - pt_begin (plane-major for wide items)
   const uint64_t* coeffs = nullptr;                   // update_plaintexts: its new coefficient row
   std::vector<std::pair<uint32_t, uint64_t>> items;   // update_items: (item slot in the plaintext, row of `items`)
 };
@@ -1687,14 +1762,18 @@ void quiesce(pirgpu_ctx* c) {
 }
 
 void require_loaded(pirgpu_ctx* c) {
-  if (c->n_loaded != c->pt_end - c->pt_begin || c->pt_end == c->pt_begin)
+  if (c->n_loaded != held_pts(c) || c->pt_end == c->pt_begin)
     throw Fail{PIRGPU_FAILED_PRECONDITION, "database not fully loaded (the first load is pirgpu_db_load_items / _coeffs)"};
 }
 
 void apply_update(pirgpu_ctx* c, const std::vector<PtUpdate>& pts, const uint8_t* items, uint32_t item_bytes) {
   const uint32_t N = c->N, kN = c->k * c->N;
-  const bool splice = items != nullptr;
-  const uint64_t ipp = splice ? c->prm.items_per_plaintext : 0, bpp = ipp * item_bytes;
+  // wide items: a touched plaintext is one whole plane of ONE item (items_per_plaintext = 1), nothing of the old
+  // plaintext survives -- no fetch, no inverse transform, no splice: the plane's bytes are encoded like a first load
+  const bool wide = items != nullptr && c->planes > 1;
+  const bool splice = items != nullptr && !wide;
+  const uint64_t plane_bytes = (uint64_t)N * c->bits / 8;
+  const uint64_t ipp = splice ? c->prm.items_per_plaintext : 0, bpp = wide ? plane_bytes : ipp * item_bytes;
   const bool to_packed = c->mfma_on && c->packed_valid && c->d_dbp;
   // chunks of at most 64 MB of device scratch (pirgpu_db_load_items' upload size) and 65535 units (grid.y)
   const uint64_t per_pt = (uint64_t)N * 8 + (uint64_t)kN * 8 + bpp + ipp + 8 + 4 + sizeof(DbUnit);
@@ -1705,7 +1784,7 @@ void apply_update(pirgpu_ctx* c, const std::vector<PtUpdate>& pts, const uint8_t
   uint64_t* d_enc = s_enc.get<uint64_t>(cap * kN * 8);
   uint64_t* d_loc = s_loc.get<uint64_t>(cap * 8);
   DbUnit* d_units = s_units.get<DbUnit>(cap * sizeof(DbUnit));
-  uint8_t* d_img = splice ? s_img.get<uint8_t>(cap * bpp) : nullptr;
+  uint8_t* d_img = splice || wide ? s_img.get<uint8_t>(cap * bpp) : nullptr;
   uint8_t* d_upd = splice ? s_upd.get<uint8_t>(cap * ipp) : nullptr;
   uint32_t* d_nz = splice ? s_nz.get<uint32_t>(cap * 4) : nullptr;
   std::vector<uint64_t> loc, coef_rows;
@@ -1717,7 +1796,7 @@ void apply_update(pirgpu_ctx* c, const std::vector<PtUpdate>& pts, const uint8_t
     loc.resize(n);
     units.clear();
     for (uint64_t i = 0; i < n; ++i) {
-      const uint64_t l = pts[b + i].local;
+      const uint64_t l = db_row(c, pts[b + i].local + c->pt_begin);   // row of d_db = position in the scanned matrix
       loc[i] = l;
       if (!to_packed) continue;
       const uint32_t r = (uint32_t)(l / c->scan_cols), col = (uint32_t)(l % c->scan_cols), kg = col / 16;
@@ -1727,7 +1806,17 @@ void apply_update(pirgpu_ctx* c, const std::vector<PtUpdate>& pts, const uint8_t
     HIP_TRY(hipMemcpyAsync(d_loc, loc.data(), n * 8, hipMemcpyHostToDevice, c->stream));
     if (!units.empty())
       HIP_TRY(hipMemcpyAsync(d_units, units.data(), units.size() * sizeof(DbUnit), hipMemcpyHostToDevice, c->stream));
-    if (splice) {
+    std::vector<uint8_t> zero_pt;
+    if (wide) {
+      img.assign(n * bpp, 0);
+      zero_pt.resize(n);
+      for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t off = pts[b + i].local / c->P * plane_bytes, len = std::min<uint64_t>(plane_bytes, item_bytes - off);
+        memcpy(&img[i * bpp], items + pts[b + i].items[0].second * item_bytes + off, len);
+        zero_pt[i] = all_zero_bytes(&img[i * bpp], len);
+      }
+      HIP_TRY(hipMemcpyAsync(d_img, img.data(), n * bpp, hipMemcpyHostToDevice, c->stream));
+    } else if (splice) {
       img.assign(n * bpp, 0);
       upd.assign(n * ipp, 0);
       for (uint64_t i = 0; i < n; ++i)
@@ -1751,7 +1840,10 @@ void apply_update(pirgpu_ctx* c, const std::vector<PtUpdate>& pts, const uint8_t
       HIP_TRY(hipMemcpyAsync(d_coef, coef_rows.data(), n * N * 8, hipMemcpyHostToDevice, c->stream));
     }
     // (4) lift + forward NTT, (5) write back
-    HIP_TRY(c->ops->db_encode(c->stream, c->mode, c->dp, c->k, d_coef, nullptr, 0, 0, c->bits, n, d_enc));
+    if (wide)
+      HIP_TRY(c->ops->db_encode(c->stream, c->mode, c->dp, c->k, nullptr, d_img, bpp, n * bpp, c->bits, n, d_enc, 1, 0, 0));
+    else
+      HIP_TRY(c->ops->db_encode(c->stream, c->mode, c->dp, c->k, d_coef, nullptr, 0, 0, c->bits, n, d_enc, 1, 0, 0));
     if (c->d_db) HIP_TRY(launch_copy_rows(c->stream, d_enc, c->d_db, nullptr, d_loc, n, kN, kN, kN));
     if (to_packed)
       HIP_TRY(launch_db_pack_update(c->stream, c->dp, c->mg, d_enc, d_units, (uint32_t)units.size(), c->d_dbp, kN,
@@ -1762,8 +1854,8 @@ void apply_update(pirgpu_ctx* c, const std::vector<PtUpdate>& pts, const uint8_t
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (uint64_t i = 0; i < n; ++i)
-      note_plaintext(c, loc[i],
-                     splice ? nz[i] == 0
+      note_plaintext(c, pts[b + i].local,
+                     wide ? zero_pt[i] != 0 : splice ? nz[i] == 0
                             : all_zero_bytes(reinterpret_cast<const uint8_t*>(pts[b + i].coeffs), (size_t)N * 8));
   }
 }
@@ -1796,6 +1888,14 @@ int pirgpu_db_update_items(pirgpu_ctx* c, uint64_t n, const uint64_t* item_indic
       if (pt >= c->pt_begin && pt < c->pt_end) last[item_indices[i]] = i;   // other row shards' items are skipped
     }
     std::vector<PtUpdate> pts;
+    if (c->planes > 1) {   // every plane of every touched item, plane-major (= ascending rows of the scanned matrix)
+      for (uint32_t pl = 0; pl < c->planes; ++pl)
+        for (const auto& e : last) {
+          pts.push_back(PtUpdate{pl * c->P + e.first});
+          pts.back().items.emplace_back(0u, e.second);
+        }
+      last.clear();
+    }
     for (const auto& e : last) {
       const uint64_t local = e.first / ipp - c->pt_begin;
       if (pts.empty() || pts.back().local != local) pts.push_back(PtUpdate{local});
@@ -1815,16 +1915,16 @@ int pirgpu_db_update_plaintexts(pirgpu_ctx* c, uint64_t n, const uint64_t* pt_in
     if (!pt_indices || !coeffs) return fail(c, PIRGPU_INVALID_ARGUMENT, "null plaintext indices or coefficients");
     const uint64_t t = c->prm.plain_modulus;
     for (uint64_t i = 0; i < n; ++i) {
-      if (pt_indices[i] >= c->P)
+      if (pt_indices[i] >= c->planes * c->P)
         return fail(c, PIRGPU_INVALID_ARGUMENT, "plaintext index " + std::to_string(pt_indices[i]) + " out of range (" +
-                                                    std::to_string(c->P) + " plaintexts)");
+                                                    std::to_string(c->planes * c->P) + " plaintexts)");
       const uint64_t* row = coeffs + i * c->N;
       for (uint32_t x = 0; x < c->N; ++x)
         if (row[x] >= t) return fail(c, PIRGPU_INVALID_ARGUMENT, "coefficient not below the plain modulus");
     }
     std::map<uint64_t, uint64_t> last;   // local plaintext -> row of `coeffs` (a later entry wins)
     for (uint64_t i = 0; i < n; ++i)
-      if (pt_indices[i] >= c->pt_begin && pt_indices[i] < c->pt_end) last[pt_indices[i] - c->pt_begin] = i;
+      if (c->planes > 1 || (pt_indices[i] >= c->pt_begin && pt_indices[i] < c->pt_end)) last[pt_indices[i] - c->pt_begin] = i;
     std::vector<PtUpdate> pts;
     for (const auto& e : last) {
       pts.push_back(PtUpdate{e.first});
@@ -2856,7 +2956,7 @@ static void batch_run_impl_body(pirgpu_ctx* c, uint32_t count, const uint64_t* e
   const size_t svwords = (size_t)c->dim_sum * c->ctw;
   const uint32_t W = std::max<uint32_t>(1, std::min<uint32_t>(c->n_active, (uint32_t)c->workers.size()));
   const uint32_t G = mq_usable(c) && c->pt_end > c->pt_begin ? std::min<uint32_t>(c->mq_nq, kMaxScanQueries) : 1;
-  if (c->n_loaded != c->pt_end - c->pt_begin)
+  if (c->n_loaded != held_pts(c))
     throw Fail{PIRGPU_FAILED_PRECONDITION, "database not fully loaded"};
   check_transparent(c);
   check_reply_target(c, count);
@@ -2991,7 +3091,7 @@ uint64_t pirgpu_packed_selector_bytes(pirgpu_ctx* c) {
   (void)guarded(c, [&]() -> int {
     ensure_workspace(c);
     // d = 2 only (dimension 0 = rows, dimension 1 = the scanned columns) and the shard scanned by the MFMA kernel
-    if (c->d == 2 && c->mfma_on) bytes = c->mg.sel_bytes;
+    if (c->d == 2 && c->mfma_on && c->planes == 1) bytes = c->mg.sel_bytes;
     return PIRGPU_OK;
   });
   return bytes;
@@ -3000,6 +3100,7 @@ uint64_t pirgpu_packed_selector_bytes(pirgpu_ctx* c) {
 static int batch_expand_packed_impl(pirgpu_ctx* c, uint32_t first_query, uint32_t count, uint8_t* device_packed,
                                     uint64_t* device_rows, const uint32_t* row_cuts, uint32_t n_ranks, bool wait) {
   return guarded(c, [&]() -> int {
+    refuse_wide(c);
     ensure_workspace(c);
     if (c->d != 2 || !c->mfma_on)
       return fail(c, PIRGPU_FAILED_PRECONDITION, "packed selector exchange needs d = 2 and the int8-MFMA scan");
@@ -3066,13 +3167,14 @@ int pirgpu_batch_expand_packed_async(pirgpu_ctx* c, uint32_t first_query, uint32
 int pirgpu_batch_run_packed(pirgpu_ctx* c, const uint8_t* device_packed, uint32_t n_ranks, uint32_t per_rank,
                             const uint64_t* device_rows) {
   return guarded(c, [&]() -> int {
+    refuse_wide(c);
     ensure_workspace(c);
     if (c->d != 2 || !c->mfma_on)
       return fail(c, PIRGPU_FAILED_PRECONDITION, "packed selector exchange needs d = 2 and the int8-MFMA scan");
     refuse_slot_shard(c);
     const uint64_t count = (uint64_t)n_ranks * per_rank;
     if (!device_packed || !device_rows || count == 0 || count > 4096) return fail(c, PIRGPU_INVALID_ARGUMENT, "invalid batch");
-    if (c->n_loaded != c->pt_end - c->pt_begin) return fail(c, PIRGPU_FAILED_PRECONDITION, "database not fully loaded");
+    if (c->n_loaded != held_pts(c)) return fail(c, PIRGPU_FAILED_PRECONDITION, "database not fully loaded");
     check_transparent(c);
     check_reply_target(c, count);
     ensure_packed(c);
@@ -3137,6 +3239,7 @@ void lane_then(BatchLane& ln, void* then) {
 }
 
 void check_slots_ctx(pirgpu_ctx* c) {
+  refuse_wide(c);
   ensure_workspace(c);
   if (c->d != 2 || !c->mfma_on || c->mg.nchunks != 1 || c->sb != 0 || c->se != c->dims[0])
     throw Fail{PIRGPU_FAILED_PRECONDITION, "the slot-sharded step needs d = 2, all rows and the int8-MFMA scan in one column chunk"};
@@ -3148,7 +3251,7 @@ uint64_t pirgpu_slots_packed_bytes(pirgpu_ctx* c, uint32_t slots) {
   uint64_t bytes = 0;
   (void)guarded(c, [&]() -> int {
     ensure_workspace(c);
-    if (c->d == 2 && c->mfma_on && c->mg.nchunks == 1) bytes = (uint64_t)slots * c->mg.KG * c->mg.tile_bytes;
+    if (c->d == 2 && c->mfma_on && c->mg.nchunks == 1 && c->planes == 1) bytes = (uint64_t)slots * c->mg.KG * c->mg.tile_bytes;
     return PIRGPU_OK;
   });
   return bytes;
@@ -3207,7 +3310,7 @@ int pirgpu_slots_scan_async(pirgpu_ctx* c, const uint8_t* device_packed, uint32_
     check_slots_ctx(c);
     const uint64_t count = (uint64_t)n_ranks * per_rank;
     if (!device_packed || !device_rowsums || count == 0 || count > 4096) return fail(c, PIRGPU_INVALID_ARGUMENT, "invalid batch");
-    if (c->n_loaded != c->pt_end - c->pt_begin) return fail(c, PIRGPU_FAILED_PRECONDITION, "database not fully loaded");
+    if (c->n_loaded != held_pts(c)) return fail(c, PIRGPU_FAILED_PRECONDITION, "database not fully loaded");
     check_transparent(c);
     ensure_packed(c);
     ensure_lanes(c, true);

@@ -56,9 +56,11 @@ struct NttOps {
   // same transform for B interleaved queries (source ciphertext i*B + q -> dst.p[q] + i): batched expansion
   hipError_t (*ct_ntt_fwd_split)(hipStream_t st, int mode, const DevParams* P, uint32_t k, const uint64_t* src,
                                  const MfmaPtrs& dst, uint32_t B, uint64_t n_cts_total);
+  // planes > 1 (wide items, byte source only): source row pt is a whole item of bytes_per_pt bytes and plane j encodes
+  // its bytes [j * plane_bytes, min((j + 1) * plane_bytes, bytes_per_pt)) into plaintext j * plane_stride + pt of db
   hipError_t (*db_encode)(hipStream_t st, int mode, const DevParams* P, uint32_t k, const uint64_t* coeffs,
                           const uint8_t* bytes, uint64_t bytes_per_pt, uint64_t total_bytes, uint32_t bits,
-                          uint64_t n_pt, uint64_t* db);
+                          uint64_t n_pt, uint64_t* db, uint32_t planes, uint64_t plane_bytes, uint64_t plane_stride);
   // c0_out != nullptr (fp64 flavours, ks_digit_takes_c0(nodes)): the launch also writes NTT(c0) of every node into the
   // product buffer c0_out (NTT-domain last level), sparing ks_last_ntt its own launch for that (c0_done)
   // tree40: res_in holds the tree in the 5-byte form (wide levels of the fused expansion, ks_mac_combine's tout40)

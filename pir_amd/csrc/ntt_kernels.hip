@@ -416,18 +416,22 @@ ct_ntt_fwd_split_kernel(const DevParams* __restrict__ P, const uint64_t* __restr
   for (int e = 0; e < EPT; ++e) out[e * NT + tid] = A::out(x[e], m);
 }
 
-// grid = (n_pt, k).  Source is either pre-encoded coefficients (coeffs != null)
+// grid = (n_pt, k, planes).  Source is either pre-encoded coefficients (coeffs != null)
 // or raw item bytes packed MSB-first into bits-wide coefficients
 // (reference string_encoder.cpp:58-122); then plain lift + forward NTT.
+// Wide items (gridDim.z = planes > 1): source row pt is one item of bytes_per_pt bytes, and plane blockIdx.z packs
+// the item's bytes [z * plane_bytes, min((z + 1) * plane_bytes, bytes_per_pt)) -- a plane boundary is a coefficient
+// boundary, plane_bytes * 8 = N * bits -- into plaintext z * plane_stride + pt.
 template <int MODE>
 __global__ void __launch_bounds__(NT)
 db_encode_kernel(const DevParams* __restrict__ P, const uint64_t* __restrict__ coeffs,
                  const uint8_t* __restrict__ bytes, uint64_t bytes_per_pt, uint64_t total_bytes, uint32_t bits,
-                 uint64_t* __restrict__ db) {
+                 uint64_t* __restrict__ db, uint64_t plane_bytes, uint64_t plane_stride) {
   using A = Arith<MODE>;
   const uint32_t tid = threadIdx.x, k = P->k;
   const uint32_t j = blockIdx.y;
   const uint64_t pt = blockIdx.x;
+  const uint64_t plane_off = blockIdx.z * plane_bytes;   // 0 unless wide
   const ModConst mc = P->mod[j];
   const typename A::Mod m = A::mod(P, j);
   const uint64_t thr = P->plain_thr;
@@ -435,8 +439,10 @@ db_encode_kernel(const DevParams* __restrict__ P, const uint64_t* __restrict__ c
   uint64_t L = 0;
   const uint8_t* src = nullptr;
   if (!coeffs) {
-    uint64_t start = pt * bytes_per_pt;
-    L = start >= total_bytes ? 0 : (total_bytes - start < bytes_per_pt ? total_bytes - start : bytes_per_pt);
+    const uint64_t start = pt * bytes_per_pt + plane_off;
+    uint64_t len = bytes_per_pt - plane_off;               // what the item has left for this plane ...
+    if (gridDim.z > 1 && len > plane_bytes) len = plane_bytes;   // ... at most one plaintext's worth
+    L = start >= total_bytes ? 0 : (total_bytes - start < len ? total_bytes - start : len);
     src = bytes + start;
   }
   typename A::T x[EPT];
@@ -468,7 +474,7 @@ db_encode_kernel(const DevParams* __restrict__ P, const uint64_t* __restrict__ c
     x[e] = A::in(r, m);
   }
   ntt_forward<MODE, LOGN, kPF>(x, smem_raw, P, j, tid);
-  uint64_t* out = db + (pt * k + j) * N;
+  uint64_t* out = db + ((blockIdx.z * plane_stride + pt) * k + j) * N;
 #pragma unroll
   for (int e = 0; e < EPT; ++e) out[e * NT + tid] = A::out(x[e], m);
 }
@@ -1738,9 +1744,14 @@ static hipError_t op_ct_ntt_fwd_split(hipStream_t st, int mode, const DevParams*
 
 static hipError_t op_db_encode(hipStream_t st, int mode, const DevParams* P, uint32_t k, const uint64_t* coeffs,
                                const uint8_t* bytes, uint64_t bytes_per_pt, uint64_t total_bytes, uint32_t bits,
-                               uint64_t n_pt, uint64_t* db) {
-  PIRGPU_BY_MODE(mode, hipLaunchKernelGGL(db_encode_kernel<MODE>, dim3((uint32_t)n_pt, k), dim3(NT), kLdsBytes, st,
-                                          P, coeffs, bytes, bytes_per_pt, total_bytes, bits, db));
+                               uint64_t n_pt, uint64_t* db, uint32_t planes, uint64_t plane_bytes,
+                               uint64_t plane_stride) {
+  if (planes < 1 || (planes > 1 && (coeffs || !plane_bytes || (uint64_t)(planes - 1) * plane_bytes >= bytes_per_pt)))
+    return hipErrorInvalidValue;
+  if (!n_pt) return hipSuccess;
+  PIRGPU_BY_MODE(mode, hipLaunchKernelGGL(db_encode_kernel<MODE>, dim3((uint32_t)n_pt, k, planes), dim3(NT), kLdsBytes, st,
+                                          P, coeffs, bytes, bytes_per_pt, total_bytes, bits, db,
+                                          planes > 1 ? plane_bytes : 0, planes > 1 ? plane_stride : 0));
   return hipGetLastError();
 }
 

@@ -304,10 +304,12 @@ __global__ void __launch_bounds__(kEw) ks_mac_kernel(const DevParams* __restrict
 
 // db_encode, part 1: bits-wide coefficients packed MSB-first from the item bytes (reference string_encoder.cpp:58-122)
 // or pre-encoded ones, then the plain lift (Evaluator::transform_to_ntt_inplace(Plaintext)) into
-// db[pt][j]; the batched forward transform follows.
+// db[pt][j]; the batched forward transform follows.  Wide items: one launch per plane, which packs the bytes
+// [src_off, src_off + src_len) of every source row (an item of bytes_per_pt bytes); otherwise 0, bytes_per_pt.
 __global__ void __launch_bounds__(kEw) db_lift_kernel(const DevParams* __restrict__ P, const uint64_t* __restrict__ coeffs,
                                                       const uint8_t* __restrict__ bytes, uint64_t bytes_per_pt,
-                                                      uint64_t total_bytes, uint32_t bits, uint64_t* __restrict__ db) {
+                                                      uint64_t total_bytes, uint32_t bits, uint64_t* __restrict__ db,
+                                                      uint64_t src_off, uint64_t src_len) {
   const uint64_t gid = (uint64_t)blockIdx.x * kEw + threadIdx.x;
   const uint32_t k = P->k, c = (uint32_t)(gid & (N - 1));
   const uint64_t poly = gid >> LOGN, pt = poly / k;
@@ -317,8 +319,8 @@ __global__ void __launch_bounds__(kEw) db_lift_kernel(const DevParams* __restric
   if (coeffs) {
     v = coeffs[pt * N + c];
   } else {
-    const uint64_t start = pt * bytes_per_pt;
-    const uint64_t L = start >= total_bytes ? 0 : (total_bytes - start < bytes_per_pt ? total_bytes - start : bytes_per_pt);
+    const uint64_t start = pt * bytes_per_pt + src_off;
+    const uint64_t L = start >= total_bytes ? 0 : (total_bytes - start < src_len ? total_bytes - start : src_len);
     const uint8_t* src = bytes + start;
     uint64_t bitpos = (uint64_t)c * bits, byte = bitpos >> 3;
     uint32_t off = (uint32_t)(bitpos & 7);
@@ -453,13 +455,22 @@ static hipError_t op_ct_ntt_fwd_split(hipStream_t st, int mode, const DevParams*
 
 static hipError_t op_db_encode(hipStream_t st, int mode, const DevParams* P, uint32_t k, const uint64_t* coeffs,
                                const uint8_t* bytes, uint64_t bytes_per_pt, uint64_t total_bytes, uint32_t bits,
-                               uint64_t n_pt, uint64_t* db) {
+                               uint64_t n_pt, uint64_t* db, uint32_t planes, uint64_t plane_bytes,
+                               uint64_t plane_stride) {
   if (mode != kNttInt) return hipErrorInvalidValue;
+  if (planes < 1 || (planes > 1 && (coeffs || !plane_bytes || (uint64_t)(planes - 1) * plane_bytes >= bytes_per_pt)))
+    return hipErrorInvalidValue;
   if (!n_pt) return hipSuccess;
-  hipLaunchKernelGGL(db_lift_kernel, ew_grid(n_pt * k), dim3(kEw), 0, st, P, coeffs, bytes, bytes_per_pt, total_bytes,
-                     bits, db);
-  if (hipError_t e = hipGetLastError()) return e;
-  return transform(st, P, contiguous(db, db, 1, k, 0), n_pt * k, false);
+  for (uint32_t pl = 0; pl < planes; ++pl) {   // plane pl of every item -> plaintexts pl * plane_stride + [0, n_pt)
+    uint64_t* dst = db + (size_t)pl * plane_stride * k * N;
+    const uint64_t off = planes > 1 ? pl * plane_bytes : 0;
+    const uint64_t len = planes > 1 && bytes_per_pt - off > plane_bytes ? plane_bytes : bytes_per_pt - off;
+    hipLaunchKernelGGL(db_lift_kernel, ew_grid(n_pt * k), dim3(kEw), 0, st, P, coeffs, bytes, bytes_per_pt, total_bytes,
+                       bits, dst, off, len);
+    if (hipError_t e = hipGetLastError()) return e;
+    if (hipError_t e = transform(st, P, contiguous(dst, dst, 1, k, 0), n_pt * k, false)) return e;
+  }
+  return hipSuccess;
 }
 
 // u64 digits only: no packed intermediates (ctx.hip turns pack40 off at this degree), no 5-byte tree, no c0 products

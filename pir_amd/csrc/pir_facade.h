@@ -11,6 +11,7 @@
 //   std::string request / response   serialized pir.Request / pir.Response (payload.proto)
 // Every method is a thin call into libpirgpu (include/pirgpu.h); nothing is computed here.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <map>
 #include <memory>
@@ -64,6 +65,7 @@ struct PIRParameters {
   std::vector<uint32_t> dimensions;
   uint32_t bytes_per_item = 0, items_per_plaintext = 0, bits_per_coeff = 0;
   bool use_ciphertext_multiplication = false;
+  uint32_t plaintexts_per_item = 1;      // wide items (not in the reference): pirgpu_params.plaintexts_per_item
   size_t DimensionsSum() const {          // PIRContext::DimensionsSum, context.h:59-62
     size_t s = 0;
     for (auto d : dimensions) s += d;
@@ -104,6 +106,7 @@ class PIRDatabase {
     p.items_per_plaintext = params->items_per_plaintext;
     p.bits_per_coeff = params->bits_per_coeff;
     p.use_ciphertext_multiplication = params->use_ciphertext_multiplication ? 1 : 0;
+    p.plaintexts_per_item = params->plaintexts_per_item;
     p.device = device;
     pirgpu_ctx* ctx = nullptr;
     int rc = pirgpu_create(&p, &ctx);
@@ -204,7 +207,7 @@ class PIRServer {
   // server.cpp:35-42
   static StatusOr<std::unique_ptr<PIRServer>> Create(std::shared_ptr<PIRDatabase> db,
                                                      std::shared_ptr<PIRParameters> params) {
-    if (params->num_pt != db->size()) return InvalidArgumentError("database size mismatch");
+    if (params->num_pt * std::max<uint32_t>(1, params->plaintexts_per_item) != db->size()) return InvalidArgumentError("database size mismatch");
     return std::unique_ptr<PIRServer>(new PIRServer(std::move(db), std::move(params)));
   }
 

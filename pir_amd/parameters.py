@@ -133,6 +133,22 @@ class PIRParameters:
     items_per_plaintext: int
     bits_per_coeff: int = 0
     use_ciphertext_multiplication: bool = False
+    plaintexts_per_item: int = 1      # wide items (not in the reference): planes an item is spread over
+
+    @property
+    def planes(self) -> int:
+        return max(1, self.plaintexts_per_item)
+
+    @property
+    def max_bytes_per_plaintext(self) -> int:  # string_encoder.cpp:29-31
+        enc = self.encryption_parameters
+        bpc = self.bits_per_coeff or bits_per_coeff(enc.plain_modulus)
+        return enc.poly_modulus_degree * bpc // 8
+
+    def plane_bytes(self, plane: int) -> range:
+        """Byte range of an item that plane `plane` holds."""
+        B = self.max_bytes_per_plaintext
+        return range(plane * B, min((plane + 1) * B, self.bytes_per_item))
 
     @property
     def dim_sum(self) -> int:
@@ -153,8 +169,11 @@ class PIRParameters:
 
 def create_pir_parameters(dbsize: int, bytes_per_item: int = 0, dimensions: int = 1,
                           enc: Optional[EncryptionParams] = None, use_ciphertext_multiplication: bool = False,
-                          bits_per_coeff_: int = 0) -> PIRParameters:
-    """CreatePIRParameters (parameters.cpp:56-107); raises ValueError where it returns InvalidArgument."""
+                          bits_per_coeff_: int = 0, max_plaintexts_per_item: int = 1) -> PIRParameters:
+    """CreatePIRParameters (parameters.cpp:56-107); raises ValueError where it returns InvalidArgument.
+
+    max_plaintexts_per_item > 1 (not in the reference) opts in to wide items: an item that does not fit one plaintext is
+    spread over ceil(bytes_per_item / max_bytes_per_plaintext) plaintexts (planes), at most that many."""
     if enc is None:
         enc = generate_encryption_params()
     N, t = enc.poly_modulus_degree, enc.plain_modulus
@@ -163,10 +182,17 @@ def create_pir_parameters(dbsize: int, bytes_per_item: int = 0, dimensions: int 
         if bits_per_coeff_ > bpc:
             raise ValueError("Bits per coefficient greater than max")
         bpc = bits_per_coeff_
+    planes = 1
     if bytes_per_item > 0:
         ipp = N * bpc // bytes_per_item // 8          # string_encoder.cpp:25-27
         if ipp <= 0:
-            raise ValueError("Cannot fit an item within one plaintext")
+            if max_plaintexts_per_item <= 1:
+                raise ValueError("Cannot fit an item within one plaintext")
+            B = N * bpc // 8
+            planes = -(-bytes_per_item // B) if B > 0 else max_plaintexts_per_item + 1
+            if planes > max_plaintexts_per_item:
+                raise ValueError("Cannot fit an item within %d plaintexts" % max_plaintexts_per_item)
+            ipp = 1
         num_pt = dbsize // ipp
         while dbsize > num_pt * ipp:
             num_pt += 1
@@ -177,4 +203,5 @@ def create_pir_parameters(dbsize: int, bytes_per_item: int = 0, dimensions: int 
         num_pt = dbsize
     return PIRParameters(num_items=dbsize, num_pt=num_pt, dimensions=calculate_dimensions(num_pt, dimensions),
                          encryption_parameters=enc, bytes_per_item=bpi, items_per_plaintext=ipp,
-                         bits_per_coeff=bits_per_coeff_, use_ciphertext_multiplication=use_ciphertext_multiplication)
+                         bits_per_coeff=bits_per_coeff_, use_ciphertext_multiplication=use_ciphertext_multiplication,
+                         plaintexts_per_item=planes)

@@ -197,6 +197,11 @@ class PIRDatabase:
     def reply_ct_count(self) -> int:
         return int(self.lib.pirgpu_reply_ct_count(self._h))
 
+    def planes(self) -> int:
+        """Plaintexts per item (wide items; 1: the reference's layout).  Plaintext indices of read_plaintext,
+        populate_coeffs and update_plaintexts are plane-major: plane * num_pt + pt."""
+        return int(self.lib.pirgpu_planes(self._h))
+
     def expansion_ratio(self) -> int:
         return int(self.lib.pirgpu_expansion_ratio(self._h))
 
@@ -233,7 +238,7 @@ class PIRServer:
     def Create(cls, db: PIRDatabase, params: PIRParameters) -> "PIRServer":
         """server.cpp:35-42"""
         full = db._cparams.shard_begin == 0 and db._cparams.shard_end in (0, params.dimensions[0])
-        if full and params.num_pt != db.size():
+        if full and params.num_pt * getattr(params, "planes", 1) != db.size():
             raise PirGpuError(3, "database size mismatch")
         return cls(db, params)
 
