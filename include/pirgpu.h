@@ -473,6 +473,13 @@ int pirgpu_get_option(pirgpu_ctx* ctx, const char* name, int64_t* value);
  * Chosen from the largest modulus; PIRGPU_NTT_MODE=0|2 in the environment at pirgpu_create forces a more general
  * flavour (all three produce identical residues -- tests/test_gpu_ntt_modes.py). */
 int pirgpu_ntt_mode(const pirgpu_ctx* ctx);
+/* Which arithmetic paths the moduli (and the options) selected for this context; read-only.  info[0] = the flavour of
+ * pirgpu_ntt_mode, info[1] = 1 if the fp64 inverse transform runs without per-pass renormalisation (bits of the
+ * largest modulus + log2 N <= 52), info[2] = bytes per residue of the packed key-switch intermediates (5 / 6 / 7;
+ * 8 = unpacked 64-bit words or doubles), info[3] = 1 if the expansion tree between fused levels is stored packed as
+ * well, info[4] = 128-bit products summed before a reduction (2^(128 - 2 bits), at most 2^30), info[5] = flags: bit 0 =
+ * fp64 fold of the scan's digit diagonals for single queries, bit 1 = for groups of queries, bit 2 = 28-bit limb accumulators in the 64-bit scan; info[6..7] = 0. */
+int pirgpu_arith_info(pirgpu_ctx* ctx, uint32_t info[8]);
 
 #ifdef __cplusplus
 }

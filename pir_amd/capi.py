@@ -174,6 +174,7 @@ SIGNATURES = {
     "pirgpu_batch_scan_timings": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "pirgpu_scan_bytes": (C.c_uint64, [C.c_void_p]),
     "pirgpu_scan_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "pirgpu_arith_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
 }
 
 _lib = None

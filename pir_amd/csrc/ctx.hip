@@ -1569,6 +1569,21 @@ uint64_t pirgpu_scan_bytes(const pirgpu_ctx* cc) {
 
 int pirgpu_ntt_mode(const pirgpu_ctx* c) { return c ? c->mode : -1; }
 
+int pirgpu_arith_info(pirgpu_ctx* c, uint32_t info[8]) {
+  return guarded(c, [&]() -> int {
+    if (!info) return fail(c, PIRGPU_INVALID_ARGUMENT, "null info");
+    ensure_workspace(c);
+    info[0] = (uint32_t)c->mode;
+    info[1] = c->mode == kNttF64 ? c->hp.f64_lazy_inv : 0u;   // only the exact-fp64 flavour reads the flag (ntt_core.h)
+    info[2] = c->pack40 ? (uint32_t)c->pack_bytes : 8u;
+    info[3] = c->tree40 && c->pack40 ? 1u : 0u;
+    info[4] = c->hp.lazy_limit;
+    info[5] = (c->scan_f64_fold ? 1u : 0u) | (c->scan_f64_fold_batch ? 2u : 0u) | (c->scan_limb ? 4u : 0u);
+    info[6] = info[7] = 0;
+    return PIRGPU_OK;
+  });
+}
+
 int pirgpu_scan_info(pirgpu_ctx* c, uint32_t info[8]) {
   return guarded(c, [&]() -> int {
     if (!info) return fail(c, PIRGPU_INVALID_ARGUMENT, "null info");

@@ -628,6 +628,14 @@ class PIRServer:
         """0 integer / 1 fp64 / 2 wide fp64 butterflies (pirgpu_ntt_mode)."""
         return int(self.lib.pirgpu_ntt_mode(self.db.handle))
 
+    def arith_info(self) -> dict:
+        """Which arithmetic paths the moduli selected (pirgpu_arith_info); read-only."""
+        info = (C.c_uint32 * 8)()
+        self._check(self.lib.pirgpu_arith_info(self.db.handle, info))
+        return {"ntt_mode": info[0], "f64_lazy_inv": bool(info[1]), "pack_bytes": info[2], "tree40": bool(info[3]),
+                "lazy_limit": info[4], "scan_f64_fold": bool(info[5] & 1), "scan_f64_fold_batch": bool(info[5] & 2),
+                "scan_limb": bool(info[5] & 4)}
+
     def scan_bytes(self) -> int:
         return int(self.lib.pirgpu_scan_bytes(self.db.handle))
 

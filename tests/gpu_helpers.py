@@ -28,6 +28,42 @@ def random_key(orc, rng):
     return key
 
 
+def chain(N, data_bits, special_bits=None):
+    """Coefficient modulus chain with data primes of `data_bits` bits each (an int = two of that size, or a list) and
+    a special prime of `special_bits` (default: the largest data size), found the way SEAL's CoeffModulus::Create does."""
+    data = [data_bits, data_bits] if isinstance(data_bits, int) else list(data_bits)
+    return oracle.coeff_modulus_create(N, data + [max(data) if special_bits is None else special_bits])
+
+
+def structured_patterns(q, N, rng):
+    """Deterministic worst-case residue vectors of one modulus: [(name, uint64[N])].  Random inputs stay a factor
+    sqrt(N) inside the worst-case bounds of the transforms; these sit on them."""
+    q = int(q)
+    pos = np.arange(N)
+    full = lambda v: np.full(N, v, dtype=np.uint64)
+    out = [("all 0", full(0)), ("all q-1", full(q - 1)), ("all q/2", full(q // 2)), ("all q/2+1", full(q // 2 + 1))]
+    for i in (0, 1, N // 2, N - 1):
+        for c in (1, q - 1):
+            v = full(0)
+            v[i] = c
+            out.append(("%d * delta_%d" % (c, i), v))
+    for b in range(N.bit_length() - 1):
+        m = ((pos >> b) & 1).astype(bool)
+        out.append(("bit %d set -> q-1" % b, np.where(m, q - 1, 0).astype(np.uint64)))
+        out.append(("bit %d clear -> q-1" % b, np.where(m, 0, q - 1).astype(np.uint64)))
+    out.append(("random top", (q - 1 - rng.integers(0, 1000, size=N)).astype(np.uint64)))
+    out.append(("alternating 0 / q-1", np.where(pos & 1, q - 1, 0).astype(np.uint64)))
+    return out
+
+
+def device_to_seal_order(a):
+    """NTT-domain polynomials in device order (last axis; slot e * N/16 + tid holds SEAL position 16 * tid + e,
+    pir_amd/csrc/ntt_core.h) -> SEAL's order."""
+    a = np.asarray(a)
+    N = a.shape[-1]
+    return np.ascontiguousarray(a.reshape(a.shape[:-1] + (16, N // 16)).swapaxes(-1, -2).reshape(a.shape))
+
+
 def all_to_all_in_process(recvs, sends, recv_splits, send_splits):
     """What torch.distributed.all_to_all_single does, between in-process 'ranks' (1-D tensors, element splits)."""
     G = len(sends)
