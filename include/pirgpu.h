@@ -78,10 +78,12 @@ typedef struct pirgpu_params {
    * pirgpu_slots_* step only; 0,0 = all slots.  (The base case of PIRDatabase::multiply, reference database.cpp:185-194,
    * is a dyadic product in NTT form: independent per slot.)
    * Memory: AFTER pirgpu_db_finalize(ctx, 1) such a context holds (slot_end - slot_begin) / (k N) of the packed database.
-   * WHILE it is being loaded it holds the full u64 staging copy of every plaintext as well (every rank encodes and
-   * transforms the whole database, then packs its own slots out of it): the load-time peak per rank is the whole
-   * database at 8 bytes per residue + its share of the operand layout, so slot sharding spreads the scan's bytes, not yet a
-   * database larger than one GPU's memory (that needs the encode + pack in row blocks). */
+   * WHILE it is being loaded, a context made by pirgpu_create holds the full u64 staging copy of every plaintext as well
+   * (every rank encodes and transforms the whole database, then packs its own slots out of it): the whole database at
+   * 8 bytes per residue + its share of the operand layout.  A STREAMED context (pirgpu_create_ex with
+   * PIRGPU_CREATE_STREAMED_DB) encodes and packs in row bands and never has the staging copy: the per-rank load-time peak
+   * is the rank's share of the operand layout plus one load chunk (option DB_STREAM_MB of encoded plaintexts + their raw
+   * bytes), so slot shards hold a database larger than one GPU's memory. */
   uint32_t slot_begin;
   uint32_t slot_end;
   /* Wide items (not in the reference, whose CreatePIRParameters refuses an item larger than one plaintext,
@@ -99,6 +101,19 @@ typedef struct pirgpu_params {
 /* PIRContext::Create + PIRDatabase::Create(params) (reference context.cpp:37-50,
  * database.cpp:40-44): validates the parameters, builds NTT tables on the device. */
 int pirgpu_create(const pirgpu_params* params, pirgpu_ctx** out);
+/* pirgpu_create with flags (0: exactly pirgpu_create; unknown bits: InvalidArgument).
+ * PIRGPU_CREATE_STREAMED_DB: the u64 staging copy of the database is never allocated (not in the reference; DESIGN.md
+ * section 6.3).  Loads encode chunks of whole row bands -- 16 rows of the scanned matrix, option "db_stream_mb"
+ * (default 256) megabytes of encoded plaintexts per chunk, at least one band -- into a scratch and store them straight
+ * into the operand layout of the int8-MFMA scan, which is allocated (zero-filled) when the context is first used; the
+ * load-time peak is that layout plus one chunk instead of plus 8 bytes per residue of the whole database.  Afterwards the
+ * context behaves like one that was populated and then given pirgpu_db_finalize(ctx, 1) -- queries, updates,
+ * pirgpu_db_read_plaintext, the refusals of a slot shard -- except that it CAN be reloaded (a load overwrites), and
+ * pirgpu_db_finalize succeeds and frees nothing.  d = 1 is InvalidArgument here (its scans read the staging copy); a
+ * context whose int8-MFMA scan is off (fewer than 8 rows, a modulus of 2^55 or more, option scan_mfma = 0) is created,
+ * but its first load returns FailedPrecondition before anything is allocated for the database. */
+#define PIRGPU_CREATE_STREAMED_DB 1u
+int pirgpu_create_ex(const pirgpu_params* params, uint32_t flags, pirgpu_ctx** out);
 void pirgpu_destroy(pirgpu_ctx* ctx);
 /* Message of the calling thread's last failed call on this context (falls back to the context's last
  * failure when this thread has none). */
@@ -167,6 +182,15 @@ int pirgpu_set_remote_zero_plaintexts(pirgpu_ctx* ctx, uint64_t count);
 int pirgpu_check_ready(pirgpu_ctx* ctx);
 /* Test hook: read back one encoded plaintext [k][N] (NTT form) from HBM (wide items: pt_index = plane * num_pt + pt). */
 int pirgpu_db_read_plaintext(pirgpu_ctx* ctx, uint64_t pt_index, uint64_t* out);
+/* Device memory of the database, counted by the library at its own allocation sites (not a query of the device: other
+ * processes may share it).  out[0] bytes of the operand-layout copy, out[1] bytes of the u64 staging copy (0 on a streamed
+ * context, always), out[2] the largest number of bytes operand copy + staging copy + load/update scratch (raw upload
+ * buffers, encode scratch, unit lists) ever held at once on this context, out[3] band_bytes of a streamed context --
+ * 16 rows of the scanned matrix as u64 residues, the unit of its load chunks -- (0 otherwise).  Fixes the workspace
+ * geometry like a first query (set workspace-shaping options before). */
+int pirgpu_db_memory(const pirgpu_ctx* ctx, uint64_t out[4]);
+/* Test hook: bytes [offset, offset + n) of the operand-layout copy (FailedPrecondition before it exists). */
+int pirgpu_db_read_operand(pirgpu_ctx* ctx, uint64_t offset, uint64_t n, uint8_t* out);
 
 /* What SEALDeserialize<GaloisKeys> yields per request (reference server.cpp:46-48):
  * install the key for one Galois element.  Keys stay on the device until cleared.

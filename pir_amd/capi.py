@@ -9,6 +9,7 @@ LIB_PATH = os.environ.get("PIRGPU_LIB", os.path.join(HERE, "libpirgpu.so"))   # 
 
 MAX_PRIMES, MAX_DIMS = 8, 8
 OK, INVALID_ARGUMENT, FAILED_PRECONDITION, UNIMPLEMENTED, INTERNAL = 0, 3, 9, 12, 13
+CREATE_STREAMED_DB = 1          # pirgpu_create_ex flag
 
 u64p = C.POINTER(C.c_uint64)
 u8p = C.POINTER(C.c_uint8)
@@ -72,6 +73,7 @@ def make_params(params, device: int = 0, shard=None, slots=None) -> Params:
 # every symbol include/pirgpu.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "pirgpu_create": (C.c_int, [C.POINTER(Params), C.POINTER(C.c_void_p)]),
+    "pirgpu_create_ex": (C.c_int, [C.POINTER(Params), C.c_uint32, C.POINTER(C.c_void_p)]),
     "pirgpu_destroy": (None, [C.c_void_p]),
     "pirgpu_last_error": (C.c_char_p, [C.c_void_p]),
     "pirgpu_create_error": (C.c_char_p, []),
@@ -79,6 +81,8 @@ SIGNATURES = {
     "pirgpu_db_load_coeffs": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, u64p]),
     "pirgpu_db_size": (C.c_uint64, [C.c_void_p]),
     "pirgpu_db_read_plaintext": (C.c_int, [C.c_void_p, C.c_uint64, u64p]),
+    "pirgpu_db_memory": (C.c_int, [C.c_void_p, u64p]),
+    "pirgpu_db_read_operand": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, u8p]),
     "pirgpu_db_finalize": (C.c_int, [C.c_void_p, C.c_int]),
     "pirgpu_db_update_items": (C.c_int, [C.c_void_p, C.c_uint64, u64p, u8p, C.c_uint32]),
     "pirgpu_db_update_plaintexts": (C.c_int, [C.c_void_p, C.c_uint64, u64p, u64p]),

@@ -315,6 +315,13 @@ struct pirgpu_ctx {
   uint8_t* d_dbp = nullptr;
   bool packed_valid = false;
   bool staging_released = false;            // pirgpu_db_finalize(release): only the operand-layout copy is left
+  // streamed database (pirgpu_create_ex, PIRGPU_CREATE_STREAMED_DB): d_db is never allocated,
+  // loads encode chunks of whole row bands into a scratch and pack them straight into d_dbp (pack_range)
+  bool streamed = false;
+  uint64_t stream_bands = 1;                // row bands (16 rows of the scanned matrix) per load chunk (option DB_STREAM_MB)
+  // the library's own count of the database's device bytes (pirgpu_db_memory): the two copies, the load / update scratch
+  // held right now, and the largest sum of the three so far
+  uint64_t db_bytes = 0, dbp_alloc = 0, mem_scratch = 0, mem_peak = 0;
   std::vector<BatchLane> lanes;             // created on the first batch
   uint64_t groups_run = 0;
   hipStream_t head_stream = nullptr;        // the narrow first levels of every group's expansion (HeadSlot)
@@ -371,6 +378,22 @@ static inline uint64_t matrix_pts(const pirgpu_ctx* c) {
 static inline uint64_t db_row(const pirgpu_ctx* c, uint64_t index) {
   return c->planes > 1 ? index / c->P * c->plane_pad + index % c->P : index - c->pt_begin;
 }
+// pirgpu_db_memory's peak: called wherever one of the counted sizes grows
+static inline void note_mem(pirgpu_ctx* c) {
+  c->mem_peak = std::max(c->mem_peak, c->db_bytes + c->dbp_alloc + c->mem_scratch);
+}
+// device scratch of a load or an update, counted while it is held
+struct ScratchNote {
+  pirgpu_ctx* c;
+  uint64_t bytes;
+  ScratchNote(pirgpu_ctx* ctx, uint64_t n) : c(ctx), bytes(n) {
+    c->mem_scratch += bytes;
+    note_mem(c);
+  }
+  ~ScratchNote() { c->mem_scratch -= bytes; }
+  ScratchNote(const ScratchNote&) = delete;
+  ScratchNote& operator=(const ScratchNote&) = delete;
+};
 
 namespace {
 
@@ -511,6 +534,10 @@ void build_tables(pirgpu_ctx* c) {
 }
 
 uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
+
+// Streamed database: bytes of one encoded row band -- the 16 rows of the scanned matrix that make up one row tile of the
+// operand layout -- as u64 residues (valid once ensure_workspace has fixed the geometry)
+uint64_t stream_band_bytes(const pirgpu_ctx* c) { return 16ull * c->scan_cols * c->k * c->N * 8; }
 
 // Option `name` (upper case, without the PIRGPU_ prefix): pirgpu_set_option's value, else the environment variable
 // PIRGPU_<name>, else dflt.  *present reports whether either was given.
@@ -718,12 +745,30 @@ void ensure_workspace(pirgpu_ctx* c) {
     const uint64_t rem = c->dim_sum % N;
     c->sel_f64 = c->want_sel_f64 && c->mfma_on && c->mode != kNttInt && c->fuse_last_level && c->last_level_ntt &&
                  !c->split_upper && c->dim_sum >= 2 && rem != 1;
+    //   DB_STREAM_MB  streamed database: megabytes of encoded plaintexts per load chunk, rounded down to whole row bands
+    //   (at least one)
+    if (c->streamed && c->mfma_on) {
+      const uint64_t mb = (uint64_t)std::max<int64_t>(0, option(c, "DB_STREAM_MB", 256));
+      c->stream_bands = std::min<uint64_t>(std::max<uint64_t>(1, (mb << 20) / stream_band_bytes(c)), 65535);
+      c->mfma_single = true;   // the 64-bit kernels read the staging copy, which a streamed context never has
+    }
   }
   c->ws_ready = true;
   if (c->workers.empty()) c->workers.emplace_back();
   c->workers[0].stream = c->stream;
   for (Worker& w : c->workers) alloc_worker(c, w);
   ensure_expansion_buffers(c, c->workers[0]);  // worker 0 serves the single-query entry points and test hooks
+  if (c->streamed && c->mfma_on) {
+    // the only copy of a streamed database, allocated once the geometry is fixed.  Zero digits are the zero plaintext:
+    // every padding row and column holds the bytes db_pack_band_kernel would store there, whichever ranges are loaded
+    const size_t bytes = (size_t)c->nslots * c->mg.RT * c->mg.KG * c->mg.tile_bytes;
+    c->d_dbp = c->dalloc<uint8_t>(bytes);
+    c->dbp_alloc = bytes;
+    note_mem(c);
+    HIP_TRY(hipMemsetAsync(c->d_dbp, 0, bytes, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->packed_valid = true;
+  }
 }
 
 // Expansion tree (ping/pong) and key-switch scratch of one worker, on first use.
@@ -1062,11 +1107,72 @@ void refuse_slot_shard(const pirgpu_ctx* c) {
 // Brings the operand-layout copy of the database up to date (after loads); one-time cost per load.
 void ensure_packed(pirgpu_ctx* c) {
   if (!c->mfma_on || c->packed_valid) return;
-  if (!c->d_dbp) c->d_dbp = c->dalloc<uint8_t>(dbp_bytes(c));
+  if (c->streamed)   // (its operand layout is valid from ensure_workspace on; there is no staging copy to pack from)
+    throw Fail{PIRGPU_INTERNAL, "streamed database without its operand-layout copy"};
+  if (!c->d_dbp) {
+    c->d_dbp = c->dalloc<uint8_t>(dbp_bytes(c));
+    c->dbp_alloc = dbp_bytes(c);
+    note_mem(c);
+  }
   HIP_TRY(launch_db_pack(c->stream, c->dp, c->mg, c->d_db, c->d_dbp, c->scan_rows, c->scan_cols, c->k * c->N, c->slot0,
                          c->nslots));
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->packed_valid = true;
+}
+
+// Streamed database: the first load fixes the geometry like a first query does; without the int8 scan there is no
+// operand layout to load into.  Waits for every queued use of the database (a reload overwrites it).
+void begin_streamed_load(pirgpu_ctx* c) {
+  ensure_workspace(c);
+  if (!c->mfma_on)
+    throw Fail{PIRGPU_FAILED_PRECONDITION,
+               "a streamed database needs the int8-MFMA scan (d >= 2, at least 8 rows, moduli below 2^55, option "
+               "SCAN_MFMA not 0): this context scans with the 64-bit kernels, which read the staging copy"};
+  if (!c->d_dbp) throw Fail{PIRGPU_INTERNAL, "streamed database without its operand-layout copy"};
+  sync_batch_streams(c);
+  HIP_TRY(hipStreamSynchronize(c->stream));
+}
+
+// Plaintexts per load chunk of a streamed context: whole row bands, no more than `pts` plaintexts need
+uint64_t stream_chunk_pts(const pirgpu_ctx* c, uint64_t bands, uint64_t pts) {
+  const uint64_t tile = 16ull * c->scan_cols;
+  return std::min<uint64_t>(std::max<uint64_t>(bands, 1), std::max<uint64_t>(ceil_div(pts, tile), 1)) * tile;
+}
+// DbUnits of the ragged head and tail of one pack_range call: each lies inside one row tile
+uint64_t stream_unit_bytes(const pirgpu_ctx* c) { return 2ull * 16 * c->mg.KG * sizeof(DbUnit); }
+
+// Streamed load: stores n consecutive plaintexts of the scanned matrix' row-major order, already encoded in the compact
+// buffer d_enc[n][k][N], first one at position l0 (db_row), into the operand layout.  The part of the range that covers
+// whole row tiles -- 16 * scan_cols aligned plaintexts, or the last, short tile when the range ends where the matrix
+// ends (what follows is padding) -- goes through the band kernel: full-tile stores, d_dbp is not read.  The ragged head
+// and tail share their tiles with plaintexts outside the range: they go through the read-modify-write column update
+// (launch_db_pack_update) with units built here.  d_units: stream_unit_bytes(c) of device scratch.
+void pack_range(pirgpu_ctx* c, const uint64_t* d_enc, uint64_t l0, uint64_t n, DbUnit* d_units) {
+  if (!n) return;
+  const uint32_t kN = c->k * c->N, cols = c->scan_cols;
+  const uint64_t tile = 16ull * cols, end = l0 + n;
+  if (end > c->scan_npt) throw Fail{PIRGPU_INTERNAL, "pack_range: range past the scanned matrix"};
+  const uint64_t head_end = std::min(ceil_div(l0, tile) * tile, end);
+  const uint64_t body_end = end == c->scan_npt ? end : std::max(head_end, end / tile * tile);
+  std::vector<DbUnit> units[2];
+  auto ragged = [&](int which, uint64_t x0, uint64_t x1) {
+    std::vector<DbUnit>& u = units[which];
+    for (uint64_t l = x0; l < x1; ++l) {
+      const uint32_t r = (uint32_t)(l / cols), col = (uint32_t)(l % cols), kg = col / 16;
+      if (u.empty() || u.back().r != r || u.back().kg != kg) u.push_back(DbUnit{r, kg, 0u, (uint32_t)(l - l0)});
+      u.back().mask |= 1u << (col % 16);
+    }
+    DbUnit* d = d_units + (size_t)which * 16 * c->mg.KG;
+    HIP_TRY(hipMemcpyAsync(d, u.data(), u.size() * sizeof(DbUnit), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(launch_db_pack_update(c->stream, c->dp, c->mg, d_enc, d, (uint32_t)u.size(), c->d_dbp, kN, c->slot0, c->nslots));
+  };
+  if (head_end > l0) ragged(0, l0, head_end);
+  if (body_end > head_end)
+    HIP_TRY(launch_db_pack_band(c->stream, c->dp, c->mg, d_enc + (head_end - l0) * kN, c->d_dbp, (uint32_t)(head_end / tile),
+                                (uint32_t)ceil_div(body_end - head_end, tile), body_end - head_end, cols, kN, c->slot0,
+                                c->nslots));
+  if (end > body_end) ragged(1, body_end, end);
+  HIP_TRY(hipStreamSynchronize(c->stream));   // the unit lists above are read by the copies queued here
 }
 
 // One pass of the MFMA scan for up to 8 queries (the caller has ordered stream `st` after their expansions): pack
@@ -1282,7 +1388,9 @@ extern "C" {
 // ======================================================================================================================
 const char* pirgpu_create_error(void) { return g_create_error.c_str(); }
 
-int pirgpu_create(const pirgpu_params* p, pirgpu_ctx** out) {
+int pirgpu_create(const pirgpu_params* p, pirgpu_ctx** out) { return pirgpu_create_ex(p, 0, out); }
+
+int pirgpu_create_ex(const pirgpu_params* p, uint32_t flags, pirgpu_ctx** out) {
   if (!p || !out) return PIRGPU_INVALID_ARGUMENT;
   *out = nullptr;
   pirgpu_ctx* c = new pirgpu_ctx();
@@ -1293,6 +1401,9 @@ int pirgpu_create(const pirgpu_params* p, pirgpu_ctx** out) {
     return code;
   };
   try {
+    if (flags & ~PIRGPU_CREATE_STREAMED_DB)
+      return bail(PIRGPU_INVALID_ARGUMENT, "unknown pirgpu_create_ex flags " + std::to_string(flags));
+    c->streamed = (flags & PIRGPU_CREATE_STREAMED_DB) != 0;
     c->prm = *p;
     const uint32_t N = p->poly_modulus_degree, k = p->num_data_primes;
     if (N < 2048 || N > 32768 || (N & (N - 1)))
@@ -1314,6 +1425,8 @@ int pirgpu_create(const pirgpu_params* p, pirgpu_ctx** out) {
       return bail(PIRGPU_INVALID_ARGUMENT, "invalid plain modulus");
     if (p->num_dimensions < 1 || p->num_dimensions > PIRGPU_MAX_DIMS)
       return bail(PIRGPU_INVALID_ARGUMENT, "invalid number of dimensions");
+    if (c->streamed && p->num_dimensions == 1)
+      return bail(PIRGPU_INVALID_ARGUMENT, "a streamed database needs d >= 2: the d = 1 scans read the u64 staging copy");
     c->N = N;
     c->k = k;
     while ((1u << c->logN) < N) ++c->logN;
@@ -1383,11 +1496,15 @@ int pirgpu_create(const pirgpu_params* p, pirgpu_ctx** out) {
     // rows are padded with zero plaintexts to full length so the scan kernels are branch-free
     const uint64_t cols_last = c->dims[c->d - 1];
     const uint64_t padded = c->planes > 1 ? matrix_pts(c) : c->d == 1 ? shard_pts : ceil_div(shard_pts, cols_last) * cols_last;
-    c->d_db = c->dalloc<uint64_t>(padded * k * N);
-    if (c->planes > 1)   // every plane is padded to the whole box of its dimensions
-      HIP_TRY(hipMemset(c->d_db, 0, padded * k * N * 8));
-    else if (padded > shard_pts)
-      HIP_TRY(hipMemset(c->d_db + shard_pts * k * N, 0, (padded - shard_pts) * k * N * 8));
+    if (!c->streamed) {
+      c->d_db = c->dalloc<uint64_t>(padded * k * N);
+      c->db_bytes = std::max<uint64_t>(padded * k * N, 1) * 8;
+      note_mem(c);
+      if (c->planes > 1)   // every plane is padded to the whole box of its dimensions
+        HIP_TRY(hipMemset(c->d_db, 0, padded * k * N * 8));
+      else if (padded > shard_pts)
+        HIP_TRY(hipMemset(c->d_db + shard_pts * k * N, 0, (padded - shard_pts) * k * N * 8));
+    }
     c->loaded.assign(held_pts(c), 0);   // per ABI plaintext index - pt_begin (plane-major)
   } catch (const Fail& e) {
     return bail(e.code, e.msg);
@@ -1490,7 +1607,7 @@ static const struct { const char* name; bool early; } kOptions[] = {
     {"SPLIT_UPPER", true}, {"SPLIT_UPPER_MB", true}, {"PACK40", true}, {"PACK_BYTES", true}, {"TREE40_WIDE", true},
     {"SCAN_MFMA", true}, {"SCAN_MFMA_WIDE", true}, {"SCAN_MFMA_TOP4", true}, {"SCAN_MFMA_NQ", true}, {"SCAN_MFMA_SINGLE", true},
     {"HEAD_LEVELS", true}, {"HEAD_MODE", true}, {"SCAN_F64_FOLD", true}, {"SCAN_F64_FOLD_BATCH", true}, {"LOOP_TRANSFORMS", true},
-    {"SLOTS_SCAN_WGS", false}, {"SLOTS_GATHER_NTT", false}, {"SLOTS_SCAN_BLK_MAJOR", false},
+    {"SLOTS_SCAN_WGS", false}, {"SLOTS_GATHER_NTT", false}, {"SLOTS_SCAN_BLK_MAJOR", false}, {"DB_STREAM_MB", true},
 };
 
 int pirgpu_set_option(pirgpu_ctx* c, const char* name, int64_t value) {
@@ -1613,15 +1730,25 @@ int pirgpu_db_load_items(pirgpu_ctx* c, const uint8_t* items, uint64_t num_items
     const uint64_t bytes_per_pt = ipp * bytes_per_item;
     if (c->staging_released)
       return fail(c, PIRGPU_FAILED_PRECONDITION, "database staging was released by pirgpu_db_finalize; it cannot be reloaded");
-    c->packed_valid = false;
+    // streamed context: a chunk is a whole number of row bands, encoded into a compact scratch and packed from there
+    // (pack_range); the raw-byte upload buffer is sized to the same chunk
+    const uint64_t kN = (uint64_t)c->k * c->N;
+    if (!c->streamed) c->packed_valid = false;
     if (c->planes > 1) {
       // wide items: item i is uploaded once and the encode kernel cuts it into its planes -- plane j reads bytes
       // [j B, min((j + 1) B, bytes_per_item)) of it and writes plaintext row j * plane_pad + i
       if (num_items > c->P) return fail(c, PIRGPU_INVALID_ARGUMENT, "more items than plaintexts");
+      if (c->streamed) begin_streamed_load(c);
       const uint64_t B = (uint64_t)c->N * c->bits / 8;
-      const uint64_t chunk_items = std::max<uint64_t>(1, (64ull << 20) / bytes_per_item);
-      DevScratch s_bytes;
+      // (streamed: one item chunk becomes `planes` compact pieces [planes][n][k][N], so the bands are shared out)
+      const uint64_t chunk_items = c->streamed ? stream_chunk_pts(c, c->stream_bands / c->planes, c->P)
+                                               : std::max<uint64_t>(1, (64ull << 20) / bytes_per_item);
+      DevScratch s_bytes, s_enc, s_units;
+      const uint64_t enc_bytes = c->streamed ? c->planes * chunk_items * kN * 8 : 0;
+      ScratchNote held(c, chunk_items * bytes_per_item + enc_bytes + (c->streamed ? stream_unit_bytes(c) : 0));
       uint8_t* d_bytes = s_bytes.get<uint8_t>(chunk_items * bytes_per_item);
+      uint64_t* d_enc = c->streamed ? s_enc.get<uint64_t>(enc_bytes) : nullptr;
+      DbUnit* d_units = c->streamed ? s_units.get<DbUnit>(stream_unit_bytes(c)) : nullptr;
       for (uint64_t it = 0; it < c->P; it += chunk_items) {
         const uint64_t n = std::min<uint64_t>(chunk_items, c->P - it);
         const uint64_t have = it < num_items ? std::min<uint64_t>(n, num_items - it) : 0;   // plaintexts past the items: zero
@@ -1633,6 +1760,13 @@ int pirgpu_db_load_items(pirgpu_ctx* c, const uint8_t* items, uint64_t num_items
             note_plaintext(c, pl * c->P + it + i,
                            it + i >= num_items || all_zero_bytes(items + (it + i) * bytes_per_item + off, len));
         }
+        if (c->streamed) {
+          HIP_TRY(c->ops->db_encode(c->stream, c->mode, c->dp, c->k, nullptr, d_bytes, bytes_per_item, have * bytes_per_item,
+                                    c->bits, n, d_enc, c->planes, B, n));
+          for (uint32_t pl = 0; pl < c->planes; ++pl)   // plane pl's rows start at pl * plane_pad: no tile boundary
+            pack_range(c, d_enc + pl * n * kN, pl * c->plane_pad + it, n, d_units);
+          continue;
+        }
         HIP_TRY(c->ops->db_encode(c->stream, c->mode, c->dp, c->k, nullptr, d_bytes, bytes_per_item, have * bytes_per_item,
                                   c->bits, n, c->d_db + it * c->k * c->N, c->planes, B, c->plane_pad));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1643,8 +1777,14 @@ int pirgpu_db_load_items(pirgpu_ctx* c, const uint8_t* items, uint64_t num_items
     if ((uint64_t)std::ceil((double)(bytes_per_pt * 8) / c->bits) > c->N)
       return fail(c, PIRGPU_INVALID_ARGUMENT, "Number of coefficients needed greater than poly modulus degree");
     if (ceil_div(num_items, ipp) > c->P) return fail(c, PIRGPU_INVALID_ARGUMENT, "more items than plaintexts");
+    if (c->streamed) begin_streamed_load(c);
     const uint64_t total_bytes = num_items * bytes_per_item;
-    const uint64_t chunk_pts = std::max<uint64_t>(1, (64ull << 20) / std::max<uint64_t>(bytes_per_pt, 1));
+    const uint64_t chunk_pts = c->streamed ? stream_chunk_pts(c, c->stream_bands, c->pt_end - c->pt_begin)
+                                           : std::max<uint64_t>(1, (64ull << 20) / std::max<uint64_t>(bytes_per_pt, 1));
+    DevScratch s_enc, s_units;
+    ScratchNote held(c, chunk_pts * bytes_per_pt + (c->streamed ? chunk_pts * kN * 8 + stream_unit_bytes(c) : 0));
+    uint64_t* d_enc = c->streamed ? s_enc.get<uint64_t>(chunk_pts * kN * 8) : nullptr;
+    DbUnit* d_units = c->streamed ? s_units.get<DbUnit>(stream_unit_bytes(c)) : nullptr;
     uint8_t* d_bytes = nullptr;
     HIP_TRY(hipMalloc((void**)&d_bytes, chunk_pts * bytes_per_pt));
     try {
@@ -1659,7 +1799,8 @@ int pirgpu_db_load_items(pirgpu_ctx* c, const uint8_t* items, uint64_t num_items
           note_plaintext(c, pt - c->pt_begin + i, all_zero_bytes(items + p0, p1 - p0));
         }
         HIP_TRY(c->ops->db_encode(c->stream, c->mode, c->dp, c->k, nullptr, d_bytes, bytes_per_pt, b1 - b0, c->bits,
-                                  n, c->d_db + (pt - c->pt_begin) * c->k * c->N, 1, 0, 0));
+                                  n, c->streamed ? d_enc : c->d_db + (pt - c->pt_begin) * c->k * c->N, 1, 0, 0));
+        if (c->streamed) pack_range(c, d_enc, pt - c->pt_begin, n, d_units);
         HIP_TRY(hipStreamSynchronize(c->stream));
       }
     } catch (...) {
@@ -1681,14 +1822,24 @@ int pirgpu_db_load_coeffs(pirgpu_ctx* c, uint64_t first_pt, uint64_t n_pt, const
     if (lo >= hi) return PIRGPU_OK;
     if (c->staging_released)
       return fail(c, PIRGPU_FAILED_PRECONDITION, "database staging was released by pirgpu_db_finalize; it cannot be reloaded");
-    c->packed_valid = false;
-    const uint64_t chunk = std::max<uint64_t>(1, (64ull << 20) / (c->N * 8));
+    if (c->streamed) begin_streamed_load(c);
+    else c->packed_valid = false;
+    // (streamed: chunks of whole row bands through a compact scratch and pack_range, as in pirgpu_db_load_items)
+    const uint64_t kN = (uint64_t)c->k * c->N;
+    const uint64_t chunk = c->streamed ? stream_chunk_pts(c, c->stream_bands, hi - lo)
+                                       : std::max<uint64_t>(1, (64ull << 20) / (c->N * 8));
+    DevScratch s_enc, s_units;
+    ScratchNote held(c, chunk * c->N * 8 + (c->streamed ? chunk * kN * 8 + stream_unit_bytes(c) : 0));
+    uint64_t* d_enc = c->streamed ? s_enc.get<uint64_t>(chunk * kN * 8) : nullptr;
+    DbUnit* d_units = c->streamed ? s_units.get<DbUnit>(stream_unit_bytes(c)) : nullptr;
     uint64_t* d_coeffs = nullptr;
     HIP_TRY(hipMalloc((void**)&d_coeffs, chunk * c->N * 8));
     try {
       for (uint64_t pt = lo; pt < hi;) {
         // a piece never crosses a plane boundary: the rows of one plane are contiguous in d_db
-        const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(chunk, hi - pt), c->planes > 1 ? c->P - pt % c->P : chunk);
+        uint64_t n = std::min<uint64_t>(std::min<uint64_t>(chunk, hi - pt), c->planes > 1 ? c->P - pt % c->P : chunk);
+        // (streamed: the first piece ends on a chunk boundary of the matrix, so that the later ones are whole row tiles)
+        if (c->streamed) n = std::min<uint64_t>(n, chunk - db_row(c, pt) % chunk);
         HIP_TRY(hipMemcpyAsync(d_coeffs, coeffs + (pt - first_pt) * c->N, n * c->N * 8, hipMemcpyHostToDevice,
                                c->stream));
         for (uint64_t i = 0; i < n; ++i)
@@ -1696,7 +1847,8 @@ int pirgpu_db_load_coeffs(pirgpu_ctx* c, uint64_t first_pt, uint64_t n_pt, const
                          all_zero_bytes(reinterpret_cast<const uint8_t*>(coeffs + (pt - first_pt + i) * c->N),
                                         (size_t)c->N * 8));
         HIP_TRY(c->ops->db_encode(c->stream, c->mode, c->dp, c->k, d_coeffs, nullptr, 0, 0, c->bits, n,
-                                  c->d_db + db_row(c, pt) * c->k * c->N, 1, 0, 0));
+                                  c->streamed ? d_enc : c->d_db + db_row(c, pt) * c->k * c->N, 1, 0, 0));
+        if (c->streamed) pack_range(c, d_enc, db_row(c, pt), n, d_units);
         HIP_TRY(hipStreamSynchronize(c->stream));
         pt += n;
       }
@@ -1721,6 +1873,7 @@ int pirgpu_db_finalize(pirgpu_ctx* c, int release_staging) {
       if (it != c->allocs.end()) c->allocs.erase(it);
       HIP_TRY(hipFree(c->d_db));
       c->d_db = nullptr;
+      c->db_bytes = 0;
       c->staging_released = true;
       c->mfma_single = true;  // the 64-bit kernels read the staging copy
     }
@@ -1738,6 +1891,8 @@ int pirgpu_db_read_plaintext(pirgpu_ctx* c, uint64_t pt_index, uint64_t* out) {
       const uint64_t* src = c->d_db ? c->d_db + db_row(c, pt_index) * c->k * c->N : nullptr;
       if (!src) {  // staging released: gather the digits of this plaintext from the operand layout
         refuse_slot_shard(c);   // ... which a slot shard holds only 1 / G of
+        if (!c->d_dbp)          // (a streamed context before its first load)
+          throw Fail{PIRGPU_FAILED_PRECONDITION, "database not loaded: the operand-layout copy does not exist yet"};
         const uint64_t local = db_row(c, pt_index);
         uint64_t* tmp = stage + (size_t)c->k * c->N;
         HIP_TRY(launch_db_unpack(c->stream, c->dp, c->mg, c->d_dbp, tmp, (uint32_t)(local / c->scan_cols),
@@ -1752,6 +1907,32 @@ int pirgpu_db_read_plaintext(pirgpu_ctx* c, uint64_t pt_index, uint64_t* out) {
       throw;
     }
     HIP_TRY(hipFree(stage));
+    return PIRGPU_OK;
+  });
+}
+
+int pirgpu_db_memory(const pirgpu_ctx* cc, uint64_t out[4]) {
+  pirgpu_ctx* c = const_cast<pirgpu_ctx*>(cc);
+  return guarded(c, [&]() -> int {
+    if (!out) return fail(c, PIRGPU_INVALID_ARGUMENT, "null argument");
+    ensure_workspace(c);   // a streamed context's operand copy and band size exist once the geometry is fixed
+    out[0] = c->dbp_alloc;
+    out[1] = c->db_bytes;
+    out[2] = c->mem_peak;
+    out[3] = c->streamed && c->mfma_on ? stream_band_bytes(c) : 0;
+    return PIRGPU_OK;
+  });
+}
+
+int pirgpu_db_read_operand(pirgpu_ctx* c, uint64_t offset, uint64_t n, uint8_t* out) {
+  return guarded(c, [&]() -> int {
+    if (!c->d_dbp) return fail(c, PIRGPU_FAILED_PRECONDITION, "the operand-layout copy does not exist yet");
+    if (offset > c->dbp_alloc || n > c->dbp_alloc - offset || (!out && n))
+      return fail(c, PIRGPU_INVALID_ARGUMENT, "byte range outside the operand-layout copy");
+    if (!n) return PIRGPU_OK;
+    sync_batch_streams(c);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(out, c->d_dbp + offset, n, hipMemcpyDeviceToHost));
     return PIRGPU_OK;
   });
 }
@@ -1795,6 +1976,8 @@ void apply_update(pirgpu_ctx* c, const std::vector<PtUpdate>& pts, const uint8_t
   const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>((64ull << 20) / per_pt, 65535));
   const uint64_t cap = std::min<uint64_t>(chunk, pts.size());
   DevScratch s_coef, s_enc, s_loc, s_units, s_img, s_upd, s_nz;
+  ScratchNote held(c, cap * ((uint64_t)N * 8 + (uint64_t)kN * 8 + 8 + sizeof(DbUnit) +
+                             (splice || wide ? bpp : 0) + (splice ? ipp + 4 : 0)));
   uint64_t* d_coef = s_coef.get<uint64_t>(cap * N * 8);
   uint64_t* d_enc = s_enc.get<uint64_t>(cap * kN * 8);
   uint64_t* d_loc = s_loc.get<uint64_t>(cap * 8);

@@ -192,6 +192,12 @@ MfmaGeom mfma_geometry(const DevParams& hp, uint32_t rows, uint32_t cols, int wi
 // slot0 / nslots: the slots of the ring the packed copy holds (nslots = 0: all from slot0 on), local index j - slot0
 hipError_t launch_db_pack(hipStream_t st, const DevParams* P, const MfmaGeom& gm, const uint64_t* db, uint8_t* dbp,
                           uint32_t rows, uint32_t cols, uint32_t kN, uint32_t slot0 = 0, uint32_t nslots = 0);
+// The same for a band of whole row tiles (streamed database loads): band = u64 [npts][kN], plaintexts in row-major order
+// starting at matrix row 16 * rt0 and column 0, goes to the row tiles [rt0, rt0 + n_rt) of the packed copy; what the
+// band does not hold of those tiles (npts < n_rt * 16 * cols) is stored as zero.  Full-tile stores, dbp is not read.
+hipError_t launch_db_pack_band(hipStream_t st, const DevParams* P, const MfmaGeom& gm, const uint64_t* band, uint8_t* dbp,
+                               uint32_t rt0, uint32_t n_rt, uint64_t npts, uint32_t cols, uint32_t kN, uint32_t slot0 = 0,
+                               uint32_t nslots = 0);
 hipError_t launch_db_unpack(hipStream_t st, const DevParams* P, const MfmaGeom& gm, const uint8_t* dbp, uint64_t* out,
                             uint32_t row, uint32_t col, uint32_t kN);
 // In-place database updates (pirgpu_db_update_*).  One unit = one touched (row, column group) of the operand layout:

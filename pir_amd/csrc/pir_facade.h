@@ -87,8 +87,10 @@ class PIRDatabase {
   ~PIRDatabase() { pirgpu_destroy(ctx_); }
   PIRDatabase(const PIRDatabase&) = delete;
 
-  // database.cpp:40-44
-  static StatusOr<std::shared_ptr<PIRDatabase>> Create(std::shared_ptr<PIRParameters> params, int device = 0) {
+  // database.cpp:40-44.  streamed (not in the reference): loads go in row bands straight into the scan's operand layout,
+  // the u64 staging copy is never allocated (pirgpu_create_ex, PIRGPU_CREATE_STREAMED_DB)
+  static StatusOr<std::shared_ptr<PIRDatabase>> Create(std::shared_ptr<PIRParameters> params, int device = 0,
+                                                       bool streamed = false) {
     if (params->coeff_modulus.size() < 2 || params->coeff_modulus.size() > PIRGPU_MAX_PRIMES + 1 ||
         params->dimensions.empty() || params->dimensions.size() > PIRGPU_MAX_DIMS)
       return InvalidArgumentError("invalid parameters");
@@ -109,15 +111,16 @@ class PIRDatabase {
     p.plaintexts_per_item = params->plaintexts_per_item;
     p.device = device;
     pirgpu_ctx* ctx = nullptr;
-    int rc = pirgpu_create(&p, &ctx);
+    int rc = pirgpu_create_ex(&p, streamed ? PIRGPU_CREATE_STREAMED_DB : 0u, &ctx);
     if (rc) return detail::FromRc(nullptr, rc);
     return std::shared_ptr<PIRDatabase>(new PIRDatabase(ctx, std::move(params)));
   }
 
   // database.cpp:52-58
   static StatusOr<std::shared_ptr<PIRDatabase>> Create(const std::vector<std::string>& rawdb,
-                                                       std::shared_ptr<PIRParameters> params, int device = 0) {
-    auto db = Create(std::move(params), device);
+                                                       std::shared_ptr<PIRParameters> params, int device = 0,
+                                                       bool streamed = false) {
+    auto db = Create(std::move(params), device, streamed);
     if (!db.ok()) return db.status();
     Status s = (*db)->populate(rawdb);
     if (!s.ok()) return s;

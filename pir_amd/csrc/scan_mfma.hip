@@ -107,39 +107,50 @@ __device__ __forceinline__ void to_digits(uint64_t x, uint64_t q, int8_t (&d)[L]
   }
 }
 
-// database u64 [rows][cols][kN] (zero-padded rows) -> packed.  block = 16 rows x 16 slots; grid = (slots/16, RT, KG).
+// A band of the database, u64 [rows][cols][kN] whose first row is matrix row 16 * rt0 -> the row tiles rt0 + blockIdx.y
+// of the packed copy.  block = 16 rows x 16 slots; grid = (slots/16, row tiles of the band, KG): every thread stores
+// the 16 bytes of one (slot, digit, row), the 16 rows of a slot forming one 256-byte run per digit.  The band holds
+// `npts` plaintexts in row-major order (the whole matrix with rt0 = 0: launch_db_pack); plaintexts at or beyond npts --
+// the rows past the band's last one, the rest of a partial last row -- and columns at or beyond cols read as zero, so
+// every tile is stored whole and the kernel never reads dbp.
 // slot0: first slot of the packed copy (a slot-sharded context packs only its own slots, local index j - slot0)
 template <int L, bool TOP4>
 __global__ void __launch_bounds__(256)
-db_pack_kernel(const DevParams* __restrict__ P, const uint64_t* __restrict__ db, uint8_t* __restrict__ dbp,
-               uint32_t rows, uint32_t cols, uint32_t kN, uint32_t RT, uint32_t KG, uint32_t GC, uint32_t slot0) {
+db_pack_band_kernel(const DevParams* __restrict__ P, const uint64_t* __restrict__ db, uint8_t* __restrict__ dbp,
+                    uint64_t npts, uint32_t cols, uint32_t kN, uint32_t rt0, uint32_t RT, uint32_t KG, uint32_t GC,
+                    uint32_t slot0) {
   constexpr uint32_t TB = tile_bytes(L, TOP4);
   const uint32_t j = slot0 + blockIdx.x * 16 + (threadIdx.x & 15);
   const uint32_t r16 = threadIdx.x >> 4;
-  const uint32_t rt = blockIdx.y, kg = blockIdx.z;
-  const uint32_t r = rt * 16 + r16;
+  const uint32_t rt = rt0 + blockIdx.y, kg = blockIdx.z;
+  const uint32_t r = blockIdx.y * 16 + r16;   // row inside the band
   const uint64_t q = P->mod[j >> P->logN].q;
-  uint8_t o[L][16];
+  // the 16 loads of the row first (all in flight together), then the digits of column t straight into byte t of the
+  // digit's 16-byte row / nibble t of the TOP4 row (pack_top4's order): L x 4 dwords, never a register per byte
+  uint64_t x[16];
 #pragma unroll
   for (int t = 0; t < 16; ++t) {
     const uint32_t c = kg * 16 + t;
-    uint64_t x = 0;
-    if (r < rows && c < cols) x = db[((size_t)r * cols + c) * kN + j];
+    const uint64_t pt = (uint64_t)r * cols + c;
+    x[t] = 0;
+    if (c < cols && pt < npts) x[t] = db[pt * kN + j];
+  }
+  constexpr int LF = TOP4 ? L - 1 : L;
+  uint32_t w[LF][4] = {};
+  uint32_t w4[2] = {0, 0};
+#pragma unroll
+  for (int t = 0; t < 16; ++t) {
     int8_t d[L];
-    to_digits<L, TOP4>(x, q, d);
+    to_digits<L, TOP4>(x[t], q, d);
 #pragma unroll
-    for (int a = 0; a < L; ++a) o[a][t] = (uint8_t)d[a];
+    for (int a = 0; a < LF; ++a) w[a][t >> 2] |= (uint32_t)(uint8_t)d[a] << (8 * (t & 3));
+    if constexpr (TOP4) w4[t >> 3] |= ((uint32_t)d[L - 1] & 0xFu) << (8 * (t & 3) + ((t & 4) ? 4 : 0));
   }
+  uint8_t* blk = dbp + db_tile_offset(j - slot0, rt, kg, 0, TB, RT, KG, GC);
 #pragma unroll
-  for (int a = 0; a < L; ++a) {
-    if (TOP4 && a == L - 1) {
-      *reinterpret_cast<v2i*>(dbp + db_tile_offset(j - slot0, rt, kg, a, TB, RT, KG, GC) + r16 * 8) = pack_top4(o[a]);
-    } else {
-      v4i v;
-      __builtin_memcpy(&v, o[a], 16);
-      *reinterpret_cast<v4i*>(dbp + db_tile_offset(j - slot0, rt, kg, a, TB, RT, KG, GC) + r16 * 16) = v;
-    }
-  }
+  for (int a = 0; a < LF; ++a)
+    *reinterpret_cast<v4i*>(blk + (size_t)a * 256 + r16 * 16) = v4i{(int)w[a][0], (int)w[a][1], (int)w[a][2], (int)w[a][3]};
+  if constexpr (TOP4) *reinterpret_cast<v2i*>(blk + (size_t)(L - 1) * 256 + r16 * 8) = v2i{(int)w4[0], (int)w4[1]};
 }
 
 // selectors (per query u64 [cols][2][kN], NTT form) -> packed.  block = 16 x * 16 slots; grid = (kN/16, KG).
@@ -265,7 +276,7 @@ db_gather_kernel(const DevParams* __restrict__ P, const uint8_t* __restrict__ db
   }
 }
 
-// The partial twin of db_pack_kernel: one thread per (unit, local slot) reads the unit's digit rows, replaces the
+// The partial twin of db_pack_band_kernel: one thread per (unit, local slot) reads the unit's digit rows, replaces the
 // touched columns with the digits of enc[out0 + rank][j] and writes the rows back.  A unit is one (row, column group) and
 // a thread one slot, so no byte -- a TOP4 byte holds columns i and i + 4 -- is written by two threads.
 // grid = (nslots / 256, units); slots [slot0, slot0 + nslots) at local index j - slot0.
@@ -611,11 +622,22 @@ MfmaGeom mfma_geometry(const DevParams& hp, uint32_t rows, uint32_t cols, int wi
 
 hipError_t launch_db_pack(hipStream_t st, const DevParams* P, const MfmaGeom& gm, const uint64_t* db, uint8_t* dbp,
                           uint32_t rows, uint32_t cols, uint32_t kN, uint32_t slot0, uint32_t nslots) {
+  return launch_db_pack_band(st, P, gm, db, dbp, 0, gm.RT, (uint64_t)rows * cols, cols, kN, slot0, nslots);
+}
+
+hipError_t launch_db_pack_band(hipStream_t st, const DevParams* P, const MfmaGeom& gm, const uint64_t* band, uint8_t* dbp,
+                               uint32_t rt0, uint32_t n_rt, uint64_t npts, uint32_t cols, uint32_t kN, uint32_t slot0,
+                               uint32_t nslots) {
   if (nslots == 0) nslots = kN - slot0;
   if (slot0 % 16 || nslots % 16 || slot0 + nslots > kN) return hipErrorInvalidValue;
-  const dim3 grid(nslots / 16, gm.RT, gm.KG);
-#define PIRGPU_DBPACK(L_, T_) \
-  hipLaunchKernelGGL((db_pack_kernel<L_, T_>), grid, dim3(256), 0, st, P, db, dbp, rows, cols, kN, gm.RT, gm.KG, gm.GC, slot0)
+  // the band stays inside the packed copy and holds no more than its row tiles
+  if (!n_rt || n_rt > 65535 || rt0 > gm.RT || n_rt > gm.RT - rt0 || (cols + 15) / 16 != gm.KG ||
+      npts > (uint64_t)n_rt * 16 * cols)
+    return hipErrorInvalidValue;
+  const dim3 grid(nslots / 16, n_rt, gm.KG);
+#define PIRGPU_DBPACK(L_, T_)                                                                                      \
+  hipLaunchKernelGGL((db_pack_band_kernel<L_, T_>), grid, dim3(256), 0, st, P, band, dbp, npts, cols, kN, rt0, gm.RT, \
+                     gm.KG, gm.GC, slot0)
   switch (gm.L) {
     case 5:
       if (gm.top4) PIRGPU_DBPACK(5, true);

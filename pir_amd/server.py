@@ -60,9 +60,11 @@ class PIRDatabase:
     """reference database.h:37-133.  Owns the device context and the HBM-resident encoded database."""
 
     def __init__(self, params: PIRParameters, device: int = 0, shard: Optional[Sequence[int]] = None,
-                 slots: Optional[Sequence[int]] = None):
+                 slots: Optional[Sequence[int]] = None, streamed: bool = False):
         """shard: rows [begin, end) of dimension 0 this context holds; slots: NTT slots [begin, end) of every plaintext
-        it holds (multi-GPU partitionings; default: the whole database)."""
+        it holds (multi-GPU partitionings; default: the whole database).  streamed: loads go in
+        row bands straight into the scan's operand layout, the u64 staging copy is never allocated (pirgpu_create_ex,
+        DESIGN.md section 6.3)."""
         self.params = params
         enc = params.encryption_parameters
         self.N = enc.poly_modulus_degree
@@ -71,7 +73,7 @@ class PIRDatabase:
         p = capi.make_params(params, device=device, shard=shard, slots=slots)
         self._cparams = p
         h = C.c_void_p()
-        rc = self.lib.pirgpu_create(C.byref(p), C.byref(h))
+        rc = self.lib.pirgpu_create_ex(C.byref(p), capi.CREATE_STREAMED_DB if streamed else 0, C.byref(h))
         if rc != 0:
             raise PirGpuError(rc, self.lib.pirgpu_create_error().decode())
         self._h = h
@@ -98,9 +100,10 @@ class PIRDatabase:
 
     # -- reference interface ------------------------------------------------------
     @classmethod
-    def Create(cls, params: PIRParameters, rawdb=None, device: int = 0, shard=None, slots=None) -> "PIRDatabase":
+    def Create(cls, params: PIRParameters, rawdb=None, device: int = 0, shard=None, slots=None,
+               streamed: bool = False) -> "PIRDatabase":
         """database.cpp:40-58: Create(params) / Create(rawdb, params)."""
-        db = cls(params, device=device, shard=shard, slots=slots)
+        db = cls(params, device=device, shard=shard, slots=slots, streamed=streamed)
         if rawdb is not None:
             db.populate(rawdb)
         return db
@@ -193,6 +196,19 @@ class PIRDatabase:
         out = np.empty((self.k, self.N), dtype=np.uint64)
         self._check(self.lib.pirgpu_db_read_plaintext(self._h, index, _ptr(out)))
         return out
+
+    def memory(self) -> Dict[str, int]:
+        """Device bytes of the database as the library counts them (pirgpu_db_memory): operand-layout copy, u64 staging
+        copy, the peak of both plus load / update scratch, and a streamed context's band size."""
+        out = (C.c_uint64 * 4)()
+        self._check(self.lib.pirgpu_db_memory(self._h, out))
+        return {"operand": int(out[0]), "staging": int(out[1]), "peak": int(out[2]), "band": int(out[3])}
+
+    def read_operand(self, offset: int, n: int) -> np.ndarray:
+        """Test hook: bytes [offset, offset + n) of the operand-layout copy (pirgpu_db_read_operand)."""
+        out = np.empty(max(int(n), 1), dtype=np.uint8)
+        self._check(self.lib.pirgpu_db_read_operand(self._h, int(offset), int(n), out.ctypes.data_as(capi.u8p)))
+        return out[: int(n)]
 
     def reply_ct_count(self) -> int:
         return int(self.lib.pirgpu_reply_ct_count(self._h))
