@@ -93,6 +93,12 @@ int pirclient_encrypt(pirclient* c, const uint64_t* plaintext, size_t n_coeffs, 
 int pirclient_decrypt(pirclient* c, const uint64_t* ct, uint64_t* plaintext_out);
 /* seal::Decryptor::invariant_noise_budget in bits (0 = decryption no longer reliable). */
 int pirclient_noise_budget(pirclient* c, const uint64_t* ct, int* bits);
+/* The same for a ciphertext at level r of the modulus chain: ct [2][r][N] over q_0..q_{r-1}, 1 <= r <= k (r = k is
+ * the two functions above).  With params.result_primes = r the server's replies are such ciphertexts:
+ * pirclient_process_reply / _process_response then expect [n_cts][2][r][N], n_cts = (2 * the expansion ratio over the
+ * first r primes)^(d-1) per plane, and the response's ciphertexts carry parms_id(N, q_0..q_{r-1}, t). */
+int pirclient_decrypt_level(pirclient* c, const uint64_t* ct, uint32_t r, uint64_t* plaintext_out);
+int pirclient_noise_budget_level(pirclient* c, const uint64_t* ct, uint32_t r, int* bits);
 /* CiphertextReencoder::Encode -- ct_reencoder.cpp:40-73: ct -> [2*ExpansionRatio][N] plaintexts. */
 int pirclient_reencode(const pirclient* c, const uint64_t* ct, uint64_t* plaintexts_out, size_t cap_pts,
                        uint32_t* n_pts);

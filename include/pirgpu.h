@@ -96,6 +96,20 @@ typedef struct pirgpu_params {
    * shard).  Plaintext indices at this ABI are plane-major then: plane * num_pt + pt (pirgpu_db_load_coeffs,
    * pirgpu_db_read_plaintext, pirgpu_db_update_plaintexts; pirgpu_db_size and pirgpu_zero_plaintexts count all planes). */
   uint32_t plaintexts_per_item;
+  /* Modulus-switched results (not in the reference, which answers at the full data modulus): with 1 <= result_primes =
+   * r < k every level result of PIRDatabase::multiply -- the row sums after the scan, every upper level's output, the
+   * reply -- is switched from q_0..q_{k-1} down to q_0..q_{r-1} right after its inverse transform (database.cpp:250-254)
+   * and before CiphertextReencoder::Encode reads it: k - r drop steps, last prime first, each the exact
+   * floor((x + floor(q_m / 2)) / q_m) on the CRT representative (the project's reading of SEAL 3.5.6
+   * Evaluator::mod_switch_to_next_inplace for BFV; not verified against a SEAL build).  Encode then enumerates
+   * (poly, j < r, digit): pirgpu_expansion_ratio is the sum of the first r local ratios, the reply holds
+   * planes x (2 x that)^(d-1) ciphertexts of [2][r][N] words each (pirgpu_reply_ct_words), and on the wire a reply
+   * ciphertext is a SEAL ciphertext at that level of the chain (r residues, parms_id(N, q_0..q_{r-1}, t)).  Queries,
+   * keys, database, expansion and scan stay at k primes.  0 = off (the reference's behaviour, every byte as before);
+   * r >= k is InvalidArgument.  Switching does not commute with the sum over shards: r >= 1 with a row or slot shard is
+   * InvalidArgument, and the multi-GPU entry points (packed exchange, pirgpu_slots_*, pirgpu_reduce_fixup*, the device
+   * reply copies) return FailedPrecondition on such a context.  Capacities given in ciphertexts stay in ciphertexts. */
+  uint32_t result_primes;
 } pirgpu_params;
 
 /* PIRContext::Create + PIRDatabase::Create(params) (reference context.cpp:37-50,
@@ -239,8 +253,14 @@ int pirgpu_process_query(pirgpu_ctx* ctx, const uint64_t* query, uint32_t nq, ui
                          uint64_t reply_capacity, uint64_t* reply_count);
 /* (2 * ExpansionRatio)^(d-1) (reference client.cpp:224-226, ct_reencoder.cpp:29-38), times plaintexts_per_item */
 uint64_t pirgpu_reply_ct_count(const pirgpu_ctx* ctx);
-/* CiphertextReencoder::ExpansionRatio (reference ct_reencoder.cpp:29-38) */
+/* CiphertextReencoder::ExpansionRatio (reference ct_reencoder.cpp:29-38); over the first result_primes primes when set */
 uint32_t pirgpu_expansion_ratio(const pirgpu_ctx* ctx);
+/* Words of one REPLY ciphertext: 2 * result_primes * N, or 2 * k * N when result_primes is 0.  Every reply buffer at
+ * this ABI is [ciphertext][2][r][N], compact. */
+uint64_t pirgpu_reply_ct_words(const pirgpu_ctx* ctx);
+/* Test hook for the modulus switch: cts = n coefficient-form ciphertexts [2][k][N] of canonical residues, out =
+ * [n][2][r][N]; any 1 <= r < k on any context, whatever its result_primes (the launcher of the query path). */
+int pirgpu_mod_switch(pirgpu_ctx* ctx, const uint64_t* cts, uint64_t n, uint32_t r, uint64_t* out);
 
 /* Device-resident split of pirgpu_process_query for pipelining and measurement:
  * stage = H2D of the query, run = every kernel of the path (asynchronous on the

@@ -36,6 +36,7 @@ class Params(C.Structure):
         ("slot_begin", C.c_uint32),
         ("slot_end", C.c_uint32),
         ("plaintexts_per_item", C.c_uint32),
+        ("result_primes", C.c_uint32),
     ]
 
 
@@ -59,6 +60,7 @@ def make_params(params, device: int = 0, shard=None, slots=None) -> Params:
     p.bits_per_coeff = params.bits_per_coeff
     p.use_ciphertext_multiplication = 1 if params.use_ciphertext_multiplication else 0
     p.plaintexts_per_item = getattr(params, "plaintexts_per_item", 1)
+    p.result_primes = getattr(params, "result_primes", 0)
     p.device = device
     if shard is not None:
         b, e = int(shard[0]), int(shard[1])
@@ -131,6 +133,8 @@ SIGNATURES = {
     "pirgpu_process_query": (C.c_int, [C.c_void_p, u64p, C.c_uint32, u64p, C.c_uint64, u64p]),
     "pirgpu_reply_ct_count": (C.c_uint64, [C.c_void_p]),
     "pirgpu_expansion_ratio": (C.c_uint32, [C.c_void_p]),
+    "pirgpu_reply_ct_words": (C.c_uint64, [C.c_void_p]),
+    "pirgpu_mod_switch": (C.c_int, [C.c_void_p, u64p, C.c_uint64, C.c_uint32, u64p]),
     "pirgpu_query_stage": (C.c_int, [C.c_void_p, u64p, C.c_uint32]),
     "pirgpu_query_stage_async": (C.c_int, [C.c_void_p, u64p, C.c_uint32]),
     "pirgpu_query_run": (C.c_int, [C.c_void_p]),
@@ -228,6 +232,8 @@ CLIENT_SIGNATURES = {
     "pirclient_encrypt": (C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p]),
     "pirclient_decrypt": (C.c_int, [C.c_void_p, u64p, u64p]),
     "pirclient_noise_budget": (C.c_int, [C.c_void_p, u64p, C.POINTER(C.c_int)]),
+    "pirclient_decrypt_level": (C.c_int, [C.c_void_p, u64p, C.c_uint32, u64p]),
+    "pirclient_noise_budget_level": (C.c_int, [C.c_void_p, u64p, C.c_uint32, C.POINTER(C.c_int)]),
     "pirclient_reencode": (C.c_int, [C.c_void_p, u64p, u64p, C.c_size_t, C.POINTER(C.c_uint32)]),
     "pirclient_string_decode": (C.c_int, [C.c_void_p, u64p, C.c_size_t, C.c_size_t, u8p]),
 }

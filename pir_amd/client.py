@@ -33,6 +33,7 @@ class PIRClient:
         enc = params.encryption_parameters
         self.N = enc.poly_modulus_degree
         self.k = len(enc.coeff_modulus) - 1
+        self.reply_k = getattr(params, "result_primes", 0) or self.k   # residues of a reply ciphertext (result_primes)
         self.lib = capi.load_client()
         p = capi.make_params(params)
         h = C.c_void_p()
@@ -95,12 +96,12 @@ class PIRClient:
             self.lib.pirclient_free(out)
 
     def LoadResponse(self, response: bytes, max_replies: int = 4096) -> np.ndarray:
-        """serialization.cpp:32-42 over every Response.reply -> [n_replies, reply_ct_count, 2, k, N] uint64."""
+        """serialization.cpp:32-42 over every Response.reply -> [n_replies, reply_ct_count, 2, reply_k, N] uint64."""
         buf = (C.c_uint8 * max(1, len(response))).from_buffer_copy(response or b"\0")
         # a reply is at least one ciphertext object: bound the output by the response's size
-        per = self.reply_ct_count * 2 * self.k * self.N
+        per = self.reply_ct_count * 2 * self.reply_k * self.N
         cap = max(1, min(max_replies, len(response) // (per * 8) + 1))
-        out = np.empty((cap, self.reply_ct_count, 2, self.k, self.N), dtype=np.uint64)
+        out = np.empty((cap, self.reply_ct_count, 2, self.reply_k, self.N), dtype=np.uint64)
         n = C.c_size_t()
         self._check(self.lib.pirclient_load_response(self._h, buf, len(response), _ptr(out), cap, C.byref(n)))
         return out[:n.value]
@@ -177,6 +178,19 @@ class PIRClient:
         c = _u64(ct)
         bits = C.c_int()
         self._check(self.lib.pirclient_noise_budget(self._h, _ptr(c), C.byref(bits)))
+        return bits.value
+
+    def decrypt_level(self, ct, r: int) -> np.ndarray:
+        """Decrypts a ciphertext [2, r, N] at level r of the modulus chain (over the first r data primes)."""
+        c = _u64(ct)
+        out = np.empty(self.N, dtype=np.uint64)
+        self._check(self.lib.pirclient_decrypt_level(self._h, _ptr(c), int(r), _ptr(out)))
+        return out
+
+    def noise_budget_level(self, ct, r: int) -> int:
+        c = _u64(ct)
+        bits = C.c_int()
+        self._check(self.lib.pirclient_noise_budget_level(self._h, _ptr(c), int(r), C.byref(bits)))
         return bits.value
 
     def reencode(self, ct) -> np.ndarray:

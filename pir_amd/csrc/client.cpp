@@ -257,8 +257,26 @@ struct pirclient {
   Big Q, half_Q;
   std::vector<Big> punct;            // Q/q_j
   int q_bits;
+  // the same constants for every prefix q_0..q_{r-1} of the data primes (levels[r - 1]): a reply of a server with
+  // pirgpu_params.result_primes = r is a ciphertext at that level of the modulus chain
+  struct Level {
+    std::vector<uint64_t> inv_punct;   // (Q_r/q_j)^-1 mod q_j
+    std::vector<Big> punct;            // Q_r/q_j
+    Big Q, half_Q;                     // Q_r = q_0 ... q_{r-1}
+    int q_bits;
+  };
+  std::vector<Level> levels;
+  wire::Shape rsh;                     // shape of a reply ciphertext on the wire (sh, or its first result_primes primes)
 
   size_t ct_words() const { return (size_t)2 * k * N; }
+  uint32_t reply_primes() const { return prm.result_primes ? prm.result_primes : k; }
+  size_t reply_ct_words() const { return (size_t)2 * reply_primes() * N; }
+  // 2 * ExpansionRatio of a level result: Encode enumerates the residues the server kept
+  size_t reply_ratio() const {
+    size_t e = 0;
+    for (uint32_t j = 0; j < reply_primes(); ++j) e += local_ratio[j];
+    return 2 * e;
+  }
   size_t key_words() const { return (size_t)k * 2 * km * N; }
 
   // ---------------------------------------------------------------- setup
@@ -272,7 +290,14 @@ struct pirclient {
       throw Err{PIRGPU_INVALID_ARGUMENT, "invalid encryption parameters"};
     if (p.num_dimensions < 1 || p.num_dimensions > PIRGPU_MAX_DIMS)
       throw Err{PIRGPU_INVALID_ARGUMENT, "invalid number of dimensions"};
+    if (p.result_primes >= k)
+      throw Err{PIRGPU_INVALID_ARGUMENT, "result_primes must be below num_data_primes"};
     sh = wire::make_shape(p);
+    rsh = sh;
+    if (p.result_primes) {
+      rsh.k = p.result_primes;
+      wire::parms_id(rsh.N, rsh.q, rsh.k, rsh.t, rsh.data_id);
+    }
     mod.resize(km);
     for (uint32_t j = 0; j < km; ++j) {
       const uint64_t q = j < k ? p.coeff_modulus[j] : p.special_prime;
@@ -318,6 +343,23 @@ struct pirclient {
       p_mod[j] = sp % mod[j].q;
       p_inv[j] = hm::invmod_prime(p_mod[j], mod[j].q);
       half_mod[j] = (sp >> 1) % mod[j].q;
+    }
+    levels.assign(k, Level());
+    for (uint32_t r = 1; r <= k; ++r) {
+      Level& lv = levels[r - 1];
+      lv.Q.v[0] = 1;
+      for (uint32_t j = 0; j < r; ++j) lv.Q.mul_word(mod[j].q);
+      lv.q_bits = lv.Q.bits();
+      lv.half_Q = lv.Q;
+      lv.half_Q.shr1();
+      lv.punct.assign(r, Big());
+      lv.inv_punct.resize(r);
+      for (uint32_t j = 0; j < r; ++j) {
+        lv.punct[j].v[0] = 1;
+        for (uint32_t i = 0; i < r; ++i)
+          if (i != j) lv.punct[j].mul_word(mod[i].q);
+        lv.inv_punct[j] = hm::invmod_prime(lv.punct[j].mod_word(mod[j].q), mod[j].q);
+      }
     }
     rng.seed(seed, seed_len);
     keygen();
@@ -479,20 +521,25 @@ struct pirclient {
     }
   }
 
-  void check_ct(const uint64_t* ct) const {
+  // A ciphertext at level r is [2][r][N] over q_0..q_{r-1}; r = k is the data level.
+  void check_ct(const uint64_t* ct, uint32_t r) const {
     for (uint32_t c = 0; c < 2; ++c)
-      for (uint32_t j = 0; j < k; ++j) {
-        const uint64_t* v = ct + ((size_t)c * k + j) * N;
+      for (uint32_t j = 0; j < r; ++j) {
+        const uint64_t* v = ct + ((size_t)c * r + j) * N;
         for (uint32_t i = 0; i < N; ++i)
           if (v[i] >= mod[j].q) throw Err{PIRGPU_INVALID_ARGUMENT, "ciphertext data is invalid (coefficient out of range)"};
       }
   }
-  // [c0 + c1 s]_{q_j}, coefficient form: out [k][N]
-  void phase(const uint64_t* ct, uint64_t* out) const {
-    for (uint32_t j = 0; j < k; ++j) {
+  const Level& level(uint32_t r) const {
+    if (r < 1 || r > k) throw Err{PIRGPU_INVALID_ARGUMENT, "level must be in [1, num_data_primes]"};
+    return levels[r - 1];
+  }
+  // [c0 + c1 s]_{q_j}, coefficient form: out [r][N]
+  void phase(const uint64_t* ct, uint32_t r, uint64_t* out) const {
+    for (uint32_t j = 0; j < r; ++j) {
       const Modulus& m = mod[j];
       uint64_t* o = out + (size_t)j * N;
-      memcpy(o, ct + ((size_t)k + j) * N, (size_t)N * 8);
+      memcpy(o, ct + ((size_t)r + j) * N, (size_t)N * 8);
       m.ntt(o);
       for (uint32_t i = 0; i < N; ++i) o[i] = m.mul(o[i], s_ntt[(size_t)j * N + i]);
       m.intt(o);
@@ -500,17 +547,18 @@ struct pirclient {
       for (uint32_t i = 0; i < N; ++i) o[i] = m.add(o[i], c0[i]);
     }
   }
-  // round(t x / Q) mod t with x = CRT(x_j): since x = sum_j y_j Q/q_j - v Q (y_j = x_j (Q/q_j)^-1 mod q_j),
-  // t x / Q = sum_j t y_j / q_j (mod t); integer and 64-bit fixed-point fractional parts are summed apart.
-  void decrypt(const uint64_t* ct, uint64_t* pt) const {
-    check_ct(ct);
-    std::vector<uint64_t> ph((size_t)k * N);
-    phase(ct, ph.data());
+  // round(t x / Q_r) mod t with x = CRT(x_j): since x = sum_j y_j Q_r/q_j - v Q_r (y_j = x_j (Q_r/q_j)^-1 mod q_j),
+  // t x / Q_r = sum_j t y_j / q_j (mod t); integer and 64-bit fixed-point fractional parts are summed apart.
+  void decrypt_level(const uint64_t* ct, uint32_t r, uint64_t* pt) const {
+    const Level& lv = level(r);
+    check_ct(ct, r);
+    std::vector<uint64_t> ph((size_t)r * N);
+    phase(ct, r, ph.data());
     for (uint32_t i = 0; i < N; ++i) {
       u128 ipart = 0, frac = 0;
-      for (uint32_t j = 0; j < k; ++j) {
+      for (uint32_t j = 0; j < r; ++j) {
         const Modulus& m = mod[j];
-        const uint64_t y = m.mul(ph[(size_t)j * N + i], inv_punct[j]);
+        const uint64_t y = m.mul(ph[(size_t)j * N + i], lv.inv_punct[j]);
         const u128 ty = (u128)t * y;
         ipart += (uint64_t)(ty / m.q);
         frac += (((u128)(uint64_t)(ty % m.q)) << 64) / m.q;
@@ -520,39 +568,42 @@ struct pirclient {
       pt[i] = (uint64_t)(ipart % t);
     }
   }
-  // Decryptor::invariant_noise_budget: bits(Q) - bits(|[t x]_Q|_inf) - 1, floored at 0
-  int noise_budget(const uint64_t* ct) const {
-    check_ct(ct);
-    std::vector<uint64_t> ph((size_t)k * N);
-    phase(ct, ph.data());
+  void decrypt(const uint64_t* ct, uint64_t* pt) const { decrypt_level(ct, k, pt); }
+  // Decryptor::invariant_noise_budget: bits(Q_r) - bits(|[t x]_{Q_r}|_inf) - 1, floored at 0
+  int noise_budget_level(const uint64_t* ct, uint32_t r) const {
+    const Level& lv = level(r);
+    check_ct(ct, r);
+    std::vector<uint64_t> ph((size_t)r * N);
+    phase(ct, r, ph.data());
     int worst = 0;
     for (uint32_t i = 0; i < N; ++i) {
       Big acc;
       u128 frac = 0;
       uint64_t ipart = 0;
-      for (uint32_t j = 0; j < k; ++j) {
+      for (uint32_t j = 0; j < r; ++j) {
         const Modulus& m = mod[j];
         const uint64_t tx = m.mul(ph[(size_t)j * N + i], t % m.q);
-        const uint64_t y = m.mul(tx, inv_punct[j]);
-        acc.muladd(punct[j], y);
+        const uint64_t y = m.mul(tx, lv.inv_punct[j]);
+        acc.muladd(lv.punct[j], y);
         frac += (((u128)y) << 64) / m.q;
         ipart += (uint64_t)(frac >> 64);
         frac = (uint64_t)frac;
       }
       // acc = [t x]_Q + v Q with v = floor(sum y_j / q_j) up to fixed-point error: correct by at most one Q
-      Big vq = Q;
+      Big vq = lv.Q;
       vq.mul_word(ipart);
-      if (acc.sub(vq)) acc.add(Q);
-      while (acc.cmp(Q) >= 0) acc.sub(Q);
-      if (acc.cmp(half_Q) > 0) {
-        Big r = Q;
-        r.sub(acc);
-        acc = r;
+      if (acc.sub(vq)) acc.add(lv.Q);
+      while (acc.cmp(lv.Q) >= 0) acc.sub(lv.Q);
+      if (acc.cmp(lv.half_Q) > 0) {
+        Big r2 = lv.Q;
+        r2.sub(acc);
+        acc = r2;
       }
       worst = std::max(worst, acc.bits());
     }
-    return std::max(0, q_bits - worst - 1);
+    return std::max(0, lv.q_bits - worst - 1);
   }
+  int noise_budget(const uint64_t* ct) const { return noise_budget_level(ct, k); }
 
   // ---------------------------------------------------------------- reencoder
   void reencode(const uint64_t* ct, uint64_t* pts) const {  // ct_reencoder.cpp:40-73
@@ -565,11 +616,12 @@ struct pirclient {
           for (uint32_t c = 0; c < N; ++c) o[c] = (src[c] >> shift) & mask;
       }
   }
-  void redecode(const uint64_t* pts, uint64_t* ct) const {  // ct_reencoder.cpp:79-111
+  // r: residues of the re-encoded ciphertext (k, or the server's result_primes)
+  void redecode(const uint64_t* pts, uint64_t* ct, uint32_t r) const {  // ct_reencoder.cpp:79-111
     const uint64_t* in = pts;
     for (uint32_t poly = 0; poly < 2; ++poly)
-      for (uint32_t j = 0; j < k; ++j) {
-        uint64_t* dst = ct + ((size_t)poly * k + j) * N;
+      for (uint32_t j = 0; j < r; ++j) {
+        uint64_t* dst = ct + ((size_t)poly * r + j) * N;
         for (uint32_t d = 0, shift = 0; d < local_ratio[j]; ++d, shift += pt_bits, in += N)
           for (uint32_t c = 0; c < N; ++c) dst[c] = shift ? dst[c] + (in[c] << shift) : in[c];
       }
@@ -588,7 +640,7 @@ struct pirclient {
   uint64_t plane_bytes() const { return (uint64_t)N * bits_per_coeff / 8; }   // StringEncoder::max_bytes_per_plaintext
   uint64_t plane_reply_ct_count() const {
     uint64_t n = 1;
-    for (uint32_t d = 1; d < prm.num_dimensions; ++d) n *= 2ull * exp_ratio;
+    for (uint32_t d = 1; d < prm.num_dimensions; ++d) n *= reply_ratio();
     return n;
   }
   uint64_t reply_ct_count() const { return planes() * plane_reply_ct_count(); }
@@ -653,17 +705,19 @@ struct pirclient {
       decrypt(reply, pt_out);
       return;
     }
-    const size_t ratio = (size_t)exp_ratio * 2;
+    const size_t ratio = reply_ratio();
+    const uint32_t r = reply_primes();
+    const size_t ctw = reply_ct_words();   // every ciphertext of the recursion is at the reply's level
     if (n_cts != plane_reply_ct_count())   // one plane's reply: what the reference's client gets
       throw Err{PIRGPU_INVALID_ARGUMENT, "Number of ciphertexts in reply does not match expected"};
-    std::vector<uint64_t> cts(reply, reply + n_cts * ct_words()), pts;
+    std::vector<uint64_t> cts(reply, reply + n_cts * ctw), pts;
     size_t n = n_cts;
     for (uint32_t d = 0; d < prm.num_dimensions; ++d) {
       pts.resize(n * N);
-      for (size_t i = 0; i < n; ++i) decrypt(cts.data() + i * ct_words(), pts.data() + i * N);
+      for (size_t i = 0; i < n; ++i) decrypt_level(cts.data() + i * ctw, r, pts.data() + i * N);
       if (n <= 1) break;
       n /= ratio;
-      for (size_t i = 0; i < n; ++i) redecode(pts.data() + i * ratio * N, cts.data() + i * ct_words());
+      for (size_t i = 0; i < n; ++i) redecode(pts.data() + i * ratio * N, cts.data() + i * ctw, r);
     }
     memcpy(pt_out, pts.data(), (size_t)N * 8);
   }
@@ -755,7 +809,7 @@ struct pirclient {
   }
   void reply_plaintext(const std::pair<const uint8_t*, size_t>& msg, uint64_t* pt) const {
     std::vector<uint64_t> cts;
-    const uint32_t n = wire::load_query(sh, msg.first, msg.second, cts);
+    const uint32_t n = wire::load_query(rsh, msg.first, msg.second, cts);
     process_reply(cts.data(), n, pt);
   }
 };
@@ -853,10 +907,10 @@ int pirclient_load_response(pirclient* c, const uint8_t* response, size_t respon
   return guarded(c, [&] {
     const auto replies = pirclient::parse_response(response, response_len);
     if (cap_replies < replies.size() || (!replies_out && !replies.empty())) throw Err{PIRGPU_INVALID_ARGUMENT, "replies_out too small"};
-    const size_t per = (size_t)c->reply_ct_count() * c->ct_words();
+    const size_t per = (size_t)c->reply_ct_count() * c->reply_ct_words();
     std::vector<uint64_t> cts;
     for (size_t i = 0; i < replies.size(); ++i) {
-      const uint32_t n = wire::load_query(c->sh, replies[i].first, replies[i].second, cts);
+      const uint32_t n = wire::load_query(c->rsh, replies[i].first, replies[i].second, cts);
       if (n != c->reply_ct_count()) throw Err{PIRGPU_INVALID_ARGUMENT, "Number of ciphertexts in reply does not match expected"};
       memcpy(replies_out + i * per, cts.data(), per * 8);
     }
@@ -883,14 +937,14 @@ int pirclient_process_response(pirclient* c, const uint64_t* indexes, size_t n_i
         continue;
       }
       // wide item: plane j of the reply decodes to bytes [j B, min((j + 1) B, item)) of it
-      const uint32_t n = wire::load_query(c->sh, replies[i].first, replies[i].second, cts);
+      const uint32_t n = wire::load_query(c->rsh, replies[i].first, replies[i].second, cts);
       if (n != c->reply_ct_count())
         throw Err{PIRGPU_INVALID_ARGUMENT, "Number of ciphertexts in reply does not match expected"};
       const uint64_t B = c->plane_bytes(), R = c->plane_reply_ct_count();
       for (uint32_t pl = 0; pl < c->planes(); ++pl) {
         const uint64_t off = pl * B;
         if (off >= item) throw Err{PIRGPU_INVALID_ARGUMENT, "plaintexts_per_item does not match bytes_per_item"};
-        c->process_reply(cts.data() + (size_t)pl * R * c->ct_words(), R, pt.data());
+        c->process_reply(cts.data() + (size_t)pl * R * c->reply_ct_words(), R, pt.data());
         c->string_decode(pt.data(), std::min<uint64_t>(B, item - off), 0, items_out + i * item + off, false);
       }
     }
@@ -940,7 +994,7 @@ int pirclient_process_reply(pirclient* c, const uint64_t* reply, size_t n_cts, u
     if (c->planes() > 1 && n_cts == c->reply_ct_count()) {   // a wide reply: planes x N coefficients, plane-major
       const uint64_t R = c->plane_reply_ct_count();
       for (uint32_t pl = 0; pl < c->planes(); ++pl)
-        c->process_reply(reply + (size_t)pl * R * c->ct_words(), R, plaintext_out + (size_t)pl * c->N);
+        c->process_reply(reply + (size_t)pl * R * c->reply_ct_words(), R, plaintext_out + (size_t)pl * c->N);
       return;
     }
     c->process_reply(reply, n_cts, plaintext_out);
@@ -960,6 +1014,16 @@ int pirclient_decrypt(pirclient* c, const uint64_t* ct, uint64_t* plaintext_out)
 int pirclient_noise_budget(pirclient* c, const uint64_t* ct, int* bits) {
   if (!c || !ct || !bits) return PIRGPU_INVALID_ARGUMENT;
   return guarded(c, [&] { *bits = c->noise_budget(ct); });
+}
+
+int pirclient_decrypt_level(pirclient* c, const uint64_t* ct, uint32_t r, uint64_t* plaintext_out) {
+  if (!c || !ct || !plaintext_out) return PIRGPU_INVALID_ARGUMENT;
+  return guarded(c, [&] { c->decrypt_level(ct, r, plaintext_out); });
+}
+
+int pirclient_noise_budget_level(pirclient* c, const uint64_t* ct, uint32_t r, int* bits) {
+  if (!c || !ct || !bits) return PIRGPU_INVALID_ARGUMENT;
+  return guarded(c, [&] { *bits = c->noise_budget_level(ct, r); });
 }
 
 int pirclient_reencode(const pirclient* cc, const uint64_t* ct, uint64_t* plaintexts_out, size_t cap_pts,

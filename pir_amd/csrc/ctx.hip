@@ -96,6 +96,7 @@ struct Worker {
   const uint64_t* sv_cur = nullptr;  // selection vector the multiply reads: sv_ntt, or caller-owned memory
   const uint64_t* sv_rows = nullptr; // packed multi-GPU exchange: only this shard's dimension-0 selectors, local index
   std::vector<uint64_t*> lvl;  // per level results; lvl[0] = reply
+  uint64_t* last = nullptr;    // result_primes: level 0 at k primes, before the compact switch writes the reply to lvl[0]
   uint64_t* pt_buf = nullptr;
   uint64_t* scan_part = nullptr;
   uint64_t* up_scratch = nullptr;    // split upper level (large rings): transformed plaintexts of one block of children
@@ -135,6 +136,7 @@ struct BatchLane {
   // the multiply of a whole group runs on the lane's stream in these query-major buffers: one launch per kernel
   // for the (up to) 8 queries instead of one stream + one launch per query
   std::vector<uint64_t*> lvl;        // [level][query][lvl_cts[level]][2][k][N]
+  uint64_t* last = nullptr;          // result_primes: [query][lvl_cts[0]][2][k][N], level 0 before the compact switch
   uint64_t* pt_buf = nullptr;        // [query][pt_words]
   uint64_t* scan_part = nullptr;     // [query][column chunk][scan_rows][2][k][N] (matrices wider than one chunk)
   uint64_t* up_scratch = nullptr;    // split upper level (large rings)
@@ -152,6 +154,8 @@ struct Stage {
   uint64_t** up_scratch = nullptr;   // owner's scratch for the split upper level, grown on demand
   size_t* up_scratch_words = nullptr;
   bool sel_f64 = false;   // the selectors are exact doubles (a lane's own expansion, pirgpu_ctx::sel_f64)
+  uint64_t* last = nullptr;     // result_primes: the owner's level-0 buffer at k primes (query-major, lvl_cts[0] each);
+                                // the compact switch writes the reply from there to lvl[0]
   bool rows_inverted = false;   // the row sums in lvl[d - 1] are in coefficient form already (slot-sharded step: the
                                 // inverse transform gathered them out of the exchange buffer)
 };
@@ -211,6 +215,8 @@ struct pirgpu_ctx {
   pirgpu_params prm{};
   uint32_t N = 0, logN = 0, k = 0, d = 0;
   size_t ctw = 0;  // words per ciphertext
+  uint32_t rp = 0;   // pirgpu_params.result_primes (0: level results and replies stay at k primes)
+  size_t rctw = 0;   // words per REPLY ciphertext: 2 rp N, or ctw
   uint32_t dims[PIRGPU_MAX_DIMS]{};
   uint64_t stride[PIRGPU_MAX_DIMS + 1]{};  // plaintexts under one node of level l
   uint32_t sv_off[PIRGPU_MAX_DIMS + 1]{};  // selection-vector offset of dimension l
@@ -508,12 +514,25 @@ void build_tables(pirgpu_ctx* c) {
       acc = hm::mulmod(acc, w, q);
     }
   }
-  // CiphertextReencoder::Encode order (reference ct_reencoder.cpp:49-69)
+  // modulus switch: the constants of the drop step of every possible last prime q_m (any level is reachable through
+  // pirgpu_mod_switch, whatever result_primes says)
+  for (uint32_t m = 1; m < k; ++m) {
+    const uint64_t qm = hp.mod[m].q;
+    hp.ms_half[m] = qm >> 1;
+    for (uint32_t i = 0; i < m; ++i) {
+      const uint64_t q = hp.mod[i].q;
+      hp.ms_half_mod[m][i] = (qm >> 1) % q;
+      hp.ms_inv[m][i] = hm::invmod_prime(qm % q, q);
+      hp.ms_inv_s[m][i] = hm::shoup(hp.ms_inv[m][i], q);
+    }
+  }
+  // CiphertextReencoder::Encode order (reference ct_reencoder.cpp:49-69); with result_primes the level results have
+  // been switched to their first rp residues before Encode reads them
   const uint32_t b = hm::bits_per_coeff(t);
   hp.enc_bits = b;
   uint32_t e = 0;
   for (uint32_t poly = 0; poly < 2; ++poly)
-    for (uint32_t j = 0; j < k; ++j) {
+    for (uint32_t j = 0; j < (c->rp ? c->rp : k); ++j) {
       uint32_t ler = hm::local_expansion_ratio(hp.mod[j].q, b);
       for (uint32_t i = 0; i < ler; ++i) {
         if (e >= (uint32_t)kMaxEnc) throw Fail{PIRGPU_INVALID_ARGUMENT, "expansion ratio too large"};
@@ -792,6 +811,7 @@ void alloc_worker(pirgpu_ctx* c, Worker& w) {
   w.d_query = c->dalloc<uint64_t>((size_t)(c->dim_sum / c->N + 1) * ctw);
   w.lvl.assign(c->d, nullptr);
   for (uint32_t l = 0; l < c->d; ++l) w.lvl[l] = c->dalloc<uint64_t>(c->lvl_cts[l] * ctw);
+  if (c->rp) w.last = c->dalloc<uint64_t>(c->lvl_cts[0] * ctw);
   if (c->pt_words) w.pt_buf = c->dalloc<uint64_t>(c->pt_words);
   const uint32_t parts = std::max<uint32_t>(c->scan_nsplit, c->mfma_on ? c->mg.nchunks : 1);
   if (parts > 1) w.scan_part = c->dalloc<uint64_t>((size_t)parts * std::max<uint32_t>(c->scan_rows, 1) * ctw);
@@ -1099,6 +1119,16 @@ void refuse_wide(const pirgpu_ctx* c) {
                                            "points do not serve them"};
 }
 
+// Modulus switching does not commute with the sum over shards: a context with result_primes serves one GPU.
+void refuse_switched(const pirgpu_ctx* c) {
+  if (c->rp)
+    throw Fail{PIRGPU_FAILED_PRECONDITION, "this context switches its results to fewer primes (result_primes > 0): the "
+                                           "multi-GPU entry points do not serve it"};
+}
+
+// d = 1 with result_primes: the scan's sums are level 0 at k primes -- they go to the worker's `last` buffer
+uint64_t* scan_out(const pirgpu_ctx* c, Worker& w) { return c->rp && c->d == 1 ? w.last : w.lvl[c->d - 1]; }
+
 void refuse_slot_shard(const pirgpu_ctx* c) {
   if (c->slot_sharded)
     throw Fail{PIRGPU_FAILED_PRECONDITION, "this context is a slot shard: it serves the pirgpu_slots_* entry points only"};
@@ -1224,7 +1254,7 @@ void scan_group_mfma(pirgpu_ctx* c, hipStream_t st, uint8_t*& selp, const MfmaPt
 // Base case of PIRDatabase::multiply (reference database.cpp:185-194,238-247): one fused
 // multiply_plain + add_inplace pass over the database.  Leaves NTT-form row sums in lvl[d-1].
 void scan_on_device(pirgpu_ctx* c, Worker& w) {
-  const uint32_t N = c->N, k = c->k, d = c->d;
+  const uint32_t N = c->N, k = c->k;
   const size_t ctw = c->ctw;
   refuse_slot_shard(c);
   if (c->n_loaded != held_pts(c))
@@ -1234,11 +1264,11 @@ void scan_on_device(pirgpu_ctx* c, Worker& w) {
   if (c->mfma_on && c->mfma_single) {
     MfmaPtrs col{};
     col.p[0] = scan_selectors(c, w);
-    scan_group_mfma(c, w.stream, w.selp, col, 1, w.lvl[d - 1], w.scan_part, &w);
+    scan_group_mfma(c, w.stream, w.selp, col, 1, scan_out(c, w), w.scan_part, &w);
     return;
   }
   const uint64_t* sv_base = scan_selectors(c, w);
-  uint64_t* base_out = w.lvl[d - 1];
+  uint64_t* base_out = scan_out(c, w);
   if (c->mq_single && mq_usable(c)) {
     HIP_TRY(launch_scan_mq(w.stream, c->dp, N, k, c->d_db, &sv_base, &base_out, 1, c->scan_rows, c->scan_cols,
                            c->mq_single_rows, c->mq_single_limb && c->scan_limb));
@@ -1259,13 +1289,29 @@ void post_scan_stage(pirgpu_ctx* c, const Stage& sg, Worker* profiled) {
   const size_t ctw = c->ctw;
   const uint64_t shard_pts = matrix_pts(c);
   hipStream_t st = sg.stream;
+  if (c->rp && !sg.last) throw Fail{PIRGPU_INTERNAL, "result_primes without a level-0 buffer"};
+  // level l's result at k primes: lvl[l], or -- result_primes, level 0 -- the owner's `last` buffer, from where the
+  // compact switch writes the reply to lvl[0]
+  auto level = [&](uint32_t l) { return c->rp && l == 0 ? sg.last : sg.lvl[l]; };
+  // result_primes: every level result is switched right after its inverse transform (all flavours leave canonical u64
+  // residues there: Encode reads them as such) -- in place below the reply, compact for the reply itself
+  auto switch_level = [&](uint32_t l) {
+    if (!c->rp) return;
+    const uint64_t qstride = c->lvl_cts[l] * ctw;
+    if (l == 0)
+      HIP_TRY(launch_mod_switch(st, c->dp, sg.last, sg.lvl[0], c->lvl_cts[0], k, c->rp, N, true, sg.n, qstride,
+                                c->reply_cts * c->rctw));
+    else
+      HIP_TRY(launch_mod_switch(st, c->dp, sg.lvl[l], sg.lvl[l], c->lvl_cts[l], k, c->rp, N, false, sg.n, qstride, qstride));
+  };
   if (shard_pts == 0) {
-    HIP_TRY(hipMemsetAsync(sg.lvl[0], 0, (size_t)sg.n * c->reply_cts * ctw * 8, st));
+    HIP_TRY(hipMemsetAsync(sg.lvl[0], 0, (size_t)sg.n * c->reply_cts * c->rctw * 8, st));
     return;
   }
   if (profiled) record(c, *profiled, PH_UPPER);  // end of scan phase
   if (!sg.rows_inverted)
-    HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp, sg.lvl[d - 1], (uint64_t)sg.n * c->scan_rows * 2 * k, k, 0, true));
+    HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp, level(d - 1), (uint64_t)sg.n * c->scan_rows * 2 * k, k, 0, true));
+  switch_level(d - 1);
   // upper levels: fused re-encode + lift + NTT + multiply-accumulate over chunks of children,
   // then one kernel folds the chunk sums and applies the inverse NTT
   uint64_t C = 1;  // ciphertexts per child
@@ -1313,11 +1359,11 @@ void post_scan_stage(pirgpu_ctx* c, const Stage& sg, Worker* profiled) {
         HIP_TRY(c->ops->upper_ntt(st, c->mode, c->dp, k, c->E, sg.lvl[l + 1], *sg.up_scratch, (uint32_t)rows, c->dims[l],
                                   (uint32_t)nch, (uint32_t)C, b0, blk, sg.n, c->lvl_cts[l + 1] * ctw, c->loop_transforms));
         if (c->mode == kNttInt)   // N = 32768
-          HIP_TRY(launch_upper_mac_int(st, c->dp, *sg.up_scratch, sg.sel, sg.pt_buf, sg.lvl[l], sg.n, (uint32_t)rows,
+          HIP_TRY(launch_upper_mac_int(st, c->dp, *sg.up_scratch, sg.sel, sg.pt_buf, level(l), sg.n, (uint32_t)rows,
                                        (uint32_t)C, c->E, k, N, sv_first, b0, blk, nd, b0 == 0, b0 + blk >= nd, c->pt_words,
                                        c->lvl_cts[l] * ctw));
         else
-          HIP_TRY(launch_upper_mac(st, c->dp, *sg.up_scratch, sg.sel, sg.pt_buf, sg.lvl[l], sg.n, (uint32_t)rows, (uint32_t)C,
+          HIP_TRY(launch_upper_mac(st, c->dp, *sg.up_scratch, sg.sel, sg.pt_buf, level(l), sg.n, (uint32_t)rows, (uint32_t)C,
                                    c->E, k, N, sv_first, b0, blk, nd, b0 == 0, b0 + blk >= nd, c->pt_words,
                                    c->lvl_cts[l] * ctw));
       }
@@ -1328,10 +1374,11 @@ void post_scan_stage(pirgpu_ctx* c, const Stage& sg, Worker* profiled) {
                                   c->lvl_cts[l + 1] * ctw, c->pt_words, sg.sel_f64));
       if (l == 0 && profiled) record(c, *profiled, PH_FINAL);
       // fold the chunk sums (wide, elementwise) and return to coefficient form (database.cpp:250-254)
-      HIP_TRY(launch_reduce_splits(st, c->dp, sg.pt_buf, n_chunks, out_polys * N, sg.lvl[l], sg.n, c->pt_words,
+      HIP_TRY(launch_reduce_splits(st, c->dp, sg.pt_buf, n_chunks, out_polys * N, level(l), sg.n, c->pt_words,
                                    c->lvl_cts[l] * ctw));
     }
-    HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp, sg.lvl[l], (uint64_t)sg.n * out_polys, k, 0, true));
+    HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp, level(l), (uint64_t)sg.n * out_polys, k, 0, true));
+    switch_level(l);
     C *= c->E;
   }
   if (d == 1 && profiled) record(c, *profiled, PH_FINAL);
@@ -1342,6 +1389,7 @@ void post_scan_stage(pirgpu_ctx* c, const Stage& sg, Worker* profiled) {
 void post_scan_on_device(pirgpu_ctx* c, Worker& w) {
   Stage sg{w.stream, w.lvl.data(), w.pt_buf, 1, MfmaPtrs{}, w.sv_rows != nullptr, &w.up_scratch, &w.up_scratch_words};
   sg.sel.p[0] = w.sv_rows ? w.sv_rows : (w.sv_cur ? w.sv_cur : w.sv_ntt);
+  sg.last = w.last;
   post_scan_stage(c, sg, &w);
 }
 
@@ -1479,6 +1527,13 @@ int pirgpu_create_ex(const pirgpu_params* p, uint32_t flags, pirgpu_ctx** out) {
         return bail(PIRGPU_INVALID_ARGUMENT, "plaintexts_per_item > 1 needs 0 < num_pt <= the product of the dimensions");
       c->plane_pad = c->stride[0];
     }
+    c->rp = p->result_primes;
+    if (c->rp >= k)
+      return bail(PIRGPU_INVALID_ARGUMENT, "result_primes must be below num_data_primes (0 = keep every result at the full modulus)");
+    if (c->rp && (c->sb != 0 || c->se != c->dims[0] || c->slot_sharded))
+      return bail(PIRGPU_INVALID_ARGUMENT, "result_primes > 0 is served by one GPU: modulus switching does not commute with "
+                                           "the sum over row or slot shards");
+    c->rctw = c->rp ? (size_t)2 * c->rp * N : c->ctw;
     c->device = p->device;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
@@ -1670,6 +1725,29 @@ int pirgpu_get_params(const pirgpu_ctx* c, pirgpu_params* out) {
 uint64_t pirgpu_db_size(const pirgpu_ctx* c) { return c ? c->n_loaded : 0; }
 uint32_t pirgpu_planes(const pirgpu_ctx* c) { return c ? c->planes : 0; }
 uint64_t pirgpu_reply_ct_count(const pirgpu_ctx* c) { return c ? c->reply_cts : 0; }
+uint64_t pirgpu_reply_ct_words(const pirgpu_ctx* c) { return c ? c->rctw : 0; }
+
+int pirgpu_mod_switch(pirgpu_ctx* c, const uint64_t* cts, uint64_t n, uint32_t r, uint64_t* out) {
+  return guarded(c, [&]() -> int {
+    if ((!cts || !out) && n) return fail(c, PIRGPU_INVALID_ARGUMENT, "null buffer");
+    if (r < 1 || r >= c->k) return fail(c, PIRGPU_INVALID_ARGUMENT, "r must be in [1, num_data_primes)");
+    if (!n) return PIRGPU_OK;
+    const size_t in_words = (size_t)n * c->ctw, out_words = (size_t)n * 2 * r * c->N;
+    uint64_t* dev = nullptr;
+    HIP_TRY(hipMalloc((void**)&dev, (in_words + out_words) * 8));
+    try {
+      HIP_TRY(hipMemcpyAsync(dev, cts, in_words * 8, hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(launch_mod_switch(c->stream, c->dp, dev, dev + in_words, n, c->k, r, c->N, true));
+      HIP_TRY(hipMemcpyAsync(out, dev + in_words, out_words * 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+    } catch (...) {
+      (void)hipFree(dev);
+      throw;
+    }
+    HIP_TRY(hipFree(dev));
+    return PIRGPU_OK;
+  });
+}
 uint32_t pirgpu_expansion_ratio(const pirgpu_ctx* c) { return c ? c->er : 0; }
 uint64_t pirgpu_scan_bytes(const pirgpu_ctx* cc) {
   pirgpu_ctx* c = const_cast<pirgpu_ctx*>(cc);
@@ -2453,7 +2531,7 @@ uint64_t* pirgpu_host_query_buffer(pirgpu_ctx* c, uint32_t count) {
 uint64_t* pirgpu_host_reply_buffer(pirgpu_ctx* c, uint32_t count) {
   uint64_t* out = nullptr;
   (void)guarded(c, [&]() -> int {
-    out = host_buffer(c, c->bs().h_reply, c->bs().h_reply_words, (size_t)std::max<uint32_t>(count, 1) * c->reply_cts * c->ctw);
+    out = host_buffer(c, c->bs().h_reply, c->bs().h_reply_words, (size_t)std::max<uint32_t>(count, 1) * c->reply_cts * c->rctw);
     return PIRGPU_OK;
   });
   return out;
@@ -2610,7 +2688,7 @@ int pirgpu_query_fetch(pirgpu_ctx* c, uint64_t* reply, uint64_t cap, uint64_t* c
     Worker& w = c->workers[0];
     if (!w.reply_valid) return fail(c, PIRGPU_FAILED_PRECONDITION, "no query has been run");
     if (!reply || cap < c->reply_cts) return fail(c, PIRGPU_INVALID_ARGUMENT, "reply buffer too small");
-    HIP_TRY(hipMemcpyAsync(reply, w.lvl[0], c->reply_cts * c->ctw * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(reply, w.lvl[0], c->reply_cts * c->rctw * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (count) *count = c->reply_cts;
     return PIRGPU_OK;
@@ -2630,10 +2708,10 @@ int pirgpu_query_fetch_begin(pirgpu_ctx* c, uint64_t* reply, uint64_t cap, uint6
     for (hipEvent_t& e : c->ev_fetch)
       if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     const uint64_t a = (c->reply_cts + 1) / 2;
-    HIP_TRY(hipMemcpyAsync(reply, w.lvl[0], a * c->ctw * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(reply, w.lvl[0], a * c->rctw * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipEventRecord(c->ev_fetch[0], c->stream));
     if (c->reply_cts > a)
-      HIP_TRY(hipMemcpyAsync(reply + a * c->ctw, w.lvl[0] + a * c->ctw, (c->reply_cts - a) * c->ctw * 8, hipMemcpyDeviceToHost,
+      HIP_TRY(hipMemcpyAsync(reply + a * c->rctw, w.lvl[0] + a * c->rctw, (c->reply_cts - a) * c->rctw * 8, hipMemcpyDeviceToHost,
                              c->stream));
     HIP_TRY(hipEventRecord(c->ev_fetch[1], c->stream));
     if (count) *count = c->reply_cts;
@@ -2661,11 +2739,12 @@ uint64_t* pirgpu_reply_device_ptr(pirgpu_ctx* c) { return (c && c->ws_ready) ? c
 
 int pirgpu_reply_copy_to_device(pirgpu_ctx* c, uint64_t* dst, uint64_t cap) {
   return guarded(c, [&]() -> int {
+    refuse_switched(c);
     if (c->workers.empty()) return fail(c, PIRGPU_FAILED_PRECONDITION, "no query has been run");
     Worker& w = c->workers[0];
     if (!w.reply_valid) return fail(c, PIRGPU_FAILED_PRECONDITION, "no query has been run");
     if (!dst || cap < c->reply_cts) return fail(c, PIRGPU_INVALID_ARGUMENT, "reply buffer too small");
-    HIP_TRY(hipMemcpyAsync(dst, w.lvl[0], c->reply_cts * c->ctw * 8, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dst, w.lvl[0], c->reply_cts * c->rctw * 8, hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return PIRGPU_OK;
   });
@@ -2781,7 +2860,7 @@ int pirgpu_multiply(pirgpu_ctx* c, const uint64_t* sv, uint64_t sv_count, uint64
     w.sv_cur = nullptr;
     w.sv_rows = nullptr;
     multiply_on_device(c, w);
-    HIP_TRY(hipMemcpyAsync(reply, w.lvl[0], c->reply_cts * c->ctw * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(reply, w.lvl[0], c->reply_cts * c->rctw * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (count) *count = c->reply_cts;
     return PIRGPU_OK;
@@ -2908,7 +2987,7 @@ static void ensure_batch_capacity(pirgpu_ctx* c, uint32_t count) {
   }
   const uint32_t cap = std::max<uint32_t>(count, std::min<uint32_t>(4096, 2 * old_cap));
   c->bs().d_bquery = c->dalloc<uint64_t>((size_t)cap * nq * c->ctw);
-  c->bs().d_breply = c->dalloc<uint64_t>((size_t)cap * c->reply_cts * c->ctw);
+  c->bs().d_breply = c->dalloc<uint64_t>((size_t)cap * c->reply_cts * c->rctw);
   c->bs().batch_cap = cap;
 }
 
@@ -2938,6 +3017,7 @@ static void ensure_lanes(pirgpu_ctx* c, bool with_expansion_buffers) {
     for (BatchLane& ln : c->lanes) {
       ln.lvl.assign(c->d, nullptr);
       for (uint32_t l = 0; l < c->d; ++l) ln.lvl[l] = c->dalloc<uint64_t>((size_t)kMaxMfmaQueries * c->lvl_cts[l] * c->ctw);
+      if (c->rp) ln.last = c->dalloc<uint64_t>((size_t)kMaxMfmaQueries * c->lvl_cts[0] * c->ctw);
       if (c->pt_words) ln.pt_buf = c->dalloc<uint64_t>((size_t)kMaxMfmaQueries * c->pt_words);
       if (c->mg.nchunks > 1)
         ln.scan_part = c->dalloc<uint64_t>((size_t)kMaxMfmaQueries * c->mg.nchunks * std::max<uint32_t>(c->scan_rows, 1) * c->ctw);
@@ -3039,7 +3119,7 @@ static uint32_t lanes_in_use(pirgpu_ctx* c, uint32_t G) {
 }
 
 static void batch_run_mfma(pirgpu_ctx* c, uint32_t count, const uint64_t* ext_sv, const PackedInput* pk = nullptr) {
-  const size_t rwords = (size_t)c->reply_cts * c->ctw, svwords = (size_t)c->dim_sum * c->ctw;
+  const size_t rwords = (size_t)c->reply_cts * c->rctw, svwords = (size_t)c->dim_sum * c->ctw;
   const uint32_t W = std::max<uint32_t>(1, std::min<uint32_t>(c->n_active, (uint32_t)c->workers.size()));
   const uint32_t G = std::min<uint32_t>(c->mfma_nq, W);
   const uint32_t my_rows = c->se - c->sb;
@@ -3082,6 +3162,7 @@ static void batch_run_mfma(pirgpu_ctx* c, uint32_t count, const uint64_t* ext_sv
       const bool direct_reply = c->d >= 2;   // d = 1 would make the scan itself write there: keep the lane buffer
       if (direct_reply) lvl_ptrs[0] = reply_base(c) + (size_t)first * rwords;
       Stage sg{ln.stream, lvl_ptrs, ln.pt_buf, B, MfmaPtrs{}, pk != nullptr, &ln.up_scratch, &ln.up_scratch_words};
+      sg.last = ln.last;   // result_primes: level 0 lands there, the compact switch writes the replies to lvl_ptrs[0]
       MfmaPtrs col{};
       if (pk) {
         const uint32_t groups_per_rank = (pk->per_rank + kMaxMfmaQueries - 1) / kMaxMfmaQueries;
@@ -3150,7 +3231,7 @@ static void batch_run_impl(pirgpu_ctx* c, uint32_t count, const uint64_t* ext_sv
 static void batch_run_impl_body(pirgpu_ctx* c, uint32_t count, const uint64_t* ext_sv) {
   refuse_slot_shard(c);
   c->bs().host_reply_done = false;   // set again by the path that queues per-group downloads (batch_run_mfma)
-  const size_t rwords = (size_t)c->reply_cts * c->ctw;
+  const size_t rwords = (size_t)c->reply_cts * c->rctw;
   const size_t svwords = (size_t)c->dim_sum * c->ctw;
   const uint32_t W = std::max<uint32_t>(1, std::min<uint32_t>(c->n_active, (uint32_t)c->workers.size()));
   const uint32_t G = mq_usable(c) && c->pt_end > c->pt_begin ? std::min<uint32_t>(c->mq_nq, kMaxScanQueries) : 1;
@@ -3206,7 +3287,7 @@ static void batch_run_impl_body(pirgpu_ctx* c, uint32_t count, const uint64_t* e
             Worker& m = c->workers[j0 + done + q];
             if (q) HIP_TRY(hipStreamWaitEvent(lead.stream, m.ev_expanded, 0));
             svp[q] = scan_selectors(c, m);
-            outp[q] = m.lvl[c->d - 1];
+            outp[q] = scan_out(c, m);
           }
           const uint32_t rpw = take == 4 ? (c->mq_rows > 2 ? 1 : c->mq_rows) : (c->mq_rows > 2 ? 2 : c->mq_rows);
           HIP_TRY(launch_scan_mq(lead.stream, c->dp, c->N, c->k, c->d_db, svp, outp, take, c->scan_rows,
@@ -3299,6 +3380,7 @@ static int batch_expand_packed_impl(pirgpu_ctx* c, uint32_t first_query, uint32_
                                     uint64_t* device_rows, const uint32_t* row_cuts, uint32_t n_ranks, bool wait) {
   return guarded(c, [&]() -> int {
     refuse_wide(c);
+    refuse_switched(c);
     ensure_workspace(c);
     if (c->d != 2 || !c->mfma_on)
       return fail(c, PIRGPU_FAILED_PRECONDITION, "packed selector exchange needs d = 2 and the int8-MFMA scan");
@@ -3366,6 +3448,7 @@ int pirgpu_batch_run_packed(pirgpu_ctx* c, const uint8_t* device_packed, uint32_
                             const uint64_t* device_rows) {
   return guarded(c, [&]() -> int {
     refuse_wide(c);
+    refuse_switched(c);
     ensure_workspace(c);
     if (c->d != 2 || !c->mfma_on)
       return fail(c, PIRGPU_FAILED_PRECONDITION, "packed selector exchange needs d = 2 and the int8-MFMA scan");
@@ -3438,6 +3521,7 @@ void lane_then(BatchLane& ln, void* then) {
 
 void check_slots_ctx(pirgpu_ctx* c) {
   refuse_wide(c);
+  refuse_switched(c);
   ensure_workspace(c);
   if (c->d != 2 || !c->mfma_on || c->mg.nchunks != 1 || c->sb != 0 || c->se != c->dims[0])
     throw Fail{PIRGPU_FAILED_PRECONDITION, "the slot-sharded step needs d = 2, all rows and the int8-MFMA scan in one column chunk"};
@@ -3597,26 +3681,32 @@ int pirgpu_slots_finish_async(pirgpu_ctx* c, const uint64_t* device_rowsums, uin
 
 int pirgpu_batch_reply_copy_to_device(pirgpu_ctx* c, uint64_t* dst, uint64_t cap) {
   return guarded(c, [&]() -> int {
+    refuse_switched(c);
     if (!c->bs().batch_valid) return fail(c, PIRGPU_FAILED_PRECONDITION, "no batch has been run");
     const uint64_t total = (uint64_t)c->bs().batch_count * c->reply_cts;
     if (!dst || cap < total) return fail(c, PIRGPU_INVALID_ARGUMENT, "reply buffer too small");
     sync_batch_streams(c);
     // a device-to-device hipMemcpy on the null stream may return before the copy has run, and the context's
     // streams are non-blocking (not ordered with the null stream): copy on the context's stream and wait
-    HIP_TRY(hipMemcpyAsync(dst, reply_base(c), total * c->ctw * 8, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dst, reply_base(c), total * c->rctw * 8, hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return PIRGPU_OK;
   });
 }
 
 int pirgpu_batch_reply_copy_to_device_async(pirgpu_ctx* c, uint64_t* dst, uint64_t cap) {
-  int rc = pirgpu_join(c);   // the main stream now follows every lane: the copy below sees the finished batch
+  int rc = guarded(c, [&]() -> int {
+    refuse_switched(c);
+    return PIRGPU_OK;
+  });
+  if (rc) return rc;
+  rc = pirgpu_join(c);   // the main stream now follows every lane: the copy below sees the finished batch
   if (rc) return rc;
   return guarded(c, [&]() -> int {
     if (!c->bs().batch_valid) return fail(c, PIRGPU_FAILED_PRECONDITION, "no batch has been run");
     const uint64_t total = (uint64_t)c->bs().batch_count * c->reply_cts;
     if (!dst || cap < total) return fail(c, PIRGPU_INVALID_ARGUMENT, "reply buffer too small");
-    HIP_TRY(hipMemcpyAsync(dst, reply_base(c), total * c->ctw * 8, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dst, reply_base(c), total * c->rctw * 8, hipMemcpyDeviceToDevice, c->stream));
     return PIRGPU_OK;
   });
 }
@@ -3628,7 +3718,7 @@ int pirgpu_batch_fetch(pirgpu_ctx* c, uint64_t* replies, uint64_t cap, uint64_t*
     if (!replies || cap < total) return fail(c, PIRGPU_INVALID_ARGUMENT, "reply buffer too small");
     sync_batch_streams(c);
     if (!(c->bs().host_reply_done && replies == c->bs().host_reply))   // else: the groups downloaded their replies themselves
-      HIP_TRY(hipMemcpy(replies, reply_base(c), total * c->ctw * 8, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(replies, reply_base(c), total * c->rctw * 8, hipMemcpyDeviceToHost));
     if (count) *count = total;
     return PIRGPU_OK;
   });
@@ -3674,6 +3764,7 @@ int pirgpu_ntt_inverse(pirgpu_ctx* c, uint64_t* polys, uint64_t count, int key_l
 
 int pirgpu_reduce_fixup_device(pirgpu_ctx* c, uint64_t* device_ptr, uint64_t count) {
   return guarded(c, [&]() -> int {
+    refuse_switched(c);
     if (!device_ptr) return fail(c, PIRGPU_INVALID_ARGUMENT, "null buffer");
     HIP_TRY(launch_reduce_splits(c->stream, c->dp, device_ptr, 1, count * c->ctw, device_ptr));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -3683,6 +3774,7 @@ int pirgpu_reduce_fixup_device(pirgpu_ctx* c, uint64_t* device_ptr, uint64_t cou
 
 int pirgpu_reduce_fixup_device_async(pirgpu_ctx* c, uint64_t* device_ptr, uint64_t count, void* stream) {
   return guarded(c, [&]() -> int {
+    refuse_switched(c);
     if (!device_ptr) return fail(c, PIRGPU_INVALID_ARGUMENT, "null buffer");
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     HIP_TRY(launch_reduce_splits(st, c->dp, device_ptr, 1, count * c->ctw, device_ptr));

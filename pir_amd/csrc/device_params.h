@@ -88,6 +88,11 @@ struct DevParams {
   uint32_t f64_lazy_inv;
   // MFMA scan, fp64 fold (all data moduli < 2^50): 2^32, 2^64, 2^96 mod q_j as centred doubles
   double fold_w[kMaxPrimes][3];
+  // modulus switch, one drop step per last prime q_m (m = 1 .. k-1), for every i < m:
+  uint64_t ms_half[kMaxPrimes];                   // floor(q_m / 2)
+  uint64_t ms_half_mod[kMaxPrimes][kMaxPrimes];   // floor(q_m / 2) mod q_i
+  uint64_t ms_inv[kMaxPrimes][kMaxPrimes];        // q_m^-1 mod q_i
+  uint64_t ms_inv_s[kMaxPrimes][kMaxPrimes];      // Shoup quotient of ms_inv
 };
 
 }  // namespace pirgpu

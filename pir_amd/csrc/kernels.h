@@ -156,7 +156,12 @@ hipError_t launch_scan_mq(hipStream_t st, const DevParams* P, uint32_t N, uint32
 hipError_t launch_reduce_splits(hipStream_t st, const DevParams* P, const uint64_t* part, uint32_t nsplit,
                                 uint64_t words, uint64_t* out, uint32_t n_queries = 1, uint64_t part_qstride = 0,
                                 uint64_t out_qstride = 0);
-
+// Modulus switch of n_cts coefficient-form ciphertexts [2][k][N] per query from k to r primes (1 <= r < k), k - r drop
+// steps, last prime first.  compact = false: residues 0..r-1 are written where they were read (stride k kept; in == out);
+// compact = true: out is [n_cts][2][r][N].  Query q reads in + q * in_qstride and writes out + q * out_qstride.
+hipError_t launch_mod_switch(hipStream_t st, const DevParams* P, const uint64_t* in, uint64_t* out, uint64_t n_cts,
+                             uint32_t k, uint32_t r, uint32_t N, bool compact, uint32_t n_queries = 1,
+                             uint64_t in_qstride = 0, uint64_t out_qstride = 0);
 
 // the same for the integer flavour at N = 32768 (ntt_ring32k.hip): scratch holds canonical u64 residues (upper_ntt of
 // that degree), `acc` canonical partial sums

@@ -1091,4 +1091,65 @@ hipError_t launch_db_splice(hipStream_t st, const DevParams* P, uint64_t* coef, 
   return hipSuccess;
 }
 
+// ------------------------------------------------------------------ modulus switch (pirgpu_params.result_primes)
+
+// Switches coefficient-form ciphertexts [ct][2][k][N] (canonical u64 residues) from k to r primes: k - r drop steps,
+// last prime first.  One step with the current primes q_0..q_m and h = floor(q_m / 2):
+//   a = (x_m + h) mod q_m;   x_i' = (x_i - (a mod q_i) + (h mod q_i)) * q_m^-1 mod q_i   (i < m)
+// i.e. floor((x + h) / q_m) on the CRT representative, the arithmetic of the key switch's mod-down
+// with q_m in the special prime's place.  A thread owns two neighbouring coefficients of one polynomial: it loads their
+// k residues (N words apart, 16 bytes each), steps in registers and stores r residues -- at the same places
+// (COMPACT = false: stride k kept, the thread has read all it needs before it writes) or as [ct][2][r][N].
+// grid = (pairs / 256, queries); n_pairs = ciphertexts * N per query.
+template <bool COMPACT>
+__global__ void __launch_bounds__(256)
+mod_switch_kernel(const DevParams* __restrict__ P, const uint64_t* in_all, uint64_t* out_all, uint64_t n_pairs,
+                  uint32_t r, uint64_t in_qstride, uint64_t out_qstride) {
+  const uint64_t gid = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= n_pairs) return;
+  const uint32_t k = P->k, logN = P->logN;
+  const uint64_t N = 1ull << logN;
+  const uint64_t poly = gid >> (logN - 1);      // ciphertext * 2 + component
+  const uint64_t i = (gid << 1) & (N - 1);
+  const uint64_t* in = in_all + (size_t)blockIdx.y * in_qstride + poly * k * N + i;
+  u64x2 x[kMaxPrimes];
+#pragma unroll
+  for (int j = 0; j < kMaxPrimes; ++j)
+    if (j < (int)k) x[j] = *reinterpret_cast<const u64x2*>(in + (size_t)j * N);
+#pragma unroll
+  for (int m = kMaxPrimes - 1; m >= 1; --m) {
+    if (m < (int)k && m >= (int)r) {   // uniform
+      const uint64_t qm = P->mod[m].q, h = P->ms_half[m];
+      const uint64_t a0 = add_mod(x[m].x, h, qm), a1 = add_mod(x[m].y, h, qm);
+#pragma unroll
+      for (int j = 0; j < m; ++j) {
+        const ModConst mc = P->mod[j];
+        const uint64_t hj = P->ms_half_mod[m][j], w = P->ms_inv[m][j], ws = P->ms_inv_s[m][j];
+        x[j].x = mul_shoup(add_mod(sub_mod(x[j].x, reduce64(a0, mc), mc.q), hj, mc.q), w, ws, mc.q);
+        x[j].y = mul_shoup(add_mod(sub_mod(x[j].y, reduce64(a1, mc), mc.q), hj, mc.q), w, ws, mc.q);
+      }
+    }
+  }
+  uint64_t* out = out_all + (size_t)blockIdx.y * out_qstride + poly * (COMPACT ? r : k) * N + i;
+#pragma unroll
+  for (int j = 0; j < kMaxPrimes - 1; ++j)
+    if (j < (int)r) *reinterpret_cast<u64x2*>(out + (size_t)j * N) = x[j];
+}
+
+hipError_t launch_mod_switch(hipStream_t st, const DevParams* P, const uint64_t* in, uint64_t* out, uint64_t n_cts,
+                             uint32_t k, uint32_t r, uint32_t N, bool compact, uint32_t n_queries, uint64_t in_qstride,
+                             uint64_t out_qstride) {
+  if (!n_cts || !n_queries) return hipSuccess;
+  if (r < 1 || r >= k || k > (uint32_t)kMaxPrimes || N < 2) return hipErrorInvalidValue;
+  const uint64_t n_pairs = n_cts * N, blocks = (n_pairs + 255) / 256;
+  if (blocks > 0x7fffffffull || n_queries > 65535) return hipErrorInvalidValue;
+  const dim3 grid((uint32_t)blocks, n_queries);
+  if (compact)
+    hipLaunchKernelGGL(mod_switch_kernel<true>, grid, dim3(256), 0, st, P, in, out, n_pairs, r, in_qstride, out_qstride);
+  else
+    hipLaunchKernelGGL(mod_switch_kernel<false>, grid, dim3(256), 0, st, P, in, out, n_pairs, r, in_qstride, out_qstride);
+  PIRGPU_LAUNCH_CHECK();
+  return hipSuccess;
+}
+
 }  // namespace pirgpu

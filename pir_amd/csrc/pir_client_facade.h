@@ -41,6 +41,7 @@ class PIRClient {
     p.bytes_per_item = params->bytes_per_item;
     p.items_per_plaintext = params->items_per_plaintext;
     p.plaintexts_per_item = params->plaintexts_per_item;
+    p.result_primes = params->result_primes;
     p.bits_per_coeff = params->bits_per_coeff;
     p.use_ciphertext_multiplication = params->use_ciphertext_multiplication ? 1 : 0;
     pirclient* c = nullptr;

@@ -66,6 +66,7 @@ struct PIRParameters {
   uint32_t bytes_per_item = 0, items_per_plaintext = 0, bits_per_coeff = 0;
   bool use_ciphertext_multiplication = false;
   uint32_t plaintexts_per_item = 1;      // wide items (not in the reference): pirgpu_params.plaintexts_per_item
+  uint32_t result_primes = 0;            // modulus-switched results (not in the reference): pirgpu_params.result_primes
   size_t DimensionsSum() const {          // PIRContext::DimensionsSum, context.h:59-62
     size_t s = 0;
     for (auto d : dimensions) s += d;
@@ -109,6 +110,7 @@ class PIRDatabase {
     p.bits_per_coeff = params->bits_per_coeff;
     p.use_ciphertext_multiplication = params->use_ciphertext_multiplication ? 1 : 0;
     p.plaintexts_per_item = params->plaintexts_per_item;
+    p.result_primes = params->result_primes;
     p.device = device;
     pirgpu_ctx* ctx = nullptr;
     int rc = pirgpu_create_ex(&p, streamed ? PIRGPU_CREATE_STREAMED_DB : 0u, &ctx);
@@ -168,12 +170,13 @@ class PIRDatabase {
       std::copy(selection_vector[i].begin(), selection_vector[i].end(), in.begin() + i * words);
     }
     const uint64_t n = pirgpu_reply_ct_count(ctx_);
-    std::vector<uint64_t> out(n * words);
+    const size_t rwords = pirgpu_reply_ct_words(ctx_);   // a reply ciphertext has result_primes residues when that is set
+    std::vector<uint64_t> out(n * rwords);
     uint64_t got = 0;
     int rc = pirgpu_multiply(ctx_, in.data(), selection_vector.size(), out.data(), n, &got);
     if (rc) return detail::FromRc(ctx_, rc);
     std::vector<Ciphertext> result(got);
-    for (uint64_t i = 0; i < got; ++i) result[i].assign(out.begin() + i * words, out.begin() + (i + 1) * words);
+    for (uint64_t i = 0; i < got; ++i) result[i].assign(out.begin() + i * rwords, out.begin() + (i + 1) * rwords);
     return result;
   }
 

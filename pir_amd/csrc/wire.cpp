@@ -275,6 +275,8 @@ struct Server {               // what serving needs to know about a context
   pirgpu_params prm;
   Shape sh;
   size_t ctw;
+  Shape rsh;                  // the level the replies are at: sh, or (result_primes) its first r primes with their parms_id
+  size_t rctw;                // words per reply ciphertext
   uint64_t n_reply;
   uint32_t nq_expected;
   struct RelinCache* relin = nullptr;   // per context (Combiner)
@@ -284,6 +286,18 @@ struct Server {               // what serving needs to know about a context
 // Response.reply (payload.proto:39-42) for one query: n ciphertexts, written straight into the response buffer
 // Upper bound of what append_reply adds for a reply of n ciphertexts (tags and varint lengths: < 32 bytes each)
 size_t reply_bytes_bound(const Shape& sh, uint64_t n) { return 32 + n * (32 + saved_ciphertext_size(sh)); }
+
+// The level the replies of a context with these parameters are at: the data level, or -- pirgpu_params.result_primes --
+// its first r primes; a reply ciphertext is then a SEAL ciphertext further down the modulus chain, with that level's
+// parms_id.
+Shape reply_shape(const pirgpu_params& prm, const Shape& sh) {
+  Shape rsh = sh;
+  if (prm.result_primes) {
+    rsh.k = prm.result_primes;
+    parms_id(rsh.N, rsh.q, rsh.k, rsh.t, rsh.data_id);
+  }
+  return rsh;
+}
 
 // `ready(i)` (optional) is called before ciphertext i is copied: the caller can wait there for the part of the download
 // that holds it.
@@ -561,7 +575,7 @@ void run_single(const Server& sv, Job& job, const std::pair<const uint8_t*, size
   rc = pirgpu_query_fetch_begin(sv.ctx, hr, sv.n_reply, &got, &first_part);
   if (rc) throw Err{rc, pirgpu_last_error(sv.ctx)};
   int wrc = 0;
-  append_reply(job.out, sv.sh, hr, got, sv.ctw, [&](uint64_t i) {
+  append_reply(job.out, sv.rsh, hr, got, sv.rctw, [&](uint64_t i) {
     if (i == 0 && !wrc) wrc = pirgpu_query_fetch_wait(sv.ctx, 0);
     if (i == first_part && !wrc) wrc = pirgpu_query_fetch_wait(sv.ctx, 1);
   });
@@ -716,7 +730,7 @@ void begin_window(const Server& sv, Window& w, const std::vector<Item>& items, T
   for (auto& run : w.runs) {
     Job& job = *w.chunk[run.first].job;
     try {
-      job.out.reserve(job.out.n + (run.second - run.first) * reply_bytes_bound(sv.sh, sv.n_reply));
+      job.out.reserve(job.out.n + (run.second - run.first) * reply_bytes_bound(sv.rsh, sv.n_reply));
     } catch (const std::exception& e) {
       fail_job(job, PIRGPU_INTERNAL, e.what());
     }
@@ -752,7 +766,7 @@ void finish_window(const Server& sv, Window& w, Trace& trace) {
   });
   if (w.chunk.empty()) return;
   const uint32_t count = (uint32_t)w.chunk.size();
-  const size_t rwords = (size_t)sv.n_reply * sv.ctw;
+  const size_t rwords = (size_t)sv.n_reply * sv.rctw;
   if (w.rc) {
     for (const Item& it : w.chunk)
       if (!it.job->rc) fail_job(*it.job, w.rc, w.err);
@@ -765,7 +779,7 @@ void finish_window(const Server& sv, Window& w, Trace& trace) {
     if (job.rc || !job.uniform || job.mismatch) return;
     try {
       for (uint32_t i = w.runs[r].first; i < w.runs[r].second; ++i)
-        append_reply(job.out, sv.sh, w.hr + (size_t)i * rwords, sv.n_reply, sv.ctw);
+        append_reply(job.out, sv.rsh, w.hr + (size_t)i * rwords, sv.n_reply, sv.rctw);
     } catch (const std::exception& e) {
       fail_job(job, PIRGPU_INTERNAL, e.what());
     }
@@ -846,6 +860,8 @@ void serve(pirgpu_ctx* ctx, Combiner& cb, int first_set, Job* const* jobs, size_
   }
   sv.sh = make_shape(sv.prm);
   sv.ctw = (size_t)2 * sv.sh.k * sv.sh.N;
+  sv.rsh = reply_shape(sv.prm, sv.sh);
+  sv.rctw = (size_t)2 * sv.rsh.k * sv.rsh.N;   // == pirgpu_reply_ct_words(ctx)
   sv.n_reply = pirgpu_reply_ct_count(ctx);
   uint64_t dim_sum = 0;
   for (uint32_t l = 0; l < sv.prm.num_dimensions; ++l) dim_sum += sv.prm.dimensions[l];
@@ -1111,6 +1127,22 @@ std::shared_ptr<Combiner> combiner_for(pirgpu_ctx* ctx) {
 extern "C" {
 
 void pirgpu_free(void* p) { pool_release(static_cast<uint8_t*>(p)); }
+
+int pirgpu_wire_save_reply(const pirgpu_params* params, const uint64_t* cts, uint64_t n, uint8_t** out, size_t* out_len) {
+  if (!params || (!cts && n) || !out || !out_len) return PIRGPU_INVALID_ARGUMENT;
+  if (params->result_primes >= params->num_data_primes) return PIRGPU_INVALID_ARGUMENT;
+  try {
+    const Shape rsh = reply_shape(*params, make_shape(*params));
+    OutBuf buf;
+    append_reply(buf, rsh, cts, n, (size_t)2 * rsh.k * rsh.N);
+    *out = buf.release(out_len);
+    return PIRGPU_OK;
+  } catch (const Err& e) {
+    return e.code;
+  } catch (const std::exception&) {
+    return PIRGPU_INTERNAL;
+  }
+}
 
 void pirgpu_wire_forget(pirgpu_ctx* ctx) {
   std::lock_guard<std::mutex> lock(g_combiners_mu);

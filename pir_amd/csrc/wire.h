@@ -20,6 +20,11 @@ int pirgpu_wire_load_kswitch_key(const struct pirgpu_params* params, const uint8
 struct pirgpu_params;
 int pirgpu_wire_validate_request(const struct pirgpu_params* params, const uint8_t* request, size_t request_len,
                                  uint32_t* n_queries);
+// Device-free serialisation of one query's reply the way pirgpu_process_request does it: cts = n reply ciphertexts
+// [2][r][N] (r = params->result_primes, or num_data_primes when that is 0) -> one Response.reply field; release with
+// pirgpu_free.
+int pirgpu_wire_save_reply(const struct pirgpu_params* params, const uint64_t* cts, uint64_t n, uint8_t** out,
+                           size_t* out_len);
 // A pinned key set is never evicted or released (one pin per request in flight that uses it; slot handles as handed out
 // by pirgpu_keyset_lookup / _claim).
 struct pirgpu_ctx;

@@ -134,6 +134,8 @@ class PIRParameters:
     bits_per_coeff: int = 0
     use_ciphertext_multiplication: bool = False
     plaintexts_per_item: int = 1      # wide items (not in the reference): planes an item is spread over
+    result_primes: int = 0            # modulus-switched results (not in the reference): data primes a level result and
+                                      # the reply keep; 0 = all of them
 
     @property
     def planes(self) -> int:
@@ -169,14 +171,21 @@ class PIRParameters:
 
 def create_pir_parameters(dbsize: int, bytes_per_item: int = 0, dimensions: int = 1,
                           enc: Optional[EncryptionParams] = None, use_ciphertext_multiplication: bool = False,
-                          bits_per_coeff_: int = 0, max_plaintexts_per_item: int = 1) -> PIRParameters:
+                          bits_per_coeff_: int = 0, max_plaintexts_per_item: int = 1,
+                          result_primes: int = 0) -> PIRParameters:
     """CreatePIRParameters (parameters.cpp:56-107); raises ValueError where it returns InvalidArgument.
 
     max_plaintexts_per_item > 1 (not in the reference) opts in to wide items: an item that does not fit one plaintext is
-    spread over ceil(bytes_per_item / max_bytes_per_plaintext) plaintexts (planes), at most that many."""
+    spread over ceil(bytes_per_item / max_bytes_per_plaintext) plaintexts (planes), at most that many.
+
+    result_primes = r >= 1 (not in the reference) opts in to modulus-switched results: the server switches every level
+    result and the reply down to the first r data primes (r below their number), which shrinks the re-encoding and the
+    reply; the client must be created with the same parameters."""
     if enc is None:
         enc = generate_encryption_params()
     N, t = enc.poly_modulus_degree, enc.plain_modulus
+    if result_primes < 0 or (result_primes and result_primes >= len(enc.coeff_modulus) - 1):
+        raise ValueError("result_primes must be below the number of data primes")
     bpc = bits_per_coeff(t)
     if bits_per_coeff_ > 0:
         if bits_per_coeff_ > bpc:
@@ -204,4 +213,4 @@ def create_pir_parameters(dbsize: int, bytes_per_item: int = 0, dimensions: int 
     return PIRParameters(num_items=dbsize, num_pt=num_pt, dimensions=calculate_dimensions(num_pt, dimensions),
                          encryption_parameters=enc, bytes_per_item=bpi, items_per_plaintext=ipp,
                          bits_per_coeff=bits_per_coeff_, use_ciphertext_multiplication=use_ciphertext_multiplication,
-                         plaintexts_per_item=planes)
+                         plaintexts_per_item=planes, result_primes=result_primes)

@@ -79,6 +79,11 @@ class PIRDatabase:
         self._h = h
 
     # -- lifetime ---------------------------------------------------------------
+    @property
+    def reply_k(self) -> int:
+        """Residues of a reply ciphertext: params.result_primes, or all k data primes when that is 0."""
+        return getattr(self.params, "result_primes", 0) or self.k
+
     def close(self):
         if getattr(self, "_h", None):
             self.lib.pirgpu_destroy(self._h)
@@ -221,13 +226,26 @@ class PIRDatabase:
     def expansion_ratio(self) -> int:
         return int(self.lib.pirgpu_expansion_ratio(self._h))
 
+    def reply_ct_words(self) -> int:
+        """Words of one reply ciphertext: 2 * reply_k * N."""
+        return int(self.lib.pirgpu_reply_ct_words(self._h))
+
+    def mod_switch(self, cts, r: int) -> np.ndarray:
+        """Test hook: [n, 2, k, N] coefficient-form ciphertexts switched down to their first r primes -> [n, 2, r, N]."""
+        c = _u64(cts)
+        if c.ndim != 4 or c.shape[1:] != (2, self.k, self.N):
+            raise PirGpuError(3, "ciphertexts must have shape [n, 2, %d, %d], got %s" % (self.k, self.N, list(c.shape)))
+        out = np.empty((c.shape[0], 2, max(int(r), 1), self.N), dtype=np.uint64)
+        self._check(self.lib.pirgpu_mod_switch(self._h, _ptr(c), c.shape[0], int(r), _ptr(out)))
+        return out
+
     def multiply(self, selection_vector) -> np.ndarray:
         """database.cpp:290-316: selection vector [dim_sum, 2, k, N] (coefficient form) -> reply cts."""
         sv = _u64(selection_vector)
         if sv.ndim != 4 or sv.shape[1:] != (2, self.k, self.N):
             raise PirGpuError(3, "selection vector must have shape [n, 2, %d, %d], got %s" % (self.k, self.N, list(sv.shape)))
         n = self.reply_ct_count()
-        out = np.empty((n, 2, self.k, self.N), dtype=np.uint64)
+        out = np.empty((n, 2, self.reply_k, self.N), dtype=np.uint64)
         cnt = C.c_uint64(0)
         self._check(self.lib.pirgpu_multiply(self._h, _ptr(sv), sv.shape[0], _ptr(out), n, C.byref(cnt)))
         return out[: cnt.value]
@@ -249,6 +267,10 @@ class PIRServer:
         self.params = params
         self.lib = db.lib
         self.N, self.k = db.N, db.k
+
+    @property
+    def reply_k(self) -> int:
+        return self.db.reply_k
 
     @classmethod
     def Create(cls, db: PIRDatabase, params: PIRParameters) -> "PIRServer":
@@ -329,7 +351,7 @@ class PIRServer:
             self.set_galois_keys(galois_keys)
         q = self._cts(query, 4, "query")
         n = self.db.reply_ct_count()
-        out = np.empty((n, 2, self.k, self.N), dtype=np.uint64)
+        out = np.empty((n, 2, self.reply_k, self.N), dtype=np.uint64)
         cnt = C.c_uint64(0)
         self._check(self.lib.pirgpu_process_query(self.db.handle, _ptr(q), q.shape[0], _ptr(out), n, C.byref(cnt)))
         return out[: cnt.value]
@@ -449,7 +471,7 @@ class PIRServer:
 
     def fetch_reply(self) -> np.ndarray:
         n = self.db.reply_ct_count()
-        out = np.empty((n, 2, self.k, self.N), dtype=np.uint64)
+        out = np.empty((n, 2, self.reply_k, self.N), dtype=np.uint64)
         cnt = C.c_uint64(0)
         self._check(self.lib.pirgpu_query_fetch(self.db.handle, _ptr(out), n, C.byref(cnt)))
         return out[: cnt.value]
@@ -474,7 +496,7 @@ class PIRServer:
 
     def fetch_batch(self) -> np.ndarray:
         n = self.db.reply_ct_count()
-        out = np.empty((self._batch_count, n, 2, self.k, self.N), dtype=np.uint64)
+        out = np.empty((self._batch_count, n, 2, self.reply_k, self.N), dtype=np.uint64)
         cnt = C.c_uint64(0)
         self._check(self.lib.pirgpu_batch_fetch(self.db.handle, _ptr(out), self._batch_count * n, C.byref(cnt)))
         return out
@@ -602,7 +624,7 @@ class PIRServer:
         self._check(self.lib.pirgpu_reduce_fixup_device(self.db.handle, C.c_void_p(device_ptr), n_cts))
 
     def process_batch(self, queries, n_workers: Optional[int] = None) -> np.ndarray:
-        """All queries of one request: [count, nq, 2, k, N] -> [count, reply_cts, 2, k, N]."""
+        """All queries of one request: [count, nq, 2, k, N] -> [count, reply_cts, 2, reply_k, N]."""
         if n_workers is not None:
             self.set_concurrency(n_workers)
         self.stage_batch(queries)
