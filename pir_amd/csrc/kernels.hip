@@ -374,7 +374,8 @@ __device__ __forceinline__ void scan_load(ScanBuf<ROWS, VEC>& b, const uint64_t*
 //  AccLimb: for moduli < 2^50 the residues are split at bit 28 and the four
 //    partial products accumulate in three 64-bit sums with no carry handling at
 //    all (4 v_mad_u64_u32 per product, ~3x fewer VALU ops than the 128-bit path);
-//    exact for up to kLimbLazy terms: s00 < 128 * 2^56, s01 < 128 * 2^51, s11 < 128 * 2^44.
+//    exact for up to kLimbLazy terms: s00 < 128 * 2^56 + q (a folded sum is carried on as a residue), s01 < 128 * 2^51,
+//    s11 < 128 * 2^44 (tests/test_scan_fold_model.py, at the residues whose limbs are largest).
 constexpr uint32_t kLimbLazy = 128;
 
 struct AccWide {

@@ -12,7 +12,7 @@
 //     B tile = 64 columns x 16 (query, comp) pairs of digit b of the selectors
 //     T[a+b] += A_a * B_b      (the K accumulation and the digit diagonal share one int32 accumulator)
 // then value = sum_s T[s] 2^(8 s) is folded and reduced modulo q_j exactly.  All arithmetic is integer
-// and exact (|T| < L * 2^14 * 64 * KS < 2^25), so replies stay bit-identical to the reference.  The
+// and exact (|T| <= (L - 1) * 2^14 * 64 * KS < 2^25.2, see kBiasBits), so replies stay bit-identical to the reference.  The
 // database is stored ONCE in the operand layout of the instruction, which also shrinks it from
 // 8 to L bytes per residue (5 for the 36-bit moduli of N = 4096): the pass reads 0.74x the bytes of
 // the u64 layout (incl. padding to 16 x 16 tiles) and serves up to 8 queries.
@@ -342,6 +342,17 @@ struct ChunkPlan {
   uint32_t nchunks;
 };
 
+// The integer fold's magnitudes (tests/scan_fold_model.py restates the fold; tests/test_scan_fold_model.py asserts every
+// figure here over the sign-coherent worst-case operands of every instantiated variant and modulus size):
+//   |T[s]| <= (L - 1) 2^14 * 64 KS < 2^25.2   a top digit is at most 64 in magnitude (residues are centred and below
+//             2^(8 L - 1); 8 as a nibble), so the two top-digit pairs of a diagonal weigh no more than one pair of low digits
+//   |group| <= |T| (2^40 - 1) / 255 < 2^57.2  five diagonals, 8 bits apart
+//   bias = q << (kBiasBits - bits(q)): a multiple of q with 2^58 <= bias < 2^59, so 0 < group + bias < 2^59.4 whatever
+//             the size of q inside its bit count.  (One bit lower -- 2^57 <= bias -- a group of 6 digits over 412 or more
+//             columns could reach -2^57.13 < -bias for a prime just above 2^(bits - 1): the cast wrapped.)
+//   reduce128 takes any 128-bit value; what it is given here, (top group << 40) + group at the most, is < 2^99.5
+constexpr int kBiasBits = 59;
+
 // grid = sum of the plan's workgroups; block = NW waves (wave w <-> slot j0 + w).  NW = 8: two waves per SIMD, 256
 // registers each -- selectors of up to 3 k-steps; NW = 4 ("wide"): one wave per SIMD with the whole 512-entry register
 // file (VGPRs + AGPRs: MFMA operands may live in either), selectors of up to 7 k-steps = 28 column groups in registers,
@@ -455,8 +466,8 @@ scan_mfma_kernel(const DevParams* __restrict__ P, const uint8_t* __restrict__ db
     const ModConst m = P->mod[mi];
     const uint32_t nx = 2u * grp.nq[gi];
     uint64_t* const obase = grp.out[gi] + ch * chunk_stride;
-    // multiple of q that makes every 40-bit group positive: 2^57 <= bias < 2^58, |group| < 2^56.1
-    const uint64_t bias = m.q << (58 - (64 - __builtin_clzll(m.q)));
+    // multiple of q that makes every 40-bit group positive: 2^58 <= bias < 2^59, |group| < 2^57.2 (kBiasBits)
+    const uint64_t bias = m.q << (kBiasBits - (64 - __builtin_clzll(m.q)));
     [[maybe_unused]] const F64Mod fm{P->tab[mi].qd, P->tab[mi].qinvd};
     [[maybe_unused]] const double fw0 = P->fold_w[mi][0], fw1 = P->fold_w[mi][1], fw2 = P->fold_w[mi][2];
     const uint8_t* abase = dbp + (size_t)(j0 + w) * slab + chunk_base;
@@ -519,7 +530,7 @@ scan_mfma_kernel(const DevParams* __restrict__ P, const uint8_t* __restrict__ db
 #pragma unroll
             for (int s = gq * 5; s < gq * 5 + 5 && s < NS; ++s) G += (int64_t)T[s][i] << (8 * (s - gq * 5));
             if (gq == NG - 1 && NG > 1) {
-              r = (uint64_t)(G + (int64_t)bias);   // top group: < 2^58, reduced together with the next one (bias = 0 mod q)
+              r = (uint64_t)(G + (int64_t)bias);   // top group: < 2^59.4, reduced together with the next one (bias = 0 mod q)
             } else {
               const u128 v = ((u128)r << 40) + (uint64_t)(G + (int64_t)bias);
               r = reduce128((uint64_t)v, (uint64_t)(v >> 64), m);

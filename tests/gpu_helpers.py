@@ -35,6 +35,31 @@ def chain(N, data_bits, special_bits=None):
     return oracle.coeff_modulus_create(N, data + [max(data) if special_bits is None else special_bits])
 
 
+def smallest_primes(N, bits, count):
+    """The `count` smallest NTT-friendly primes (== 1 mod 2N) of exactly `bits` bits, ascending: the ones just above
+    2^(bits - 1), where a constant derived from the bit count alone (a shift of q up to a fixed size) is smallest."""
+    found, v = [], (1 << (bits - 1)) + 1
+    while len(found) < count and v < (1 << bits):
+        if oracle.is_prime(v):
+            found.append(v)
+        v += 2 * N
+    if len(found) < count:
+        raise ValueError("not enough primes")
+    return found
+
+
+def chain_low(N, data_bits, special_bits=None):
+    """chain()'s counterpart at the other end of every size: the SMALLEST NTT-friendly primes of `data_bits` bits (an int =
+    two of that size, or a list), the special prime -- the largest of its size -- after them."""
+    data = [data_bits, data_bits] if isinstance(data_bits, int) else list(data_bits)
+    need = {}
+    for b in data:
+        need[b] = need.get(b, 0) + 1
+    table = {b: smallest_primes(N, b, cnt) for b, cnt in need.items()}
+    special = oracle.coeff_modulus_create(N, [max(data) if special_bits is None else special_bits])
+    return [table[b].pop(0) for b in data] + special
+
+
 def structured_patterns(q, N, rng):
     """Deterministic worst-case residue vectors of one modulus: [(name, uint64[N])].  Random inputs stay a factor
     sqrt(N) inside the worst-case bounds of the transforms; these sit on them."""

@@ -12,8 +12,8 @@ shows it on a model).  The inputs here sit on the bounds:
   * the rounding of the special-prime division, with the accumulator chosen coefficient by coefficient next to 0, p / 2
     and p - 1, against floor((CRT(r) + floor(p / 2)) / p) in Python integers;
   * scan selectors on the boundaries of the digit decomposition for every digit count and top-digit form, against the
-    oracle's db_multiply.  (The database side cannot be set residue by residue: plaintexts enter as coefficients below
-    t and the server lifts and transforms them.)"""
+    oracle's db_multiply.  (The database side is random here; tests/test_gpu_scan_worst_case.py sets it through constant
+    plaintexts and takes the accumulators of the scan to their bounds.)"""
 import numpy as np
 import pytest
 
@@ -293,8 +293,10 @@ WIDEST = [("L5 nibble", 4096, 36, 5, True, 440), ("L5 byte", 4096, 39, 5, False,
 def test_scan_with_every_selector_at_one_extreme_residue(monkeypatch, label, N, bits, L, nibble, cols):
     """All selectors equal to the same extreme residue -- vmax(L), the largest value the asymmetric centring keeps
     positive, and vmax(L) + 1, the most negative one; for moduli too wide for the nibble form the centred extremes
-    floor(q / 2) and floor(q / 2) + 1 as well -- over the widest chunk: the int32 sums of digit products are at the
-    top of their budget (every term of a digit pair has the same selector digit)."""
+    floor(q / 2) and floor(q / 2) + 1 as well -- over the widest chunk.  Only the selector side is extreme: the database
+    is the transform of random bytes, so the digit products of a row sum add like a random walk and the int32 sums stay
+    near 2^19, far below their bound (the groups and fp64 chunks likewise).  tests/test_gpu_scan_worst_case.py makes both
+    sides coherent and reaches the bounds."""
     import torch
     s = setup_with_dims(0, 2048, [9, cols], N=N, plain_bits=24, moduli=chain(N, bits))
     p, k = s.params, s.orc.k
