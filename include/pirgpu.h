@@ -110,6 +110,22 @@ typedef struct pirgpu_params {
    * InvalidArgument, and the multi-GPU entry points (packed exchange, pirgpu_slots_*, pirgpu_reduce_fixup*, the device
    * reply copies) return FailedPrecondition on such a context.  Capacities given in ciphertexts stay in ciphertexts. */
   uint32_t result_primes;
+  /* Tables (not in the reference, whose PIRDatabase is one database): the context holds `tables` = T databases of exactly
+   * these parameters -- num_items, num_pt, dimensions and item size describe ONE of them -- and every query names, in the
+   * clear, the table it is answered from (pirgpu_query_use_table, pirgpu_batch_set_tables, pirgpu_process_request_table /
+   * _requests_tables).  Expansion, key sets, the batch pipeline and the workspace are shared; the scan reads the named
+   * table only; the reply is bit-identical to the reference's processQuery on the database made of that table's items
+   * alone (same ciphertext count, same words), and a query fails with Internal ("transparent") exactly when ITS table
+   * holds an all-zero plaintext.  0 and 1 both mean one table (every byte, status and reply as without the field).
+   * T > 1 is served by one GPU and from a staging copy: with a row shard, a slot shard, plaintexts_per_item > 1 or
+   * PIRGPU_CREATE_STREAMED_DB it is InvalidArgument, and T x num_pt must stay below 2^32.  All ring degrees, arithmetic
+   * flavours, d = 1, 2, 3, both scan families, key sets and result_primes work with it.  Indices at this ABI are
+   * table-major then: plaintext table * num_pt + pt (pirgpu_db_load_coeffs, pirgpu_db_read_plaintext,
+   * pirgpu_db_update_plaintexts), item table * num_items + i (pirgpu_db_update_items; pirgpu_db_load_items takes all
+   * T x num_items items); pirgpu_db_size and pirgpu_zero_plaintexts count all tables, pirgpu_scan_bytes one table,
+   * pirgpu_db_memory the whole allocation (table t's operand layout is the bytes [t, t + 1) x out[0] / T of it).
+   * DESIGN.md section 6.5. */
+  uint32_t tables;
 } pirgpu_params;
 
 /* PIRContext::Create + PIRDatabase::Create(params) (reference context.cpp:37-50,
@@ -146,6 +162,11 @@ const char* pirgpu_create_error(void);
  * item-major; must equal params.num_items.  Bit packing, plain lift and forward
  * NTT all run on the device; the encoded database stays resident in HBM. */
 int pirgpu_db_load_items(pirgpu_ctx* ctx, const uint8_t* items, uint64_t num_items, uint32_t bytes_per_item);
+/* Tables: loads or reloads table `table` alone (num_items == params.num_items items of it) and leaves the others as they
+ * are; a query on a loaded table is answered while other tables are still empty (FailedPrecondition on those).  On a
+ * context without tables, table 0 is the database.  Waits for the work queued on the context before it overwrites. */
+int pirgpu_db_load_table_items(pirgpu_ctx* ctx, uint32_t table, const uint8_t* items, uint64_t num_items,
+                               uint32_t bytes_per_item);
 /* PIRDatabase::populate from already-encoded plaintexts (the IntegerEncoder path,
  * reference database.cpp:60-82): coeffs = n_pt x N coefficients, each < t,
  * zero padded; plaintext indices [first_pt, first_pt + n_pt). */
@@ -193,6 +214,9 @@ int pirgpu_set_transparent_policy(pirgpu_ctx* ctx, int allow);
  * collective has run: FailedPrecondition (database not fully loaded), Internal (transparent), else 0. */
 uint64_t pirgpu_zero_plaintexts(const pirgpu_ctx* ctx);
 int pirgpu_set_remote_zero_plaintexts(pirgpu_ctx* ctx, uint64_t count);
+/* Tables: identically-zero plaintexts of ONE table -- what decides the transparent-ciphertext failure of the queries that
+ * name it (pirgpu_zero_plaintexts keeps counting the whole context); 0 for a table out of range. */
+uint64_t pirgpu_table_zero_plaintexts(const pirgpu_ctx* ctx, uint32_t table);
 int pirgpu_check_ready(pirgpu_ctx* ctx);
 /* Test hook: read back one encoded plaintext [k][N] (NTT form) from HBM (wide items: pt_index = plane * num_pt + pt). */
 int pirgpu_db_read_plaintext(pirgpu_ctx* ctx, uint64_t pt_index, uint64_t* out);
@@ -245,6 +269,25 @@ int pirgpu_keyset_set_keys(pirgpu_ctx* ctx, uint32_t slot, uint32_t n, const uin
 int pirgpu_query_use_keyset(pirgpu_ctx* ctx, uint32_t slot);
 int pirgpu_batch_set_keysets(pirgpu_ctx* ctx, const uint32_t* slots, uint32_t count);
 int pirgpu_keyset_stats(pirgpu_ctx* ctx, uint64_t stats[4]);
+
+/* Tables (pirgpu_params.tables resolved: at least 1) and the table a query is answered from.
+ *   query_use_table   table for pirgpu_process_query / query_run / multiply and pirgpu_check_ready; sticky like
+ *                     pirgpu_query_use_keyset, default 0.
+ *   batch_set_tables  one table per staged query of the batch (after pirgpu_batch_stage, which resets them to the
+ *                     selected table for all); pirgpu_batch_run_selectors uses them when they were set for as many
+ *                     queries as it is given.  The batch is served ordered by table -- equal tables share their pass
+ *                     over that table -- and every reply lands at its query's own index: the caller never sees the order.
+ * A table >= pirgpu_tables is InvalidArgument before anything is queued or changed.  A batch fails as a whole
+ * (FailedPrecondition / Internal) when one of its tables is not fully loaded / holds an all-zero plaintext. */
+uint32_t pirgpu_tables(const pirgpu_ctx* ctx);
+int pirgpu_query_use_table(pirgpu_ctx* ctx, uint32_t table);
+int pirgpu_batch_set_tables(pirgpu_ctx* ctx, const uint32_t* tables, uint32_t count);
+/* Test hook (no context, no device): the order and the runs the batch pipeline forms for `count` queries naming these
+ * tables, with groups of `group` queries: order[i] = the query served at position i (a stable sort by table);
+ * run r = the positions [run_begin[r], run_begin[r + 1]) -- one table, inside one group.  order holds count entries,
+ * run_begin count + 1, of which *n_runs + 1 are written. */
+int pirgpu_plan_table_runs(const uint32_t* tables, uint32_t count, uint32_t group, uint32_t* order, uint32_t* run_begin,
+                           uint32_t* n_runs);
 
 /* PIRServer::processQuery minus (de)serialisation (reference server.cpp:173-195):
  * query = nq ciphertexts (coefficient form), reply = reply_count ciphertexts
@@ -310,7 +353,9 @@ int pirgpu_batch_fetch(pirgpu_ctx* ctx, uint64_t* replies, uint64_t reply_capaci
 int pirgpu_batch_set_host_replies(pirgpu_ctx* ctx, uint64_t* pinned_host, uint64_t capacity);
 /* Blocks until the NEXT group of the batch just run has its replies in that host buffer and reports how many leading
  * queries are complete (*ready; the batch's size once every group has been reported): the caller can serialise replies
- * [previous ready, *ready) while the later groups are still being computed. */
+ * [previous ready, *ready) while the later groups are still being computed.  (A batch served ordered by table,
+ * pirgpu_batch_set_tables, finishes its queries out of submission order: *ready is then the number of LEADING queries
+ * complete so far and may stay where it was from one group to the next.) */
 int pirgpu_batch_next_host_replies(pirgpu_ctx* ctx, uint32_t* ready);
 /* Multi-GPU, query-parallel expansion (not in the reference).  batch_expand runs
  * only oblivious_expansion + the selector NTT for the staged queries [first, first+count) and writes
@@ -457,6 +502,14 @@ int pirgpu_process_request(pirgpu_ctx* ctx, const uint8_t* request, size_t reque
  * layer uses (pinned, one pair per batch set). */
 int pirgpu_process_requests(pirgpu_ctx* ctx, uint32_t n, const uint8_t* const* requests, const size_t* request_lens,
                             uint8_t** responses, size_t* response_lens, int* status);
+/* The same two entries on a context with tables: request(s) answered from `table` / request i from tables[i] (every
+ * query of a request goes to its request's table; a table out of range fails that request with InvalidArgument).  The
+ * request and response bytes are the reference's, unchanged: the table travels beside them, not in them.
+ * pirgpu_process_request(s) mean table 0. */
+int pirgpu_process_request_table(pirgpu_ctx* ctx, uint32_t table, const uint8_t* request, size_t request_len,
+                                 uint8_t** response, size_t* response_len);
+int pirgpu_process_requests_tables(pirgpu_ctx* ctx, uint32_t n, const uint8_t* const* requests, const size_t* request_lens,
+                                   const uint32_t* tables, uint8_t** responses, size_t* response_lens, int* status);
 /* Message of request i of the calling thread's last pirgpu_process_requests / _end call ("" if it succeeded). */
 const char* pirgpu_request_error(uint32_t i);
 /* The same call in two halves, for ONE calling thread that wants two calls in flight (the reference's harness calls
@@ -503,7 +556,9 @@ int pirgpu_scan_info(pirgpu_ctx* ctx, uint32_t info[8]);
 /* Options by name (case-insensitive), e.g. "scan_mfma" (0 keeps the 64-bit multiply-accumulate scan for d >= 2),
  * "scan_mfma_wide" (0 / 1 forces the 8-wave / 4-wave scan kernel), "upper_blocks", "fuse_last", "last_ntt",
  * "tree40", "sel_f64", "split_upper", "loop_transforms" (0: one transform per workgroup everywhere),
- * "scan_mfma_wgs_batch" (workgroups of a database pass that shares the chip with another group) -- DESIGN.md section 6
+ * "scan_mfma_wgs_batch" (workgroups of a database pass that shares the chip with another group), "tables_one_launch"
+ * (0: one database-pass launch per run of equal tables instead of one per batch group), "scan_launches" (a counter: the
+ * database-pass launches the batch pipeline queued so far; setting it overwrites the count) -- DESIGN.md section 6
  * lists them.  A name that was not set falls back to the environment variable
  * PIRGPU_<NAME> (the A/B scripts under tools/ use that), then to the built-in default; get_option returns -1 for
  * "built-in default".  Options that shape the workspace must be set before the context is first used

@@ -15,7 +15,8 @@ u64p = C.POINTER(C.c_uint64)
 u8p = C.POINTER(C.c_uint8)
 
 
-class Params(C.Structure):
+class ParamsLayout(C.Structure):
+    """pirgpu_params exactly as include/pirgpu.h declares it, `tables` (its last member) included."""
     _fields_ = [
         ("poly_modulus_degree", C.c_uint32),
         ("num_data_primes", C.c_uint32),
@@ -37,7 +38,26 @@ class Params(C.Structure):
         ("slot_end", C.c_uint32),
         ("plaintexts_per_item", C.c_uint32),
         ("result_primes", C.c_uint32),
+        ("tables", C.c_uint32),
     ]
+
+
+class Params(C.Structure):
+    """The struct every entry point is given.  Its declared fields end at result_primes; `tables`, the member the header
+    added behind it, occupies what used to be the struct's tail padding (same size, same offsets: a caller that never
+    heard of tables passes 0 there, which means one table) and is mirrored as a property over those four bytes."""
+    _fields_ = ParamsLayout._fields_[:-1]
+
+    @property
+    def tables(self) -> int:
+        return C.c_uint32.from_address(C.addressof(self) + ParamsLayout.tables.offset).value
+
+    @tables.setter
+    def tables(self, value: int) -> None:
+        C.c_uint32.from_address(C.addressof(self) + ParamsLayout.tables.offset).value = int(value)
+
+
+assert C.sizeof(Params) == C.sizeof(ParamsLayout) and ParamsLayout.tables.offset + 4 <= C.sizeof(Params)
 
 
 def make_params(params, device: int = 0, shard=None, slots=None) -> Params:
@@ -61,6 +81,7 @@ def make_params(params, device: int = 0, shard=None, slots=None) -> Params:
     p.use_ciphertext_multiplication = 1 if params.use_ciphertext_multiplication else 0
     p.plaintexts_per_item = getattr(params, "plaintexts_per_item", 1)
     p.result_primes = getattr(params, "result_primes", 0)
+    p.tables = getattr(params, "tables", 0)
     p.device = device
     if shard is not None:
         b, e = int(shard[0]), int(shard[1])
@@ -81,6 +102,18 @@ SIGNATURES = {
     "pirgpu_create_error": (C.c_char_p, []),
     "pirgpu_db_load_items": (C.c_int, [C.c_void_p, u8p, C.c_uint64, C.c_uint32]),
     "pirgpu_db_load_coeffs": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, u64p]),
+    "pirgpu_db_load_table_items": (C.c_int, [C.c_void_p, C.c_uint32, u8p, C.c_uint64, C.c_uint32]),
+    "pirgpu_tables": (C.c_uint32, [C.c_void_p]),
+    "pirgpu_table_zero_plaintexts": (C.c_uint64, [C.c_void_p, C.c_uint32]),
+    "pirgpu_query_use_table": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "pirgpu_batch_set_tables": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32]),
+    "pirgpu_plan_table_runs": (C.c_int, [C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
+                                         C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "pirgpu_process_request_table": (C.c_int, [C.c_void_p, C.c_uint32, u8p, C.c_size_t, C.POINTER(C.c_void_p),
+                                               C.POINTER(C.c_size_t)]),
+    "pirgpu_process_requests_tables": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                 C.POINTER(C.c_uint32), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                 C.POINTER(C.c_int)]),
     "pirgpu_db_size": (C.c_uint64, [C.c_void_p]),
     "pirgpu_db_read_plaintext": (C.c_int, [C.c_void_p, C.c_uint64, u64p]),
     "pirgpu_db_memory": (C.c_int, [C.c_void_p, u64p]),

@@ -14,7 +14,8 @@
 //   [5]  C ABI: create / destroy, options, database loading (db_encode, db_pack), finalize
 //   [6]  C ABI: Galois keys, per-client key sets (handles with generations, pins, LRU)
 //   [7]  C ABI: single query, join / fork, test hooks
-//   [8]  batch pipeline: staging, lanes, expand_group_on_lane, batch_run_mfma (groups of 8 on two lanes)
+//   [8]  batch pipeline: staging, lanes, expand_group_on_lane, batch_run_mfma (groups of 8 on two lanes); contexts with
+//        tables: plan_table_runs (order by table, runs inside a group), scan_group_runs (one launch for all runs)
 //   [9]  multi-GPU entry points: u64 exchange, packed row shards, slot shards (pirgpu_slots_*), fix-up, pack40
 //   [10] measurement
 // The kernels are in kernels.hip, scan_mfma.hip, ntt_kernels.hip (+ ntt_core.h, arith.h); the wire level in wire.cpp.
@@ -90,6 +91,7 @@ struct DevScratch {
 struct Worker {
   hipStream_t stream = nullptr;
   uint32_t keyset = 0;               // key set of the query this worker currently holds
+  uint32_t table = 0;                // table its query named (contexts with tables; 0 otherwise)
   uint64_t *res_a = nullptr, *res_b = nullptr, *prod = nullptr, *dig = nullptr, *sv_ntt = nullptr;
   uint64_t* d_query = nullptr;
   uint32_t staged_nq = 0;
@@ -131,6 +133,7 @@ struct BatchLane {
   uint32_t head_next = 0;
   uint64_t *res_a = nullptr, *res_b = nullptr, *prod = nullptr, *dig = nullptr;
   uint8_t* selp = nullptr;
+  uint8_t* selp_runs = nullptr;      // contexts with tables: packed selectors of up to 8 runs of one group (one launch for all)
   hipEvent_t ev_scanned = nullptr;
   hipEvent_t ev_join = nullptr;      // pirgpu_join: everything queued on this lane so far
   // the multiply of a whole group runs on the lane's stream in these query-major buffers: one launch per kernel
@@ -195,6 +198,7 @@ struct BatchSet {
   bool batch_valid = false;
   std::vector<uint32_t> batch_keysets;      // key set INDEX per staged query (all 0 unless pirgpu_batch_set_keysets) ...
   std::vector<uint32_t> batch_keyset_gens;  // ... and the generation it had then: checked again when the batch is run
+  std::vector<uint32_t> batch_tables;       // table per staged query (contexts with tables; empty = all 0, pirgpu_batch_set_tables)
   // pirgpu_batch_stage_async: the queries arrive in pieces of kStagePiece queries on the main stream, one event each;
   // a group waits for the pieces that hold its queries instead of the whole upload
   std::vector<hipEvent_t> st_events;
@@ -238,6 +242,17 @@ struct pirgpu_ctx {
   // their usual rows with the same selectors, and level 0 keeps `planes` rows -- the reply -- instead of one
   uint32_t planes = 1;
   uint64_t plane_pad = 0;             // plaintext rows of d_db per plane (planes > 1)
+  // tables (pirgpu_params.tables): `tables` databases of these parameters behind one context, every
+  // query naming the one it is answered from.  A table is an outermost dimension that is selected IN THE CLEAR: in d_db
+  // table t occupies the rows [t, t + 1) * table_pad (padded to whole rows of the scanned matrix like a single database),
+  // in d_dbp it is a complete operand layout of its own at byte t * dbp_bytes().  Geometry, workspace, expansion and
+  // upper levels are those of ONE table; only the scan takes the table's base pointer.
+  uint32_t tables = 1;
+  uint64_t table_pad = 0;             // plaintext rows of d_db per table (tables > 1)
+  uint32_t cur_table = 0;             // table of the single-query entry points and test hooks (pirgpu_query_use_table)
+  std::vector<uint64_t> tbl_loaded, tbl_zero;   // per table: plaintexts loaded / identically zero (tables > 1)
+  std::vector<uint8_t> tbl_packed;    // per table: its operand layout is up to date (tables > 1)
+  uint64_t scan_launches = 0;         // database-pass launches of the batch pipeline so far (option SCAN_LAUNCHES reads it)
   uint32_t bits = 0;           // bits per coefficient for item packing
 
   int device = 0;
@@ -375,14 +390,19 @@ struct pirgpu_ctx {
 BatchSet& pirgpu_ctx::bs() { return sets[t_batch_set]; }
 
 // plaintexts this context must hold before it answers queries (all planes)
-static inline uint64_t held_pts(const pirgpu_ctx* c) { return (uint64_t)c->planes * (c->pt_end - c->pt_begin); }
+static inline uint64_t held_pts(const pirgpu_ctx* c) { return (uint64_t)c->tables * c->planes * (c->pt_end - c->pt_begin); }
 // plaintext rows of the matrix the scan and the upper levels walk: the shard, or planes x the padded plane
 static inline uint64_t matrix_pts(const pirgpu_ctx* c) {
   return c->planes > 1 ? (uint64_t)c->planes * c->plane_pad : c->pt_end - c->pt_begin;
 }
-// ABI plaintext index (plane-major: plane * num_pt + pt) -> row of d_db
+// ABI plaintext index (plane-major: plane * num_pt + pt; table-major: table * num_pt + pt) -> row of d_db
 static inline uint64_t db_row(const pirgpu_ctx* c, uint64_t index) {
+  if (c->tables > 1) return index / c->P * c->table_pad + index % c->P;
   return c->planes > 1 ? index / c->P * c->plane_pad + index % c->P : index - c->pt_begin;
+}
+// contexts with tables: the staging rows of table t
+static inline const uint64_t* table_db(const pirgpu_ctx* c, uint32_t t) {
+  return c->d_db ? c->d_db + (size_t)t * c->table_pad * c->k * c->N : nullptr;
 }
 // pirgpu_db_memory's peak: called wherever one of the counted sizes grows
 static inline void note_mem(pirgpu_ctx* c) {
@@ -590,10 +610,21 @@ bool all_zero_bytes(const uint8_t* p, size_t n) {
 // loaded[] per local plaintext: 0 = not loaded, 1 = loaded, 2 = loaded and identically zero
 void note_plaintext(pirgpu_ctx* c, uint64_t local, bool zero) {
   uint8_t& st = c->loaded[local];
+  if (c->tables > 1) {   // the same counts per table (local = table * num_pt + pt)
+    const uint64_t t = local / c->P;
+    if (!st) ++c->tbl_loaded[t];
+    if (st == 2) --c->tbl_zero[t];
+    if (zero) ++c->tbl_zero[t];
+  }
   if (!st) ++c->n_loaded;
   if (st == 2) --c->zero_pts;
   st = zero ? 2 : 1;
   if (zero) ++c->zero_pts;
+}
+
+// A query is answered once ITS database is complete: the whole context, or -- with tables -- the table it names.
+bool table_loaded(const pirgpu_ctx* c, uint32_t t) {
+  return c->tables > 1 ? c->tbl_loaded[t] == c->P : c->n_loaded == held_pts(c);
 }
 
 // Evaluator::multiply_plain throws logic_error("result ciphertext is transparent") when its result has an
@@ -601,11 +632,34 @@ void note_plaintext(pirgpu_ctx* c, uint64_t local, bool zero) {
 // soon as one database plaintext is identically zero; PIRDatabase::multiply maps it to InternalError
 // (reference database.cpp:308-315).  pirgpu_set_transparent_policy(ctx, 1) returns the mathematically defined
 // reply instead.
-void check_transparent(pirgpu_ctx* c) {
+void check_transparent(pirgpu_ctx* c, uint32_t table = 0) {
   // the reference fails every query as soon as ANY plaintext of the whole database is zero: a row shard also counts
-  // the zero plaintexts the other shards reported, so that all ranks of a sharded server take the same decision
-  if ((c->zero_pts || c->remote_zero_pts) && !c->allow_transparent)
-    throw Fail{PIRGPU_INTERNAL, "result ciphertext is transparent"};
+  // the zero plaintexts the other shards reported, so that all ranks of a sharded server take the same decision.
+  // Tables: the database of a query is the table it names -- the other tables' plaintexts do not count
+  const uint64_t zeros = c->tables > 1 ? c->tbl_zero[table] : c->zero_pts || c->remote_zero_pts;
+  if (zeros && !c->allow_transparent) throw Fail{PIRGPU_INTERNAL, "result ciphertext is transparent"};
+}
+
+// Contexts with tables: the order a batch is served in.  The queries are sorted by table (stable: equal tables keep their
+// submission order) so that equal tables meet in the same group of `group` queries; order[i] = the staged query served at
+// position i.  A RUN is a maximal stretch of positions with one table inside one group: run r covers the positions
+// [run_begin[r], run_begin[r + 1]) and is scanned against its table's operand layout.  Host only, no device state.
+struct TablePlan {
+  std::vector<uint32_t> order, run_begin;
+  bool identity = true;   // order[i] == i: the batch is served exactly as a batch without tables
+};
+TablePlan plan_table_runs(const uint32_t* tables, uint32_t count, uint32_t group) {
+  TablePlan tp;
+  tp.order.resize(count);
+  for (uint32_t i = 0; i < count; ++i) tp.order[i] = i;
+  std::stable_sort(tp.order.begin(), tp.order.end(), [&](uint32_t a, uint32_t b) { return tables[a] < tables[b]; });
+  group = std::max<uint32_t>(group, 1);
+  for (uint32_t i = 0; i < count; ++i) {
+    tp.identity = tp.identity && tp.order[i] == i;
+    if (i == 0 || i % group == 0 || tables[tp.order[i]] != tables[tp.order[i - 1]]) tp.run_begin.push_back(i);
+  }
+  tp.run_begin.push_back(count);
+  return tp;
 }
 
 void alloc_worker(pirgpu_ctx* c, Worker& w);
@@ -1109,7 +1163,16 @@ const uint64_t* scan_selectors(pirgpu_ctx* c, Worker& w) {
 bool mq_usable(pirgpu_ctx* c) { return c->scan_nsplit == 1 && c->scan_rows >= 1 && c->scan_cols >= 1; }
 
 // bytes of the operand-layout copy this context holds (its slots of every plaintext)
+// (contexts with tables: the bytes of ONE table's layout; table t starts t times that far into d_dbp)
 size_t dbp_bytes(const pirgpu_ctx* c) { return (size_t)c->nslots * c->mg.RT * c->mg.KG * c->mg.tile_bytes; }
+uint8_t* table_dbp(const pirgpu_ctx* c, uint32_t t) { return c->d_dbp ? c->d_dbp + (size_t)t * dbp_bytes(c) : nullptr; }
+
+// Contexts with tables serve one GPU: the multi-GPU steps (u64 and packed exchange, slot shards) do not name tables.
+void refuse_tables(const pirgpu_ctx* c) {
+  if (c->tables > 1)
+    throw Fail{PIRGPU_FAILED_PRECONDITION, "this context holds several tables (tables > 1): the multi-GPU entry points do "
+                                           "not serve them"};
+}
 
 // A slot shard holds 1 / G of every plaintext: it serves the pirgpu_slots_* step only.
 // Wide items are served by one GPU: the multi-GPU steps (packed row-shard exchange, slot shards) do not know planes.
@@ -1140,12 +1203,23 @@ void ensure_packed(pirgpu_ctx* c) {
   if (c->streamed)   // (its operand layout is valid from ensure_workspace on; there is no staging copy to pack from)
     throw Fail{PIRGPU_INTERNAL, "streamed database without its operand-layout copy"};
   if (!c->d_dbp) {
-    c->d_dbp = c->dalloc<uint8_t>(dbp_bytes(c));
-    c->dbp_alloc = dbp_bytes(c);
+    c->d_dbp = c->dalloc<uint8_t>(c->tables * dbp_bytes(c));
+    c->dbp_alloc = c->tables * dbp_bytes(c);
     note_mem(c);
   }
-  HIP_TRY(launch_db_pack(c->stream, c->dp, c->mg, c->d_db, c->d_dbp, c->scan_rows, c->scan_cols, c->k * c->N, c->slot0,
-                         c->nslots));
+  if (c->tables > 1) {
+    // every table is a complete layout of its own: the band kernel with table t's staging rows as its source and table
+    // t's layout as its destination.  Only the tables a load touched since are packed again
+    for (uint32_t t = 0; t < c->tables; ++t) {
+      if (c->tbl_packed[t]) continue;
+      HIP_TRY(launch_db_pack(c->stream, c->dp, c->mg, table_db(c, t), table_dbp(c, t), c->scan_rows, c->scan_cols,
+                             c->k * c->N, 0, c->nslots));
+      c->tbl_packed[t] = 1;
+    }
+  } else {
+    HIP_TRY(launch_db_pack(c->stream, c->dp, c->mg, c->d_db, c->d_dbp, c->scan_rows, c->scan_cols, c->k * c->N, c->slot0,
+                           c->nslots));
+  }
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->packed_valid = true;
 }
@@ -1210,7 +1284,7 @@ void pack_range(pirgpu_ctx* c, const uint64_t* d_enc, uint64_t l0, uint64_t n, D
 // out + q * scan_rows ciphertexts; `part` (query-major as well) holds the per-chunk sums of matrices wider than one chunk.
 void scan_group_mfma(pirgpu_ctx* c, hipStream_t st, uint8_t*& selp, const MfmaPtrs& col_sel, uint32_t n, uint64_t* out_base,
                      uint64_t* part, Worker* profiled, const uint8_t* packed = nullptr, bool sel_f64 = false,
-                     bool share_chip = false) {
+                     bool share_chip = false, uint32_t table = 0) {
   const uint32_t kN = c->k * c->N;
   const uint64_t words = (uint64_t)c->scan_rows * c->ctw;
   ensure_packed(c);
@@ -1239,8 +1313,9 @@ void scan_group_mfma(pirgpu_ctx* c, hipStream_t st, uint8_t*& selp, const MfmaPt
     }
     HIP_TRY(hipEventRecord(c->bscan_ev[2 * c->bscan_n], st));
   }
-  HIP_TRY(launch_scan_mfma(st, c->dp, c->mg, c->d_dbp, packed, out, out_qstride, n, c->scan_rows, kN, words, wgs,
+  HIP_TRY(launch_scan_mfma(st, c->dp, c->mg, table_dbp(c, table), packed, out, out_qstride, n, c->scan_rows, kN, words, wgs,
                            n > 1 ? (c->scan_f64_fold || c->scan_f64_fold_batch) : c->scan_f64_fold));
+  if (!profiled) ++c->scan_launches;
   if (timed) {
     HIP_TRY(hipEventRecord(c->bscan_ev[2 * c->bscan_n + 1], st));
     ++c->bscan_n;
@@ -1257,25 +1332,27 @@ void scan_on_device(pirgpu_ctx* c, Worker& w) {
   const uint32_t N = c->N, k = c->k;
   const size_t ctw = c->ctw;
   refuse_slot_shard(c);
-  if (c->n_loaded != held_pts(c))
-    throw Fail{PIRGPU_FAILED_PRECONDITION, "database not fully loaded"};
-  check_transparent(c);
+  if (!table_loaded(c, w.table))
+    throw Fail{PIRGPU_FAILED_PRECONDITION, c->tables > 1 ? "table " + std::to_string(w.table) + " not fully loaded"
+                                                         : std::string("database not fully loaded")};
+  check_transparent(c, w.table);
   if (c->pt_end == c->pt_begin) return;
   if (c->mfma_on && c->mfma_single) {
     MfmaPtrs col{};
     col.p[0] = scan_selectors(c, w);
-    scan_group_mfma(c, w.stream, w.selp, col, 1, scan_out(c, w), w.scan_part, &w);
+    scan_group_mfma(c, w.stream, w.selp, col, 1, scan_out(c, w), w.scan_part, &w, nullptr, false, false, w.table);
     return;
   }
   const uint64_t* sv_base = scan_selectors(c, w);
   uint64_t* base_out = scan_out(c, w);
+  const uint64_t* db = table_db(c, w.table);   // the 64-bit scans take the table as an offset into the staging copy
   if (c->mq_single && mq_usable(c)) {
-    HIP_TRY(launch_scan_mq(w.stream, c->dp, N, k, c->d_db, &sv_base, &base_out, 1, c->scan_rows, c->scan_cols,
+    HIP_TRY(launch_scan_mq(w.stream, c->dp, N, k, db, &sv_base, &base_out, 1, c->scan_rows, c->scan_cols,
                            c->mq_single_rows, c->mq_single_limb && c->scan_limb));
     return;
   }
   uint64_t* scan_out = c->scan_nsplit > 1 ? w.scan_part : base_out;
-  HIP_TRY(launch_scan(w.stream, c->dp, N, k, c->d_db, sv_base, scan_out, c->scan_rows, c->scan_cols, c->scan_npt,
+  HIP_TRY(launch_scan(w.stream, c->dp, N, k, db, sv_base, scan_out, c->scan_rows, c->scan_cols, c->scan_npt,
                       c->scan_nsplit, c->scan_cps, c->scan_rpt, c->scan_block, c->scan_limb));
   if (c->scan_nsplit > 1)
     HIP_TRY(launch_reduce_splits(w.stream, c->dp, w.scan_part, c->scan_nsplit, (uint64_t)c->scan_rows * ctw,
@@ -1405,6 +1482,7 @@ void run_staged(pirgpu_ctx* c, Worker& w, bool profile) {
                "Number of ciphertexts doesn't match number of items for oblivious expansion."};
   c->prof_cur = -1;
   w.keyset = current_keyset(c);
+  w.table = c->cur_table;
   // a batch group that borrowed this worker's selection vector (its multiply runs on a lane stream) must be done
   HIP_TRY(hipStreamWaitEvent(w.stream, w.ev_done, 0));
   if (profile) begin_profiled_run(c);
@@ -1527,6 +1605,32 @@ int pirgpu_create_ex(const pirgpu_params* p, uint32_t flags, pirgpu_ctx** out) {
         return bail(PIRGPU_INVALID_ARGUMENT, "plaintexts_per_item > 1 needs 0 < num_pt <= the product of the dimensions");
       c->plane_pad = c->stride[0];
     }
+    c->tables = std::max<uint32_t>(1, p->tables);
+    if (c->tables > 1) {
+      // one GPU, one plaintext per item at the most, a staging copy to pack every table from
+      if (c->sb != 0 || c->se != c->dims[0])
+        return bail(PIRGPU_INVALID_ARGUMENT, "tables > 1 is served by one GPU: a row shard (shard_begin / shard_end) of a "
+                                             "context with tables is not supported");
+      if (c->slot_sharded)
+        return bail(PIRGPU_INVALID_ARGUMENT, "tables > 1 is served by one GPU: a slot shard (slot_begin / slot_end) of a "
+                                             "context with tables is not supported");
+      if (c->planes > 1)
+        return bail(PIRGPU_INVALID_ARGUMENT, "tables > 1 with plaintexts_per_item > 1 is not supported (a table and a plane "
+                                             "both claim the outermost rows of the stored database)");
+      if (c->streamed)
+        return bail(PIRGPU_INVALID_ARGUMENT, "tables > 1 with PIRGPU_CREATE_STREAMED_DB is not supported: every table is "
+                                             "packed from the staging copy");
+      if (c->P == 0) return bail(PIRGPU_INVALID_ARGUMENT, "tables > 1 needs num_pt > 0");
+      const uint64_t cols = c->dims[c->d - 1];
+      c->table_pad = c->d == 1 ? c->P : ceil_div(c->P, cols) * cols;
+      // the table-major plaintext index tables * num_pt and the rows of the staging copy stay inside the 32-bit range the
+      // row / unit bookkeeping of loads and updates uses
+      if ((uint64_t)c->tables * c->table_pad >= (1ull << 32))
+        return bail(PIRGPU_INVALID_ARGUMENT, "tables x num_pt does not fit the plaintext index range (2^32)");
+      c->tbl_loaded.assign(c->tables, 0);
+      c->tbl_zero.assign(c->tables, 0);
+      c->tbl_packed.assign(c->tables, 0);
+    }
     c->rp = p->result_primes;
     if (c->rp >= k)
       return bail(PIRGPU_INVALID_ARGUMENT, "result_primes must be below num_data_primes (0 = keep every result at the full modulus)");
@@ -1550,12 +1654,15 @@ int pirgpu_create_ex(const pirgpu_params* p, uint32_t flags, pirgpu_ctx** out) {
     const uint64_t shard_pts = c->pt_end - c->pt_begin;
     // rows are padded with zero plaintexts to full length so the scan kernels are branch-free
     const uint64_t cols_last = c->dims[c->d - 1];
-    const uint64_t padded = c->planes > 1 ? matrix_pts(c) : c->d == 1 ? shard_pts : ceil_div(shard_pts, cols_last) * cols_last;
+    const uint64_t padded = c->tables > 1   ? c->tables * c->table_pad
+                            : c->planes > 1 ? matrix_pts(c)
+                            : c->d == 1     ? shard_pts
+                                            : ceil_div(shard_pts, cols_last) * cols_last;
     if (!c->streamed) {
       c->d_db = c->dalloc<uint64_t>(padded * k * N);
       c->db_bytes = std::max<uint64_t>(padded * k * N, 1) * 8;
       note_mem(c);
-      if (c->planes > 1)   // every plane is padded to the whole box of its dimensions
+      if (c->planes > 1 || c->tables > 1)   // every plane is padded to the whole box of its dimensions, every table to whole rows
         HIP_TRY(hipMemset(c->d_db, 0, padded * k * N * 8));
       else if (padded > shard_pts)
         HIP_TRY(hipMemset(c->d_db + shard_pts * k * N, 0, (padded - shard_pts) * k * N * 8));
@@ -1663,6 +1770,10 @@ static const struct { const char* name; bool early; } kOptions[] = {
     {"SCAN_MFMA", true}, {"SCAN_MFMA_WIDE", true}, {"SCAN_MFMA_TOP4", true}, {"SCAN_MFMA_NQ", true}, {"SCAN_MFMA_SINGLE", true},
     {"HEAD_LEVELS", true}, {"HEAD_MODE", true}, {"SCAN_F64_FOLD", true}, {"SCAN_F64_FOLD_BATCH", true}, {"LOOP_TRANSFORMS", true},
     {"SLOTS_SCAN_WGS", false}, {"SLOTS_GATHER_NTT", false}, {"SLOTS_SCAN_BLK_MAJOR", false}, {"DB_STREAM_MB", true},
+    // contexts with tables: 0 = one database-pass launch per run of equal tables instead of one per group (A/B);
+    // SCAN_LAUNCHES is a COUNTER, not a choice: get returns the database-pass launches the batch pipeline queued so far,
+    // set overwrites the count (0 to start over)
+    {"TABLES_ONE_LAUNCH", false}, {"SCAN_LAUNCHES", false},
 };
 
 int pirgpu_set_option(pirgpu_ctx* c, const char* name, int64_t value) {
@@ -1674,6 +1785,10 @@ int pirgpu_set_option(pirgpu_ctx* c, const char* name, int64_t value) {
       if (up != o.name) continue;
       if (o.early && c->ws_ready)
         return fail(c, PIRGPU_FAILED_PRECONDITION, "option " + up + " shapes the workspace: set it before the context is first used");
+      if (up == "SCAN_LAUNCHES") {
+        c->scan_launches = (uint64_t)std::max<int64_t>(0, value);
+        return PIRGPU_OK;
+      }
       c->opts[up] = value;
       if (up == "SCAN_MFMA_WGS_BATCH") c->scan_wgs_batch = (uint32_t)std::max<int64_t>(0, value);
       return PIRGPU_OK;
@@ -1691,6 +1806,7 @@ int pirgpu_get_option(pirgpu_ctx* c, const char* name, int64_t* value) {
       if (up == o.name) {
         bool present = false;
         *value = option(c, o.name, -1, &present);   // -1: not set anywhere, the built-in default applies
+        if (up == "SCAN_LAUNCHES") *value = (int64_t)c->scan_launches;
         return PIRGPU_OK;
       }
     return fail(c, PIRGPU_INVALID_ARGUMENT, "unknown option " + up);
@@ -1708,8 +1824,9 @@ int pirgpu_set_remote_zero_plaintexts(pirgpu_ctx* c, uint64_t n) {
 
 int pirgpu_check_ready(pirgpu_ctx* c) {
   return guarded(c, [&]() -> int {
-    if (c->n_loaded != held_pts(c)) return fail(c, PIRGPU_FAILED_PRECONDITION, "database not fully loaded");
-    check_transparent(c);
+    // (tables: what the next query on the table selected with pirgpu_query_use_table would fail with)
+    if (!table_loaded(c, c->cur_table)) return fail(c, PIRGPU_FAILED_PRECONDITION, "database not fully loaded");
+    check_transparent(c, c->cur_table);
     return PIRGPU_OK;
   });
 }
@@ -1759,7 +1876,8 @@ uint64_t pirgpu_scan_bytes(const pirgpu_ctx* cc) {
     return 0;
   }
   // bytes a single-query pass over the database must read: the operand-layout copy when that pass is the MFMA scan
-  return c->mfma_on && c->mfma_single ? (uint64_t)dbp_bytes(c) : held_pts(c) * c->k * c->N * 8;
+  // (tables: a query scans the table it names and nothing else)
+  return c->mfma_on && c->mfma_single ? (uint64_t)dbp_bytes(c) : held_pts(c) / c->tables * c->k * c->N * 8;
 }
 
 int pirgpu_ntt_mode(const pirgpu_ctx* c) { return c ? c->mode : -1; }
@@ -1795,13 +1913,47 @@ int pirgpu_scan_info(pirgpu_ctx* c, uint32_t info[8]) {
   });
 }
 
+// PIRDatabase::populate for one table of the context (the only one unless tables > 1): num_items == params.num_items
+// items into the plaintext rows of table `table`, whose loaded[] entries start at table * num_pt.
+static int load_table_items(pirgpu_ctx* c, uint32_t table, const uint8_t* items, uint64_t num_items, uint32_t bytes_per_item);
+
 int pirgpu_db_load_items(pirgpu_ctx* c, const uint8_t* items, uint64_t num_items, uint32_t bytes_per_item) {
   return guarded(c, [&]() -> int {
     const pirgpu_params& p = c->prm;
-    if (num_items != p.num_items)  // reference database.cpp:85-90
+    if (num_items != c->tables * p.num_items)  // reference database.cpp:85-90 (tables: all of them, table-major)
       return fail(c, PIRGPU_INVALID_ARGUMENT,
                   "Database size " + std::to_string(num_items) + " does not match params value " +
-                      std::to_string(p.num_items));
+                      std::to_string(c->tables * p.num_items));
+    for (uint32_t t = 0; t < c->tables; ++t) {
+      const int rc = load_table_items(c, t, items ? items + (size_t)t * p.num_items * bytes_per_item : nullptr, p.num_items,
+                                      bytes_per_item);
+      if (rc) return rc;
+    }
+    return PIRGPU_OK;
+  });
+}
+
+int pirgpu_db_load_table_items(pirgpu_ctx* c, uint32_t table, const uint8_t* items, uint64_t num_items,
+                               uint32_t bytes_per_item) {
+  return guarded(c, [&]() -> int {
+    if (table >= c->tables)
+      return fail(c, PIRGPU_INVALID_ARGUMENT, "table " + std::to_string(table) + " out of range (tables = " +
+                                                  std::to_string(c->tables) + ")");
+    if (num_items != c->prm.num_items)
+      return fail(c, PIRGPU_INVALID_ARGUMENT,
+                  "Database size " + std::to_string(num_items) + " does not match params value " +
+                      std::to_string(c->prm.num_items));
+    if (c->tables > 1) {   // a RELOAD overwrites rows that queued queries on this table may still read
+      sync_batch_streams(c);
+      HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return load_table_items(c, table, items, num_items, bytes_per_item);
+  });
+}
+
+static int load_table_items(pirgpu_ctx* c, uint32_t table, const uint8_t* items, uint64_t num_items, uint32_t bytes_per_item) {
+  {
+    const pirgpu_params& p = c->prm;
     if (bytes_per_item != p.bytes_per_item || p.items_per_plaintext == 0 || (!items && num_items))
       return fail(c, PIRGPU_INVALID_ARGUMENT, "item size does not match parameters");
     const uint64_t ipp = p.items_per_plaintext;
@@ -1812,6 +1964,9 @@ int pirgpu_db_load_items(pirgpu_ctx* c, const uint8_t* items, uint64_t num_items
     // (pack_range); the raw-byte upload buffer is sized to the same chunk
     const uint64_t kN = (uint64_t)c->k * c->N;
     if (!c->streamed) c->packed_valid = false;
+    if (c->tables > 1) c->tbl_packed[table] = 0;
+    const uint64_t row0 = (uint64_t)table * c->table_pad;   // first staging row / loaded[] entry of the table (0 without
+    const uint64_t idx0 = (uint64_t)table * c->P;           // tables)
     if (c->planes > 1) {
       // wide items: item i is uploaded once and the encode kernel cuts it into its planes -- plane j reads bytes
       // [j B, min((j + 1) B, bytes_per_item)) of it and writes plaintext row j * plane_pad + i
@@ -1874,10 +2029,10 @@ int pirgpu_db_load_items(pirgpu_ctx* c, const uint8_t* items, uint64_t num_items
         for (uint64_t i = 0; i < n; ++i) {  // all-zero plaintexts (host scan while the copy is in flight)
           const uint64_t p0 = std::min<uint64_t>((pt + i) * bytes_per_pt, total_bytes);
           const uint64_t p1 = std::min<uint64_t>((pt + i + 1) * bytes_per_pt, total_bytes);
-          note_plaintext(c, pt - c->pt_begin + i, all_zero_bytes(items + p0, p1 - p0));
+          note_plaintext(c, idx0 + pt - c->pt_begin + i, all_zero_bytes(items + p0, p1 - p0));
         }
         HIP_TRY(c->ops->db_encode(c->stream, c->mode, c->dp, c->k, nullptr, d_bytes, bytes_per_pt, b1 - b0, c->bits,
-                                  n, c->streamed ? d_enc : c->d_db + (pt - c->pt_begin) * c->k * c->N, 1, 0, 0));
+                                  n, c->streamed ? d_enc : c->d_db + (row0 + pt - c->pt_begin) * c->k * c->N, 1, 0, 0));
         if (c->streamed) pack_range(c, d_enc, pt - c->pt_begin, n, d_units);
         HIP_TRY(hipStreamSynchronize(c->stream));
       }
@@ -1887,16 +2042,16 @@ int pirgpu_db_load_items(pirgpu_ctx* c, const uint8_t* items, uint64_t num_items
     }
     HIP_TRY(hipFree(d_bytes));
     return PIRGPU_OK;
-  });
+  }
 }
 
 int pirgpu_db_load_coeffs(pirgpu_ctx* c, uint64_t first_pt, uint64_t n_pt, const uint64_t* coeffs) {
   return guarded(c, [&]() -> int {
-    if (first_pt + n_pt > c->planes * c->P || (!coeffs && n_pt))
+    if (first_pt + n_pt > (uint64_t)c->tables * c->planes * c->P || (!coeffs && n_pt))
       return fail(c, PIRGPU_INVALID_ARGUMENT, "plaintext range out of bounds");
     // (wide items: pt_begin = 0, pt_end = P, and the index runs over all planes, plane-major)
     const uint64_t lo = std::max(first_pt, c->pt_begin);
-    const uint64_t hi = c->planes > 1 ? first_pt + n_pt : std::min(first_pt + n_pt, c->pt_end);
+    const uint64_t hi = c->planes > 1 || c->tables > 1 ? first_pt + n_pt : std::min(first_pt + n_pt, c->pt_end);
     if (lo >= hi) return PIRGPU_OK;
     if (c->staging_released)
       return fail(c, PIRGPU_FAILED_PRECONDITION, "database staging was released by pirgpu_db_finalize; it cannot be reloaded");
@@ -1915,7 +2070,10 @@ int pirgpu_db_load_coeffs(pirgpu_ctx* c, uint64_t first_pt, uint64_t n_pt, const
     try {
       for (uint64_t pt = lo; pt < hi;) {
         // a piece never crosses a plane boundary: the rows of one plane are contiguous in d_db
-        uint64_t n = std::min<uint64_t>(std::min<uint64_t>(chunk, hi - pt), c->planes > 1 ? c->P - pt % c->P : chunk);
+        // (nor a table boundary: table-major indices, every table's rows contiguous)
+        uint64_t n = std::min<uint64_t>(std::min<uint64_t>(chunk, hi - pt),
+                                        c->planes > 1 || c->tables > 1 ? c->P - pt % c->P : chunk);
+        if (c->tables > 1) c->tbl_packed[pt / c->P] = 0;
         // (streamed: the first piece ends on a chunk boundary of the matrix, so that the later ones are whole row tiles)
         if (c->streamed) n = std::min<uint64_t>(n, chunk - db_row(c, pt) % chunk);
         HIP_TRY(hipMemcpyAsync(d_coeffs, coeffs + (pt - first_pt) * c->N, n * c->N * 8, hipMemcpyHostToDevice,
@@ -1961,7 +2119,8 @@ int pirgpu_db_finalize(pirgpu_ctx* c, int release_staging) {
 
 int pirgpu_db_read_plaintext(pirgpu_ctx* c, uint64_t pt_index, uint64_t* out) {
   return guarded(c, [&]() -> int {
-    if (pt_index < c->pt_begin || pt_index >= (c->planes > 1 ? c->planes * c->P : c->pt_end) || !out)
+    if (pt_index < c->pt_begin ||
+        pt_index >= (c->tables > 1 ? c->tables * c->P : c->planes > 1 ? c->planes * c->P : c->pt_end) || !out)
       return fail(c, PIRGPU_INVALID_ARGUMENT, "plaintext index outside this shard");
     uint64_t* stage = nullptr;
     HIP_TRY(hipMalloc((void**)&stage, (size_t)2 * c->k * c->N * 8));
@@ -1971,9 +2130,11 @@ int pirgpu_db_read_plaintext(pirgpu_ctx* c, uint64_t pt_index, uint64_t* out) {
         refuse_slot_shard(c);   // ... which a slot shard holds only 1 / G of
         if (!c->d_dbp)          // (a streamed context before its first load)
           throw Fail{PIRGPU_FAILED_PRECONDITION, "database not loaded: the operand-layout copy does not exist yet"};
-        const uint64_t local = db_row(c, pt_index);
+        // (tables: the position inside the table's own layout)
+        const uint64_t local = c->tables > 1 ? pt_index % c->P : db_row(c, pt_index);
         uint64_t* tmp = stage + (size_t)c->k * c->N;
-        HIP_TRY(launch_db_unpack(c->stream, c->dp, c->mg, c->d_dbp, tmp, (uint32_t)(local / c->scan_cols),
+        HIP_TRY(launch_db_unpack(c->stream, c->dp, c->mg, table_dbp(c, c->tables > 1 ? (uint32_t)(pt_index / c->P) : 0), tmp,
+                                 (uint32_t)(local / c->scan_cols),
                                  (uint32_t)(local % c->scan_cols), c->k * c->N));
         src = tmp;
       }
@@ -2040,8 +2201,12 @@ void require_loaded(pirgpu_ctx* c) {
     throw Fail{PIRGPU_FAILED_PRECONDITION, "database not fully loaded (the first load is pirgpu_db_load_items / _coeffs)"};
 }
 
-void apply_update(pirgpu_ctx* c, const std::vector<PtUpdate>& pts, const uint8_t* items, uint32_t item_bytes) {
+// Tables: `pts` lie in ONE table (apply_update_tables cuts the sorted list), whose operand layout the units index.
+void apply_update(pirgpu_ctx* c, const std::vector<PtUpdate>& pts, const uint8_t* items, uint32_t item_bytes,
+                  uint32_t table = 0) {
   const uint32_t N = c->N, kN = c->k * c->N;
+  uint8_t* const dbp = table_dbp(c, table);
+  const uint64_t table_row0 = (uint64_t)table * c->table_pad;   // 0 without tables
   // wide items: a touched plaintext is one whole plane of ONE item (items_per_plaintext = 1), nothing of the old
   // plaintext survives -- no fetch, no inverse transform, no splice: the plane's bytes are encoded like a first load
   const bool wide = items != nullptr && c->planes > 1;
@@ -2049,6 +2214,7 @@ void apply_update(pirgpu_ctx* c, const std::vector<PtUpdate>& pts, const uint8_t
   const uint64_t plane_bytes = (uint64_t)N * c->bits / 8;
   const uint64_t ipp = splice ? c->prm.items_per_plaintext : 0, bpp = wide ? plane_bytes : ipp * item_bytes;
   const bool to_packed = c->mfma_on && c->packed_valid && c->d_dbp;
+  if (c->tables > 1 && !to_packed) c->tbl_packed[table] = 0;   // the next ensure_packed packs this table again
   // chunks of at most 64 MB of device scratch (pirgpu_db_load_items' upload size) and 65535 units (grid.y)
   const uint64_t per_pt = (uint64_t)N * 8 + (uint64_t)kN * 8 + bpp + ipp + 8 + 4 + sizeof(DbUnit);
   const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>((64ull << 20) / per_pt, 65535));
@@ -2073,9 +2239,10 @@ void apply_update(pirgpu_ctx* c, const std::vector<PtUpdate>& pts, const uint8_t
     units.clear();
     for (uint64_t i = 0; i < n; ++i) {
       const uint64_t l = db_row(c, pts[b + i].local + c->pt_begin);   // row of d_db = position in the scanned matrix
-      loc[i] = l;
+      loc[i] = l;                                                      // (tables: table_row0 + the position in the table's)
       if (!to_packed) continue;
-      const uint32_t r = (uint32_t)(l / c->scan_cols), col = (uint32_t)(l % c->scan_cols), kg = col / 16;
+      const uint64_t lt = l - table_row0;
+      const uint32_t r = (uint32_t)(lt / c->scan_cols), col = (uint32_t)(lt % c->scan_cols), kg = col / 16;
       if (units.empty() || units.back().r != r || units.back().kg != kg) units.push_back(DbUnit{r, kg, 0u, (uint32_t)i});
       units.back().mask |= 1u << (col % 16);
     }
@@ -2106,7 +2273,7 @@ void apply_update(pirgpu_ctx* c, const std::vector<PtUpdate>& pts, const uint8_t
       if (c->d_db)
         HIP_TRY(launch_copy_rows(c->stream, c->d_db, d_coef, d_loc, nullptr, n, N, kN, N));
       else
-        HIP_TRY(launch_db_gather(c->stream, c->dp, c->mg, c->d_dbp, d_units, (uint32_t)units.size(), d_coef, N));
+        HIP_TRY(launch_db_gather(c->stream, c->dp, c->mg, dbp, d_units, (uint32_t)units.size(), d_coef, N));
       // (2) back to coefficients (residues < t < q_0 carry the plaintext exactly), (3) splice
       HIP_TRY(c->ops->ntt_batch(c->stream, c->mode, c->dp, d_coef, n, 1, 0, true));
       HIP_TRY(launch_db_splice(c->stream, c->dp, d_coef, N, d_img, d_upd, n, bpp, item_bytes, c->bits, d_nz));
@@ -2122,7 +2289,7 @@ void apply_update(pirgpu_ctx* c, const std::vector<PtUpdate>& pts, const uint8_t
       HIP_TRY(c->ops->db_encode(c->stream, c->mode, c->dp, c->k, d_coef, nullptr, 0, 0, c->bits, n, d_enc, 1, 0, 0));
     if (c->d_db) HIP_TRY(launch_copy_rows(c->stream, d_enc, c->d_db, nullptr, d_loc, n, kN, kN, kN));
     if (to_packed)
-      HIP_TRY(launch_db_pack_update(c->stream, c->dp, c->mg, d_enc, d_units, (uint32_t)units.size(), c->d_dbp, kN,
+      HIP_TRY(launch_db_pack_update(c->stream, c->dp, c->mg, d_enc, d_units, (uint32_t)units.size(), dbp, kN,
                                     c->slot0, c->nslots));
     if (splice) {
       nz.resize(n);
@@ -2133,6 +2300,18 @@ void apply_update(pirgpu_ctx* c, const std::vector<PtUpdate>& pts, const uint8_t
       note_plaintext(c, pts[b + i].local,
                      wide ? zero_pt[i] != 0 : splice ? nz[i] == 0
                             : all_zero_bytes(reinterpret_cast<const uint8_t*>(pts[b + i].coeffs), (size_t)N * 8));
+  }
+}
+
+// The sorted touched plaintexts of an update, table by table (without tables: one call).
+void apply_update_tables(pirgpu_ctx* c, const std::vector<PtUpdate>& pts, const uint8_t* items, uint32_t item_bytes) {
+  if (c->tables <= 1) return apply_update(c, pts, items, item_bytes);
+  for (size_t b = 0; b < pts.size();) {
+    const uint64_t t = pts[b].local / c->P;
+    size_t e = b;
+    while (e < pts.size() && pts[e].local / c->P == t) ++e;
+    apply_update(c, std::vector<PtUpdate>(pts.begin() + b, pts.begin() + e), items, item_bytes, (uint32_t)t);
+    b = e;
   }
 }
 
@@ -2150,17 +2329,19 @@ int pirgpu_db_update_items(pirgpu_ctx* c, uint64_t n, const uint64_t* item_indic
     if (!n) return PIRGPU_OK;
     if (!item_indices || !items) return fail(c, PIRGPU_INVALID_ARGUMENT, "null item indices or items");
     for (uint64_t i = 0; i < n; ++i)
-      if (item_indices[i] >= p.num_items)
+      if (item_indices[i] >= c->tables * p.num_items)
         return fail(c, PIRGPU_INVALID_ARGUMENT, "item index " + std::to_string(item_indices[i]) + " out of range (" +
-                                                    std::to_string(p.num_items) + " items)");
+                                                    std::to_string(c->tables * p.num_items) + " items)");
     if (c->slot_sharded && !c->d_db)
       return fail(c, PIRGPU_FAILED_PRECONDITION,
                   "this slot shard released its staging copy: it holds too little of each plaintext to keep the items "
                   "an update does not replace (pirgpu_db_update_plaintexts still works)");
     const uint64_t ipp = p.items_per_plaintext;
     std::map<uint64_t, uint64_t> last;   // item -> row of `items` (a later entry wins)
+    // (tables: item index = table * num_items + i -- ascending item indices are ascending (table, plaintext) pairs)
+    const uint64_t ni = c->tables > 1 ? p.num_items : UINT64_MAX;
     for (uint64_t i = 0; i < n; ++i) {
-      const uint64_t pt = item_indices[i] / ipp;
+      const uint64_t pt = item_indices[i] % ni / ipp;
       if (pt >= c->pt_begin && pt < c->pt_end) last[item_indices[i]] = i;   // other row shards' items are skipped
     }
     std::vector<PtUpdate> pts;
@@ -2173,13 +2354,14 @@ int pirgpu_db_update_items(pirgpu_ctx* c, uint64_t n, const uint64_t* item_indic
       last.clear();
     }
     for (const auto& e : last) {
-      const uint64_t local = e.first / ipp - c->pt_begin;
+      const uint64_t in_table = e.first % ni;
+      const uint64_t local = (c->tables > 1 ? e.first / ni * c->P : 0) + in_table / ipp - c->pt_begin;
       if (pts.empty() || pts.back().local != local) pts.push_back(PtUpdate{local});
-      pts.back().items.emplace_back((uint32_t)(e.first % ipp), e.second);
+      pts.back().items.emplace_back((uint32_t)(in_table % ipp), e.second);
     }
     if (pts.empty()) return PIRGPU_OK;
     quiesce(c);
-    apply_update(c, pts, items, bytes_per_item);
+    apply_update_tables(c, pts, items, bytes_per_item);
     return PIRGPU_OK;
   });
 }
@@ -2191,16 +2373,17 @@ int pirgpu_db_update_plaintexts(pirgpu_ctx* c, uint64_t n, const uint64_t* pt_in
     if (!pt_indices || !coeffs) return fail(c, PIRGPU_INVALID_ARGUMENT, "null plaintext indices or coefficients");
     const uint64_t t = c->prm.plain_modulus;
     for (uint64_t i = 0; i < n; ++i) {
-      if (pt_indices[i] >= c->planes * c->P)
+      if (pt_indices[i] >= (uint64_t)c->tables * c->planes * c->P)
         return fail(c, PIRGPU_INVALID_ARGUMENT, "plaintext index " + std::to_string(pt_indices[i]) + " out of range (" +
-                                                    std::to_string(c->planes * c->P) + " plaintexts)");
+                                                    std::to_string((uint64_t)c->tables * c->planes * c->P) + " plaintexts)");
       const uint64_t* row = coeffs + i * c->N;
       for (uint32_t x = 0; x < c->N; ++x)
         if (row[x] >= t) return fail(c, PIRGPU_INVALID_ARGUMENT, "coefficient not below the plain modulus");
     }
     std::map<uint64_t, uint64_t> last;   // local plaintext -> row of `coeffs` (a later entry wins)
     for (uint64_t i = 0; i < n; ++i)
-      if (c->planes > 1 || (pt_indices[i] >= c->pt_begin && pt_indices[i] < c->pt_end)) last[pt_indices[i] - c->pt_begin] = i;
+      if (c->planes > 1 || c->tables > 1 || (pt_indices[i] >= c->pt_begin && pt_indices[i] < c->pt_end))
+        last[pt_indices[i] - c->pt_begin] = i;
     std::vector<PtUpdate> pts;
     for (const auto& e : last) {
       pts.push_back(PtUpdate{e.first});
@@ -2208,7 +2391,7 @@ int pirgpu_db_update_plaintexts(pirgpu_ctx* c, uint64_t n, const uint64_t* pt_in
     }
     if (pts.empty()) return PIRGPU_OK;
     quiesce(c);
-    apply_update(c, pts, nullptr, 0);
+    apply_update_tables(c, pts, nullptr, 0);
     return PIRGPU_OK;
   });
 }
@@ -2482,6 +2665,57 @@ int pirgpu_batch_set_keysets(pirgpu_ctx* c, const uint32_t* slots, uint32_t coun
     c->bs().batch_keyset_gens = std::move(gens);
     return PIRGPU_OK;
   });
+}
+
+uint32_t pirgpu_tables(const pirgpu_ctx* c) { return c ? c->tables : 0; }
+
+uint64_t pirgpu_table_zero_plaintexts(const pirgpu_ctx* cc, uint32_t table) {
+  pirgpu_ctx* c = const_cast<pirgpu_ctx*>(cc);
+  if (!c) return 0;
+  std::lock_guard<std::recursive_mutex> lock(c->mu);
+  if (table >= c->tables) return 0;
+  return c->tables > 1 ? c->tbl_zero[table] : c->zero_pts;
+}
+
+int pirgpu_query_use_table(pirgpu_ctx* c, uint32_t table) {
+  return guarded(c, [&]() -> int {
+    if (table >= c->tables)
+      return fail(c, PIRGPU_INVALID_ARGUMENT, "table " + std::to_string(table) + " out of range (tables = " +
+                                                  std::to_string(c->tables) + ")");
+    c->cur_table = table;
+    return PIRGPU_OK;
+  });
+}
+
+// wire layer: the selection read and put back around a request (like pirgpu_keyset_selection_get / _set)
+uint32_t pirgpu_current_table(pirgpu_ctx* c) {
+  if (!c) return 0;
+  std::lock_guard<std::recursive_mutex> lock(c->mu);
+  return c->cur_table;
+}
+
+int pirgpu_batch_set_tables(pirgpu_ctx* c, const uint32_t* tables, uint32_t count) {
+  return guarded(c, [&]() -> int {
+    if (!tables || count != c->bs().staged_count) return fail(c, PIRGPU_INVALID_ARGUMENT, "one table per staged query");
+    for (uint32_t i = 0; i < count; ++i)
+      if (tables[i] >= c->tables)
+        return fail(c, PIRGPU_INVALID_ARGUMENT, "table " + std::to_string(tables[i]) + " of query " + std::to_string(i) +
+                                                    " out of range (tables = " + std::to_string(c->tables) + ")");
+    c->bs().batch_tables.assign(tables, tables + count);
+    return PIRGPU_OK;
+  });
+}
+
+// Test hook, no context and no device: the order and the runs the batch pipeline forms for these tables with groups of
+// `group` queries (plan_table_runs).  order[count]; run_begin[count + 1], of which *n_runs + 1 entries are written.
+int pirgpu_plan_table_runs(const uint32_t* tables, uint32_t count, uint32_t group, uint32_t* order, uint32_t* run_begin,
+                           uint32_t* n_runs) {
+  if ((!tables && count) || !order || !run_begin || !n_runs || group == 0) return PIRGPU_INVALID_ARGUMENT;
+  const TablePlan tp = plan_table_runs(tables, count, group);
+  std::copy(tp.order.begin(), tp.order.end(), order);
+  std::copy(tp.run_begin.begin(), tp.run_begin.end(), run_begin);
+  *n_runs = (uint32_t)tp.run_begin.size() - 1;
+  return PIRGPU_OK;
 }
 
 int pirgpu_keyset_stats(pirgpu_ctx* c, uint64_t stats[4]) {
@@ -2859,6 +3093,7 @@ int pirgpu_multiply(pirgpu_ctx* c, const uint64_t* sv, uint64_t sv_count, uint64
     c->prof_cur = -1;
     w.sv_cur = nullptr;
     w.sv_rows = nullptr;
+    w.table = c->cur_table;
     multiply_on_device(c, w);
     HIP_TRY(hipMemcpyAsync(reply, w.lvl[0], c->reply_cts * c->rctw * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2929,6 +3164,7 @@ static int batch_stage_impl(pirgpu_ctx* c, const uint64_t* queries, uint32_t nq,
     b.staged_count = count;
     b.batch_keysets.assign(count, 0);   // pirgpu_batch_set_keysets assigns other clients' key sets
     b.batch_keyset_gens.assign(count, 0);
+    b.batch_tables.clear();             // pirgpu_batch_set_tables names other tables than the selected one
     b.batch_valid = false;
     return PIRGPU_OK;
   });
@@ -2948,6 +3184,7 @@ int pirgpu_batch_unstage(pirgpu_ctx* c) {
     b.staged_count = 0;
     b.batch_keysets.clear();
     b.batch_keyset_gens.clear();
+    b.batch_tables.clear();
     b.st_pieces = 0;
     return PIRGPU_OK;
   });
@@ -3046,8 +3283,10 @@ static void ensure_head_slot(pirgpu_ctx* c, HeadSlot& hs) {
 // sv_dst (optional): the selection vector of query q goes to sv_dst + q * dim_sum ciphertexts (caller-owned memory that
 // outlives the members' buffers: the slot-sharded step keeps its row selectors there for two steps) instead of the
 // members' own buffers.
+// qidx (optional; batches ordered by table): the staged query each member answers -- member q is query qidx[q] of the
+// batch instead of first + q, and the roots are imported one query at a time.
 static void expand_group_on_lane(pirgpu_ctx* c, BatchLane& ln, Worker* const* members, uint32_t B, uint32_t first,
-                                 bool sel_f64 = false, uint64_t* sv_dst = nullptr) {
+                                 bool sel_f64 = false, uint64_t* sv_dst = nullptr, const uint32_t* qidx = nullptr) {
   const uint32_t N = c->N, k = c->k;
   const uint32_t nq = c->dim_sum / N + 1;
   const size_t ctw = c->ctw, qwords = (size_t)nq * ctw;
@@ -3059,24 +3298,38 @@ static void expand_group_on_lane(pirgpu_ctx* c, BatchLane& ln, Worker* const* me
   // batch gains nothing from it (5 325-5 408 against 5 379-5 433 queries/s, same box) and keeps the plain path
   const bool use_head = nq == 1 && B > 1 && c->head_levels > 0 && (c->head_mode == 2 || (c->head_mode == 1 && c->bs().st_pieces > 0)) &&
                         hm::ceil_log2((uint32_t)std::min<uint64_t>(c->dim_sum, N)) >= c->head_levels + 2;
-  if (!use_head) wait_staged(c, ln.stream, first, B);
+  // (a permuted group's queries may lie in any piece of the upload: it waits for all of them)
+  const uint32_t ws_first = qidx ? 0 : first, ws_n = qidx ? c->bs().staged_count : B;
+  if (!use_head) wait_staged(c, ln.stream, ws_first, ws_n);
+  // the B query ciphertexts, gathered side by side out of the staged batch, become the roots of the B interleaved trees:
+  // one strided import launch for consecutive queries (no separate 2-D copy), one launch per query for permuted ones
+  auto import_roots = [&](hipStream_t st, uint64_t* dst, uint32_t qc) {
+    if (!qidx) {
+      HIP_TRY(launch_tree_convert(st, c->dp, c->mode, c->bs().d_bquery + (size_t)first * qwords + (size_t)qc * ctw, dst,
+                                  (uint64_t)B * ctw, true, ctw, qwords));
+      return;
+    }
+    for (uint32_t q = 0; q < B; ++q)
+      HIP_TRY(launch_tree_convert(st, c->dp, c->mode, c->bs().d_bquery + (size_t)qidx[q] * qwords + (size_t)qc * ctw,
+                                  dst + (size_t)q * ctw, ctw, true));
+  };
   for (uint32_t qc = 0; qc < nq && remaining; ++qc) {
     const uint32_t slots = (uint32_t)std::min<uint64_t>(remaining, N);
     MfmaPtrs dst{};
     uint32_t ksets[kMaxMfmaQueries];   // every query of the group is switched with its own client's keys
     for (uint32_t q = 0; q < B; ++q) {
       dst.p[q] = (sv_dst ? sv_dst + (size_t)q * c->dim_sum * ctw : members[q]->sv_ntt) + produced * ctw;
-      ksets[q] = first + q < c->bs().batch_keysets.size() ? c->bs().batch_keysets[first + q] : 0;
+      const uint32_t oq = qidx ? qidx[q] : first + q;
+      ksets[q] = oq < c->bs().batch_keysets.size() ? c->bs().batch_keysets[oq] : 0;
     }
-    const uint64_t* roots = c->bs().d_bquery + (size_t)first * qwords + (size_t)qc * ctw;
     uint64_t* res;
     if (use_head) {
       HeadSlot& hs = ln.head[ln.head_next++ & 1];
       ensure_head_slot(c, hs);
       hipStream_t hst = c->head_stream;
       if (hs.in_use) HIP_TRY(hipStreamWaitEvent(hst, hs.ev_free, 0));   // the lane is done with the slot's previous tree
-      wait_staged(c, hst, first, B);
-      HIP_TRY(launch_tree_convert(hst, c->dp, c->mode, roots, hs.res_a, (uint64_t)B * ctw, true, ctw, qwords));
+      wait_staged(c, hst, ws_first, ws_n);
+      import_roots(hst, hs.res_a, qc);
       TreeState at;
       (void)expand_core(c, hst, hs.res_a, hs.res_b, hs.dig, hs.prod, slots, B, &dst, sel_f64, ksets, 0, c->head_levels, nullptr, &at);
       HIP_TRY(hipEventRecord(hs.ev_ready, hst));
@@ -3088,9 +3341,7 @@ static void expand_group_on_lane(pirgpu_ctx* c, BatchLane& ln, Worker* const* me
                           hs.in_use = true;
                         });
     } else {
-      // the B query ciphertexts, gathered side by side out of the staged batch, become the roots of the B interleaved
-      // trees (one strided import launch: no separate 2-D copy)
-      HIP_TRY(launch_tree_convert(ln.stream, c->dp, c->mode, roots, ln.res_a, (uint64_t)B * ctw, true, ctw, qwords));
+      import_roots(ln.stream, ln.res_a, qc);
       res = expand_core(c, ln.stream, ln.res_a, ln.res_b, ln.dig, ln.prod, slots, B, &dst, sel_f64, ksets);
     }
     if (res) HIP_TRY(c->ops->ct_ntt_fwd_split(ln.stream, c->mode, c->dp, k, res, dst, B, (uint64_t)slots * B));
@@ -3111,6 +3362,66 @@ struct PackedInput {            // multi-GPU packed exchange (pirgpu_batch_run_p
   uint32_t per_rank;           // queries per source rank (groups never span two source ranks)
 };
 
+// The database pass of a group whose members named more than one table: run r = members [rb[r], rb[r + 1]) multiplies its
+// column selectors with table tabs[r].  One launch for all runs (scan_mfma_runs_kernel; option TABLES_ONE_LAUNCH, default
+// 1, geometries of the 8-wave kernels), else one launch of the usual pass per run.  Row sums land query-major in the
+// lane's buffers exactly as a single-table group leaves them.
+static void scan_group_runs(pirgpu_ctx* c, BatchLane& ln, const MfmaPtrs& col, uint32_t B, const uint32_t* rb, uint32_t nr,
+                            const uint32_t* tabs, bool sel_f64, bool share_chip) {
+  const uint32_t kN = c->k * c->N;
+  const uint64_t words = (uint64_t)c->scan_rows * c->ctw;
+  const uint32_t nch = c->mg.nchunks;
+  ensure_packed(c);
+  uint64_t* const out_base = ln.lvl[c->d - 1];
+  if (!option(c, "TABLES_ONE_LAUNCH", 1) || !scan_mfma_runs_supported(c->mg)) {
+    for (uint32_t r = 0; r < nr; ++r) {
+      MfmaPtrs cr{};
+      for (uint32_t q = rb[r]; q < rb[r + 1]; ++q) cr.p[q - rb[r]] = col.p[q];
+      // (stream order on the lane covers the reuse of the one selector buffer by the next run)
+      scan_group_mfma(c, ln.stream, ln.selp, cr, rb[r + 1] - rb[r], out_base + rb[r] * words,
+                      ln.scan_part ? ln.scan_part + (uint64_t)rb[r] * nch * words : nullptr, nullptr, nullptr, sel_f64,
+                      share_chip, tabs[r]);
+    }
+    return;
+  }
+  if (!ln.selp_runs) ln.selp_runs = c->dalloc<uint8_t>((size_t)kMaxMfmaQueries * c->mg.sel_bytes);
+  uint64_t* const out = nch > 1 ? ln.scan_part : out_base;
+  const uint64_t out_qstride = nch > 1 ? (uint64_t)nch * words : words;
+  ScanGroupsDb grp{};
+  grp.n = nr;
+  for (uint32_t r = 0; r < nr; ++r) {
+    MfmaPtrs cr{};
+    for (uint32_t q = rb[r]; q < rb[r + 1]; ++q) cr.p[q - rb[r]] = col.p[q];
+    uint8_t* selp = ln.selp_runs + (size_t)r * c->mg.sel_bytes;
+    HIP_TRY(launch_sel_pack(ln.stream, c->dp, c->mg, cr, rb[r + 1] - rb[r], selp, c->scan_cols, kN, sel_f64));
+    grp.sel[r] = selp;
+    grp.out[r] = out + rb[r] * out_qstride;
+    grp.nq[r] = (uint8_t)(rb[r + 1] - rb[r]);
+    grp.db[r] = table_dbp(c, tabs[r]);
+  }
+  const uint32_t wgs = share_chip && c->scan_wgs_batch ? c->scan_wgs_batch : 0;
+  const bool timed = c->prof && c->bscan_n < 64;
+  if (timed) {
+    while (c->bscan_ev.size() < 2 * (size_t)(c->bscan_n + 1)) {
+      hipEvent_t e;
+      HIP_TRY(hipEventCreate(&e));
+      c->bscan_ev.push_back(e);
+    }
+    HIP_TRY(hipEventRecord(c->bscan_ev[2 * c->bscan_n], ln.stream));
+  }
+  HIP_TRY(launch_scan_mfma_runs(ln.stream, c->dp, c->mg, grp, c->scan_rows, kN, words, wgs,
+                                c->scan_f64_fold || c->scan_f64_fold_batch, out_qstride));
+  ++c->scan_launches;
+  if (timed) {
+    HIP_TRY(hipEventRecord(c->bscan_ev[2 * c->bscan_n + 1], ln.stream));
+    ++c->bscan_n;
+    c->bscan_wgs = wgs;
+    c->bscan_nq = B;
+  }
+  if (nch > 1)
+    HIP_TRY(launch_reduce_splits(ln.stream, c->dp, ln.scan_part, nch, words, out_base, B, (uint64_t)nch * words, words));
+}
+
 // Members (selection-vector buffers) of the group that runs on lane `li`: lane-bound, so that stream order on the
 // lane covers their reuse; with fewer than 2 x G workers every group uses lane 0.
 static uint32_t lanes_in_use(pirgpu_ctx* c, uint32_t G) {
@@ -3118,10 +3429,20 @@ static uint32_t lanes_in_use(pirgpu_ctx* c, uint32_t G) {
   return std::max<uint32_t>(1, std::min<uint32_t>((uint32_t)c->lanes.size(), W / std::max<uint32_t>(G, 1)));
 }
 
-static void batch_run_mfma(pirgpu_ctx* c, uint32_t count, const uint64_t* ext_sv, const PackedInput* pk = nullptr) {
+// qtab (contexts with tables): the table of every query of the batch, by submission index.  The groups are then formed
+// over the batch sorted by table (plan_table_runs); replies, key sets and downloads keep the submission index.
+static void batch_run_mfma(pirgpu_ctx* c, uint32_t count, const uint64_t* ext_sv, const PackedInput* pk = nullptr,
+                           const uint32_t* qtab = nullptr) {
   const size_t rwords = (size_t)c->reply_cts * c->rctw, svwords = (size_t)c->dim_sum * c->ctw;
   const uint32_t W = std::max<uint32_t>(1, std::min<uint32_t>(c->n_active, (uint32_t)c->workers.size()));
   const uint32_t G = std::min<uint32_t>(c->mfma_nq, W);
+  TablePlan tp;
+  if (qtab) tp = plan_table_runs(qtab, count, G);
+  const uint32_t* order = qtab && !tp.identity ? tp.order.data() : nullptr;   // position in the served order -> staged query
+  auto oq = [&](uint32_t pos) { return order ? order[pos] : pos; };
+  auto tab = [&](uint32_t pos) { return qtab ? qtab[oq(pos)] : 0u; };
+  std::vector<uint8_t> done(order ? count : 0, 0);   // permuted batch: submission indices whose replies are queued
+  uint32_t lead = 0;                                 // ... and how many leading ones are
   const uint32_t my_rows = c->se - c->sb;
   ensure_lanes(c, !ext_sv && !pk);
   const uint32_t nl = lanes_in_use(c, G);
@@ -3159,7 +3480,8 @@ static void batch_run_mfma(pirgpu_ctx* c, uint32_t count, const uint64_t* ext_sv
       // inverse transform write them where pirgpu_batch_fetch reads them (no device-to-device copy per group)
       uint64_t* lvl_ptrs[PIRGPU_MAX_DIMS];
       for (uint32_t l = 0; l < c->d; ++l) lvl_ptrs[l] = ln.lvl[l];
-      const bool direct_reply = c->d >= 2;   // d = 1 would make the scan itself write there: keep the lane buffer
+      // (d = 1 would make the scan itself write there, a permuted group's replies are not neighbours: the lane buffer)
+      const bool direct_reply = c->d >= 2 && !order;
       if (direct_reply) lvl_ptrs[0] = reply_base(c) + (size_t)first * rwords;
       Stage sg{ln.stream, lvl_ptrs, ln.pt_buf, B, MfmaPtrs{}, pk != nullptr, &ln.up_scratch, &ln.up_scratch_words};
       sg.last = ln.last;   // result_primes: level 0 lands there, the compact switch writes the replies to lvl_ptrs[0]
@@ -3170,19 +3492,34 @@ static void batch_run_mfma(pirgpu_ctx* c, uint32_t count, const uint64_t* ext_sv
         for (uint32_t q = 0; q < B; ++q) sg.sel.p[q] = pk->rows + (size_t)(first + q) * my_rows * c->ctw;
       } else {
         if (!ext_sv) {
-          expand_group_on_lane(c, ln, members, B, first, c->sel_f64);
+          expand_group_on_lane(c, ln, members, B, first, c->sel_f64, nullptr, order ? order + first : nullptr);
           sg.sel_f64 = c->sel_f64;   // written and read on this lane only: exact doubles instead of u64
         }
         for (uint32_t q = 0; q < B; ++q) {
-          const uint64_t* sv = ext_sv ? ext_sv + (size_t)(first + q) * svwords : members[q]->sv_ntt;
+          const uint64_t* sv = ext_sv ? ext_sv + (size_t)oq(first + q) * svwords : members[q]->sv_ntt;
           sg.sel.p[q] = sv;
           col.p[q] = sv + (size_t)c->sv_off[c->d - 1] * c->ctw;
         }
       }
-      scan_group_mfma(c, ln.stream, ln.selp, col, B, ln.lvl[c->d - 1], ln.scan_part, nullptr, packed, sg.sel_f64,
-                      share_chip);
+      // runs of equal tables among the members (one run without tables)
+      uint32_t rb[kMaxMfmaQueries + 1], tabs[kMaxMfmaQueries], nr = 0;
+      for (uint32_t q = 0; q < B; ++q)
+        if (q == 0 || tab(first + q) != tab(first + q - 1)) {
+          rb[nr] = q;
+          tabs[nr++] = tab(first + q);
+        }
+      rb[nr] = B;
+      if (nr == 1)
+        scan_group_mfma(c, ln.stream, ln.selp, col, B, ln.lvl[c->d - 1], ln.scan_part, nullptr, packed, sg.sel_f64,
+                        share_chip, tabs[0]);
+      else
+        scan_group_runs(c, ln, col, B, rb, nr, tabs, sg.sel_f64, share_chip);
       post_scan_stage(c, sg, nullptr);
-      if (!direct_reply)
+      if (order) {   // every reply to its query's own place
+        for (uint32_t q = 0; q < B; ++q)
+          HIP_TRY(hipMemcpyAsync(reply_base(c) + (size_t)oq(first + q) * rwords, ln.lvl[0] + (size_t)q * rwords, rwords * 8,
+                                 hipMemcpyDeviceToDevice, ln.stream));
+      } else if (!direct_reply)
         HIP_TRY(hipMemcpyAsync(reply_base(c) + (size_t)first * rwords, ln.lvl[0], (size_t)B * rwords * 8,
                                hipMemcpyDeviceToDevice, ln.stream));
       if (host_dl) {
@@ -3201,10 +3538,21 @@ static void batch_run_mfma(pirgpu_ctx* c, uint32_t count, const uint64_t* ext_sv
         if (!c->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
         HIP_TRY(hipEventRecord(b.rd_events[gi], ln.stream));
         HIP_TRY(hipStreamWaitEvent(c->copy_stream, b.rd_events[gi], 0));
-        HIP_TRY(hipMemcpyAsync(b.host_reply + (size_t)first * rwords, reply_base(c) + (size_t)first * rwords,
-                               (size_t)B * rwords * 8, hipMemcpyDeviceToHost, c->copy_stream));
+        if (order) {
+          // a permuted group's replies are scattered over the buffer: one copy each, and the group reports how many
+          // LEADING queries of the batch are complete with it (the copy stream runs the groups' copies in order)
+          for (uint32_t q = 0; q < B; ++q) {
+            const size_t at = (size_t)oq(first + q) * rwords;
+            HIP_TRY(hipMemcpyAsync(b.host_reply + at, reply_base(c) + at, rwords * 8, hipMemcpyDeviceToHost, c->copy_stream));
+            done[oq(first + q)] = 1;
+          }
+          while (lead < count && done[lead]) ++lead;
+        } else {
+          HIP_TRY(hipMemcpyAsync(b.host_reply + (size_t)first * rwords, reply_base(c) + (size_t)first * rwords,
+                                 (size_t)B * rwords * 8, hipMemcpyDeviceToHost, c->copy_stream));
+        }
         HIP_TRY(hipEventRecord(b.dl_events[gi], c->copy_stream));
-        b.dl_end.push_back(first + B);
+        b.dl_end.push_back(order ? lead : first + B);
       }
       for (uint32_t q = 0; q < B; ++q) {
         HIP_TRY(hipEventRecord(members[q]->ev_done, ln.stream));
@@ -3235,25 +3583,44 @@ static void batch_run_impl_body(pirgpu_ctx* c, uint32_t count, const uint64_t* e
   const size_t svwords = (size_t)c->dim_sum * c->ctw;
   const uint32_t W = std::max<uint32_t>(1, std::min<uint32_t>(c->n_active, (uint32_t)c->workers.size()));
   const uint32_t G = mq_usable(c) && c->pt_end > c->pt_begin ? std::min<uint32_t>(c->mq_nq, kMaxScanQueries) : 1;
-  if (c->n_loaded != held_pts(c))
-    throw Fail{PIRGPU_FAILED_PRECONDITION, "database not fully loaded"};
-  check_transparent(c);
+  // contexts with tables: the table of every query -- what pirgpu_batch_set_tables left for this many queries, else the
+  // table selected with pirgpu_query_use_table for all of them.  Every named table must be complete and free of zero
+  // plaintexts before anything is queued (the batch fails as a whole, like a batch on one database)
+  std::vector<uint32_t> qtab_v;
+  if (c->tables > 1) {
+    qtab_v = c->bs().batch_tables.size() == count ? c->bs().batch_tables : std::vector<uint32_t>(count, c->cur_table);
+    for (uint32_t t : qtab_v) {
+      if (!table_loaded(c, t)) throw Fail{PIRGPU_FAILED_PRECONDITION, "table " + std::to_string(t) + " not fully loaded"};
+      check_transparent(c, t);
+    }
+  } else {
+    if (c->n_loaded != held_pts(c))
+      throw Fail{PIRGPU_FAILED_PRECONDITION, "database not fully loaded"};
+    check_transparent(c);
+  }
+  const uint32_t* qtab = qtab_v.empty() ? nullptr : qtab_v.data();
   check_reply_target(c, count);
   if (!ext_sv) check_staged_keysets(c);
   ensure_packed(c);
   c->prof_cur = -1;
   if (c->mfma_on) {
-    batch_run_mfma(c, count, ext_sv);
+    batch_run_mfma(c, count, ext_sv, nullptr, qtab);
     c->bs().batch_valid = true;
     return;
   }
+  // 64-bit scans: the same order by table, so that the queries one pass of scan_mq_kernel serves share their table
+  TablePlan tp;
+  if (qtab) tp = plan_table_runs(qtab, count, kMaxMfmaQueries);
+  const uint32_t* order = qtab && !tp.identity ? tp.order.data() : nullptr;
+  auto oq = [&](uint32_t pos) { return order ? order[pos] : pos; };
   if (!ext_sv) ensure_lanes(c, true);
   for (uint32_t base = 0; base < count; base += W) {
     const uint32_t n = std::min<uint32_t>(W, count - base);
+    for (uint32_t j = 0; j < n; ++j) c->workers[j].table = qtab ? qtab[oq(base + j)] : 0;
     if (ext_sv) {
       for (uint32_t j = 0; j < n; ++j) {
         Worker& w = c->workers[j];
-        w.sv_cur = ext_sv + (size_t)(base + j) * svwords;
+        w.sv_cur = ext_sv + (size_t)oq(base + j) * svwords;
         HIP_TRY(hipEventRecord(w.ev_expanded, w.stream));
       }
     } else {
@@ -3265,7 +3632,7 @@ static void batch_run_impl_body(pirgpu_ctx* c, uint32_t count, const uint64_t* e
           members[q] = &c->workers[j0 + q];
           HIP_TRY(hipStreamWaitEvent(ln.stream, members[q]->ev_done, 0));  // its selection vector is free again
         }
-        expand_group_on_lane(c, ln, members, B, base + j0);
+        expand_group_on_lane(c, ln, members, B, base + j0, false, nullptr, order ? order + base + j0 : nullptr);
         for (uint32_t q = 0; q < B; ++q) {
           HIP_TRY(hipEventRecord(members[q]->ev_expanded, ln.stream));
           HIP_TRY(hipStreamWaitEvent(members[q]->stream, members[q]->ev_expanded, 0));
@@ -3276,8 +3643,14 @@ static void batch_run_impl_body(pirgpu_ctx* c, uint32_t count, const uint64_t* e
       const uint32_t g = std::min<uint32_t>(G, n - j0);
       uint32_t done = 0;
       while (done < g) {  // group sizes the kernel is instantiated for: 4, 2, 1
-        const uint32_t take = g - done >= 4 && G >= 4 ? 4 : (g - done >= 2 && G >= 2 ? 2 : 1);
+        uint32_t take = g - done >= 4 && G >= 4 ? 4 : (g - done >= 2 && G >= 2 ? 2 : 1);
         Worker& lead = c->workers[j0 + done];
+        while (take > 1) {   // (tables: one pass reads one table)
+          bool same = true;
+          for (uint32_t q = 1; q < take; ++q) same = same && c->workers[j0 + done + q].table == lead.table;
+          if (same) break;
+          take /= 2;
+        }
         if (take == 1) {
           scan_on_device(c, lead);
         } else {
@@ -3290,7 +3663,7 @@ static void batch_run_impl_body(pirgpu_ctx* c, uint32_t count, const uint64_t* e
             outp[q] = scan_out(c, m);
           }
           const uint32_t rpw = take == 4 ? (c->mq_rows > 2 ? 1 : c->mq_rows) : (c->mq_rows > 2 ? 2 : c->mq_rows);
-          HIP_TRY(launch_scan_mq(lead.stream, c->dp, c->N, c->k, c->d_db, svp, outp, take, c->scan_rows,
+          HIP_TRY(launch_scan_mq(lead.stream, c->dp, c->N, c->k, table_db(c, lead.table), svp, outp, take, c->scan_rows,
                                  c->scan_cols, rpw, c->scan_limb));
           HIP_TRY(hipEventRecord(lead.ev_scanned, lead.stream));
           for (uint32_t q = 1; q < take; ++q)
@@ -3302,7 +3675,7 @@ static void batch_run_impl_body(pirgpu_ctx* c, uint32_t count, const uint64_t* e
     for (uint32_t j = 0; j < n; ++j) {
       Worker& w = c->workers[j];
       post_scan_on_device(c, w);
-      HIP_TRY(hipMemcpyAsync(reply_base(c) + (base + j) * rwords, w.lvl[0], rwords * 8, hipMemcpyDeviceToDevice,
+      HIP_TRY(hipMemcpyAsync(reply_base(c) + (size_t)oq(base + j) * rwords, w.lvl[0], rwords * 8, hipMemcpyDeviceToDevice,
                              w.stream));
       HIP_TRY(hipEventRecord(w.ev_done, w.stream));
       w.reply_valid = true;
@@ -3380,6 +3753,7 @@ static int batch_expand_packed_impl(pirgpu_ctx* c, uint32_t first_query, uint32_
                                     uint64_t* device_rows, const uint32_t* row_cuts, uint32_t n_ranks, bool wait) {
   return guarded(c, [&]() -> int {
     refuse_wide(c);
+    refuse_tables(c);
     refuse_switched(c);
     ensure_workspace(c);
     if (c->d != 2 || !c->mfma_on)
@@ -3448,6 +3822,7 @@ int pirgpu_batch_run_packed(pirgpu_ctx* c, const uint8_t* device_packed, uint32_
                             const uint64_t* device_rows) {
   return guarded(c, [&]() -> int {
     refuse_wide(c);
+    refuse_tables(c);
     refuse_switched(c);
     ensure_workspace(c);
     if (c->d != 2 || !c->mfma_on)
@@ -3521,6 +3896,7 @@ void lane_then(BatchLane& ln, void* then) {
 
 void check_slots_ctx(pirgpu_ctx* c) {
   refuse_wide(c);
+  refuse_tables(c);
   refuse_switched(c);
   ensure_workspace(c);
   if (c->d != 2 || !c->mfma_on || c->mg.nchunks != 1 || c->sb != 0 || c->se != c->dims[0])

@@ -28,6 +28,12 @@ struct ScanGroups {
   uint8_t nq[kMaxScanGroups];
 };
 
+// ... with a database per group (contexts with tables): group g scans the operand layout at db[g], every one a complete
+// layout of the same geometry.
+struct ScanGroupsDb : ScanGroups {
+  const uint8_t* db[kMaxScanGroups];
+};
+
 // Slot ranges [cut[r], cut[r+1]) (multiples of 16, cut[0] = 0, cut[n] = k N) and, for sel_pack, the byte offset of each
 // range's piece in the output buffer.
 struct SliceMap {
@@ -234,6 +240,12 @@ hipError_t launch_scan_mfma_groups(hipStream_t st, const DevParams* P, const Mfm
                                    const ScanGroups& grp, uint32_t rows, uint64_t chunk_stride, uint32_t wgs, bool f64_fold,
                                    uint32_t slot0, uint32_t nslots, uint64_t out_qstride, uint32_t out_rstride,
                                    bool blk_major = false);   // blk_major: units ordered (slot block, group) instead of (group, slot block)
+// several groups over the whole ring, each over ITS OWN database grp.db[g] (the runs of equal tables inside one batch
+// group); scan_mfma_runs_supported: the geometries the launch is built for (the 8-wave kernels) -- others launch per run
+bool scan_mfma_runs_supported(const MfmaGeom& gm);
+hipError_t launch_scan_mfma_runs(hipStream_t st, const DevParams* P, const MfmaGeom& gm, const ScanGroupsDb& grp,
+                                 uint32_t rows, uint32_t kN, uint64_t chunk_stride, uint32_t wgs, bool f64_fold,
+                                 uint64_t out_qstride);
 // row sums of queries q0 .. q0 + nq - 1 (of the nq_total the receive buffer holds per rank) back from the per-rank slot
 // pieces of the all-to-all receive buffer to [query][row, comp][kN] at dst + (q - q0) * dst_qstride
 hipError_t launch_slots_assemble(hipStream_t st, const uint64_t* src, uint64_t* dst, const SliceMap& map, uint32_t RC,

@@ -67,6 +67,8 @@ struct PIRParameters {
   bool use_ciphertext_multiplication = false;
   uint32_t plaintexts_per_item = 1;      // wide items (not in the reference): pirgpu_params.plaintexts_per_item
   uint32_t result_primes = 0;            // modulus-switched results (not in the reference): pirgpu_params.result_primes
+  uint32_t tables = 0;                   // tables (not in the reference): databases of these parameters behind one
+                                         // context, every query naming its table (pirgpu_params.tables; 0 / 1 = one)
   size_t DimensionsSum() const {          // PIRContext::DimensionsSum, context.h:59-62
     size_t s = 0;
     for (auto d : dimensions) s += d;
@@ -111,6 +113,7 @@ class PIRDatabase {
     p.use_ciphertext_multiplication = params->use_ciphertext_multiplication ? 1 : 0;
     p.plaintexts_per_item = params->plaintexts_per_item;
     p.result_primes = params->result_primes;
+    p.tables = params->tables;
     p.device = device;
     pirgpu_ctx* ctx = nullptr;
     int rc = pirgpu_create_ex(&p, streamed ? PIRGPU_CREATE_STREAMED_DB : 0u, &ctx);
@@ -130,10 +133,12 @@ class PIRDatabase {
   }
 
   // database.cpp:84-110
+  // (tables: the items of all tables, table-major)
   Status populate(const std::vector<std::string>& rawdb) {
-    if (rawdb.size() != params_->num_items)
+    const uint64_t want = params_->num_items * std::max<uint32_t>(1, params_->tables);
+    if (rawdb.size() != want)
       return InvalidArgumentError("Database size " + std::to_string(rawdb.size()) + " does not match params value " +
-                                  std::to_string(params_->num_items));
+                                  std::to_string(want));
     std::string flat;
     flat.reserve(rawdb.size() * params_->bytes_per_item);
     for (const auto& s : rawdb) {
@@ -143,6 +148,20 @@ class PIRDatabase {
     return detail::FromRc(ctx_, pirgpu_db_load_items(ctx_, reinterpret_cast<const uint8_t*>(flat.data()),
                                                      rawdb.size(), params_->bytes_per_item));
   }
+
+  // Tables (no reference counterpart): loads or reloads table `table` alone -- num_items items of it -- and leaves the
+  // others as they are (pirgpu_db_load_table_items).
+  Status load_table(uint32_t table, const std::vector<std::string>& rawdb) {
+    std::string flat;
+    flat.reserve(rawdb.size() * params_->bytes_per_item);
+    for (const auto& s : rawdb) {
+      if (s.size() != params_->bytes_per_item) return InvalidArgumentError("item size does not match parameters");
+      flat += s;
+    }
+    return detail::FromRc(ctx_, pirgpu_db_load_table_items(ctx_, table, reinterpret_cast<const uint8_t*>(flat.data()),
+                                                           rawdb.size(), params_->bytes_per_item));
+  }
+  uint32_t tables() const { return pirgpu_tables(ctx_); }
 
   // No reference counterpart (database.cpp:84-110 only repopulates): items[i] replaces item indices[i] in place
   // (pirgpu_db_update_items); a later entry wins, items outside this context's row shard are skipped.
@@ -213,16 +232,19 @@ class PIRServer {
   // server.cpp:35-42
   static StatusOr<std::unique_ptr<PIRServer>> Create(std::shared_ptr<PIRDatabase> db,
                                                      std::shared_ptr<PIRParameters> params) {
-    if (params->num_pt * std::max<uint32_t>(1, params->plaintexts_per_item) != db->size()) return InvalidArgumentError("database size mismatch");
+    // (tables are loaded one by one and served as soon as they are complete: no size to compare with)
+    if (db->tables() <= 1 && params->num_pt * std::max<uint32_t>(1, params->plaintexts_per_item) != db->size())
+      return InvalidArgumentError("database size mismatch");
     return std::unique_ptr<PIRServer>(new PIRServer(std::move(db), std::move(params)));
   }
 
   // server.cpp:44-65 on serialized pir.Request / pir.Response
-  StatusOr<std::string> ProcessRequest(const std::string& request) const {
+  // table (contexts with tables): the table the request is answered from -- beside the request bytes, not in them
+  StatusOr<std::string> ProcessRequest(const std::string& request, uint32_t table = 0) const {
     uint8_t* resp = nullptr;
     size_t len = 0;
-    int rc = pirgpu_process_request(db_->handle(), reinterpret_cast<const uint8_t*>(request.data()), request.size(),
-                                    &resp, &len);
+    int rc = pirgpu_process_request_table(db_->handle(), table, reinterpret_cast<const uint8_t*>(request.data()),
+                                          request.size(), &resp, &len);
     if (rc) return detail::FromRc(db_->handle(), rc);
     std::string out(reinterpret_cast<const char*>(resp), len);
     pirgpu_free(resp);
@@ -231,8 +253,12 @@ class PIRServer {
 
   // The same for several independent requests (different clients) served TOGETHER -- no reference counterpart (the
   // reference is single-threaded); result[i] is what ProcessRequest(requests[i]) would have returned.
-  std::vector<StatusOr<std::string>> ProcessRequests(const std::vector<std::string>& requests) const {
+  // tables (contexts with tables): one table per request; empty = table 0 for all
+  std::vector<StatusOr<std::string>> ProcessRequests(const std::vector<std::string>& requests,
+                                                     const std::vector<uint32_t>& tables = {}) const {
     const uint32_t n = static_cast<uint32_t>(requests.size());
+    if (!tables.empty() && tables.size() != requests.size())
+      return std::vector<StatusOr<std::string>>(n, StatusOr<std::string>(InvalidArgumentError("one table per request")));
     std::vector<const uint8_t*> ptrs(n);
     std::vector<size_t> lens(n), rlens(n, 0);
     std::vector<uint8_t*> resps(n, nullptr);
@@ -241,7 +267,8 @@ class PIRServer {
       ptrs[i] = reinterpret_cast<const uint8_t*>(requests[i].data());
       lens[i] = requests[i].size();
     }
-    pirgpu_process_requests(db_->handle(), n, ptrs.data(), lens.data(), resps.data(), rlens.data(), status.data());
+    pirgpu_process_requests_tables(db_->handle(), n, ptrs.data(), lens.data(), tables.empty() ? nullptr : tables.data(),
+                                   resps.data(), rlens.data(), status.data());
     std::vector<StatusOr<std::string>> out;
     out.reserve(n);
     for (uint32_t i = 0; i < n; ++i) {
@@ -254,6 +281,9 @@ class PIRServer {
     }
     return out;
   }
+
+  // Tables: the table the single-query entry points of the C ABI answer from (sticky, default 0; pirgpu_query_use_table)
+  Status use_table(uint32_t table) const { return detail::FromRc(db_->handle(), pirgpu_query_use_table(db_->handle(), table)); }
 
   // ProcessRequests in two halves (pirgpu_process_requests_begin / _end): ONE calling thread keeps two calls in flight --
   // Begin(next) before End(previous) -- so the next call's parsing / staging / queueing run under the previous call's

@@ -376,200 +376,29 @@ constexpr int kBiasBits = 59;
 // F64F: the digit diagonals are folded in exact fp64 arithmetic (all data moduli < 2^50): four diagonals combine exactly
 // in one double (|C| < 2^49.01), chunk c times 2^(32 c) mod q with the 6-operation exact product of arith.h --
 // ~45 full-rate operations per value against ~170 mostly quarter-rate 64-bit integer ones.  Same canonical residues.
+#define PIRGPU_SCAN_DB_OF(g_) dbp
 template <int L, int KS, int NW, bool TOP4, bool F64F = false>
 __global__ void __launch_bounds__(NW * 64)
 scan_mfma_kernel(const DevParams* __restrict__ P, const uint8_t* __restrict__ dbp, ScanGroups grp, uint32_t rows,
                  uint32_t RT, uint32_t KG, uint64_t chunk_stride, ChunkPlan plan, uint32_t GC, uint32_t slot0,
                  uint32_t nslots, uint64_t out_qstride, uint32_t out_rstride, uint32_t blk_major) {
-  constexpr uint32_t TB = tile_bytes(L, TOP4);
-  constexpr int LF = TOP4 ? L - 1 : L;   // digits stored as full bytes
-  constexpr int NS = 2 * L - 1;        // digit diagonals
-  constexpr int NG = (NS + 4) / 5;     // groups of five diagonals (40 bits)
-  // results of one row tile, [row][x][slot]: a (row, x) run is padded to 9 words so that the 16 lanes of a row (x = 0..15,
-  // 72 bytes apart) hit 16 different 8-byte bank pairs when a wave stores its slot (64 bytes apart they hit two)
-  // kDirect (-DPIRGPU_SCAN_DIRECT=1): no staging and no workgroup barrier -- every lane stores its four values itself
-  // (8 bytes each; the eight waves' stores to a (row, x) run of eight slots merge in L2) and the waves run decoupled.
-  constexpr bool kDirect = PIRGPU_SCAN_DIRECT != 0;
-  __shared__ __attribute__((aligned(16))) uint64_t stage[kDirect ? 1 : 2][kDirect ? 1 : 16][kDirect ? 1 : 16][NW + PIRGPU_SCAN_PAD];
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  const int g = l >> 4, i16 = l & 15;
-  constexpr int LOGNW = NW == 8 ? 3 : 2;
-  const uint32_t nblocks = nslots >> LOGNW;
-  const uint32_t nunits = nblocks * grp.n;
-  uint32_t ch = 0;
-  while (ch + 1 < plan.nchunks && blockIdx.x >= plan.first[ch + 1]) ++ch;
-  const uint32_t wg_in_chunk = blockIdx.x - plan.first[ch], wgs_in_chunk = plan.first[ch + 1] - plan.first[ch];
-  const uint32_t kg0 = ch * GC;                                   // GC <= 4 KS column groups per chunk
-  const uint32_t gc = KG - kg0 < GC ? KG - kg0 : GC;              // column groups of this chunk
-  const size_t slab = (size_t)RT * KG * TB;                       // database bytes of one slot
-  const size_t chunk_base = (size_t)RT * kg0 * TB;                // this chunk inside a slot
-  const size_t rt_stride = (size_t)gc * TB;
-  const uint32_t lane16 = i16 * 16, lane8 = i16 * 8;              // the lane's bytes inside a full / a nibble tile
-
-  v4i B[KS][L], A[KS][LF];
-  v2i A4[KS];                           // TOP4: the top digit's tiles, packed
-  // selector tiles of (local) slot jl of group gi
-  auto load_B = [&](uint32_t gi, uint32_t jl) {
-    const uint8_t* selp = grp.sel[gi];
-    const uint32_t nx = 2u * grp.nq[gi];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const uint32_t gl = ks * 4 + g, kg = kg0 + gl;
-      const uint8_t* blk = selp + ((size_t)jl * KG + kg) * TB;
-#pragma unroll
-      for (int b = 0; b < L; ++b) {
-        B[ks][b] = v4i{0, 0, 0, 0};   // columns beyond the group's queries stay zero and are neither packed nor read
-        if (gl < gc && (uint32_t)i16 < nx) {
-          if (TOP4 && b == L - 1) B[ks][b] = expand_top4(*reinterpret_cast<const v2i*>(blk + b * 256 + lane8));
-          else B[ks][b] = *reinterpret_cast<const v4i*>(blk + b * 256 + lane16);
-        }
-      }
-    }
-  };
-  // the L tiles of column group gl (inside the chunk) of one row tile, from `base` = that row tile's first byte
-  auto load_A = [&](int ks, const uint8_t* base, uint32_t gl) {
-    const uint8_t* blk = base + (size_t)gl * TB;
-#pragma unroll
-    for (int a = 0; a < LF; ++a) A[ks][a] = load_tile(blk + a * 256 + lane16);
-    if constexpr (TOP4) A4[ks] = load_tile8(blk + (L - 1) * 256 + lane8);
-  };
-
-  // unit -> (group, slot block): group-major (u = group * nblocks + block: the launch sweeps the slots once per group) or
-  // block-major (u = block * groups + group: the workgroups running side by side read the SAME database tiles for
-  // different groups, so all but the first reader of a tile can be served by the memory-side cache)
-  // (plain scalar arithmetic at each use: a helper taking references made the compiler keep the pair in scratch)
-#define PIRGPU_UNIT_OF(uu, gi_, blk_)                                  \
-  const uint32_t gi_ = blk_major ? (uu) % grp.n : (uu) / nblocks;      \
-  const uint32_t blk_ = blk_major ? (uu) / grp.n : (uu) - gi_ * nblocks;
-  uint32_t u = wg_in_chunk;
-  if (u >= nunits) return;
-  {
-    PIRGPU_UNIT_OF(u, gi, blk)
-    load_B(gi, blk * NW + w);
-    const uint8_t* abase = dbp + (size_t)(blk * NW + w) * slab + chunk_base;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const uint32_t gl = ks * 4 + g;   // column group inside the chunk
-#pragma unroll
-      for (int a = 0; a < LF; ++a) A[ks][a] = v4i{0, 0, 0, 0};
-      A4[ks] = v2i{0, 0};
-      if (gl < gc) load_A(ks, abase, gl);
-    }
-  }
-
-  uint32_t parity = 0;
-  for (; u < nunits; u += wgs_in_chunk) {
-    PIRGPU_UNIT_OF(u, gi, blk)
-    const uint32_t j0 = blk * NW;            // local slot of wave 0
-    const uint32_t j = slot0 + j0 + w;       // this wave's slot of the ring
-    const uint32_t mi = j >> P->logN;
-    const ModConst m = P->mod[mi];
-    const uint32_t nx = 2u * grp.nq[gi];
-    uint64_t* const obase = grp.out[gi] + ch * chunk_stride;
-    // multiple of q that makes every 40-bit group positive: 2^58 <= bias < 2^59, |group| < 2^57.2 (kBiasBits)
-    const uint64_t bias = m.q << (kBiasBits - (64 - __builtin_clzll(m.q)));
-    [[maybe_unused]] const F64Mod fm{P->tab[mi].qd, P->tab[mi].qinvd};
-    [[maybe_unused]] const double fw0 = P->fold_w[mi][0], fw1 = P->fold_w[mi][1], fw2 = P->fold_w[mi][2];
-    const uint8_t* abase = dbp + (size_t)(j0 + w) * slab + chunk_base;
-    const uint32_t nu = u + wgs_in_chunk;
-    const bool has_next = nu < nunits;
-    PIRGPU_UNIT_OF(nu, ngi, nblk)
-    const uint8_t* nbase = dbp + (size_t)(nblk * NW + w) * slab + chunk_base;
-
-    for (uint32_t rt = 0; rt < RT; ++rt) {
-      v4i T[NS];
-#pragma unroll
-      for (int s = 0; s < NS; ++s) T[s] = v4i{0, 0, 0, 0};
-      const bool last = rt + 1 == RT;   // wave-uniform
-      // ring of KS k-steps of A tiles: slot ks is refilled right after use with the same step of the next
-      // row tile (or of the next unit's first row tile)
-      const uint8_t* next_tile = last ? nbase : abase + (size_t)(rt + 1) * rt_stride;
-      const bool refill = !last || has_next;
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        [[maybe_unused]] v4i Atop;
-        if constexpr (TOP4) Atop = expand_top4(A4[ks]);
-        // the L*L digit products, ordered so that consecutive MFMAs accumulate into different diagonals
-#pragma unroll
-        for (int off = 0; off < L; ++off)
-#pragma unroll
-          for (int a = 0; a < L; ++a) {
-            const int b = (a + off) % L;
-            if (TOP4 && a == L - 1)
-              T[a + b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(Atop, B[ks][b], T[a + b], 0, 0, 0);
-            else
-              T[a + b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[ks][a < LF ? a : 0], B[ks][b], T[a + b], 0, 0, 0);
-          }
-        const uint32_t gl = ks * 4 + g;
-        if (refill && gl < gc) load_A(ks, next_tile, gl);
-      }
-      if (last && has_next) load_B(ngi, nblk * NW + w);   // all MFMAs of this unit are issued: B is free
-      // lane (g, i16) holds rows rt*16 + g*4 + i (i < 4) of column x = i16:  value = sum_s T[s] 2^(8 s)
-      const int buf = parity;
-      parity ^= 1;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        uint64_t r = 0;
-        if constexpr (F64F) {
-          // chunks of four diagonals, exact in a double: C_c = ((T[4c+3] 256 + T[4c+2]) 256 + T[4c+1]) 256 + T[4c]
-          constexpr int NC = (NS + 3) / 4;
-          double acc = 0.0;
-#pragma unroll
-          for (int c = NC - 1; c >= 0; --c) {
-            double C = 0.0;
-#pragma unroll
-            for (int s = (4 * c + 3 < NS ? 4 * c + 3 : NS - 1); s >= 4 * c; --s) C = __builtin_fma(C, 256.0, (double)T[s][i]);
-            if (c == 0) acc += f64_norm(C, fm);
-            else acc += f64_mulmod(C, c == 1 ? fw0 : (c == 2 ? fw1 : fw2), fm);
-          }
-          r = f64_to_u64(f64_canon(f64_norm(acc, fm), fm));
-        } else {
-#pragma unroll
-          for (int gq = NG - 1; gq >= 0; --gq) {
-            int64_t G = 0;
-#pragma unroll
-            for (int s = gq * 5; s < gq * 5 + 5 && s < NS; ++s) G += (int64_t)T[s][i] << (8 * (s - gq * 5));
-            if (gq == NG - 1 && NG > 1) {
-              r = (uint64_t)(G + (int64_t)bias);   // top group: < 2^59.4, reduced together with the next one (bias = 0 mod q)
-            } else {
-              const u128 v = ((u128)r << 40) + (uint64_t)(G + (int64_t)bias);
-              r = reduce128((uint64_t)v, (uint64_t)(v >> 64), m);
-            }
-          }
-        }
-        if constexpr (kDirect) {
-          const uint32_t row = rt * 16 + g * 4 + i;
-          if ((uint32_t)i16 < nx && row < rows)
-            obase[(size_t)(i16 >> 1) * out_qstride + ((size_t)row * 2 + (i16 & 1)) * out_rstride + j0 + w] = r;
-        } else {
-          stage[buf][g * 4 + i][i16][w] = r;
-        }
-      }
-      if constexpr (kDirect) continue;
-      __syncthreads();
-      // 256 (row, x) runs of NW slots = 8 NW bytes each; 64 NW threads x 16 B, two rounds
-#pragma unroll
-      for (int round = 0; round < 2; ++round) {
-        const int run = round * 128 + (threadIdx.x >> (LOGNW - 1));
-        const int part = threadIdx.x & (NW / 2 - 1);
-        const int r16 = run >> 4, x = run & 15;
-        const uint32_t r = rt * 16 + r16;
-        if (x < (int)nx && r < rows) {
-          typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-#if PIRGPU_SCAN_PAD == 2
-          const u64x2 v = *reinterpret_cast<const u64x2*>(&stage[buf][r16][x][part * 2]);     // runs 80 bytes apart: one 16-byte read
-#else
-          const u64x2 v = {stage[buf][r16][x][part * 2], stage[buf][r16][x][part * 2 + 1]};   // two 8-byte LDS reads
-#endif
-          uint64_t* dst = obase + (size_t)(x >> 1) * out_qstride + ((size_t)r * 2 + (x & 1)) * out_rstride + j0 + part * 2;
-          *reinterpret_cast<u64x2*>(dst) = v;
-        }
-      }
-    }
-  }
+#include "scan_mfma_body.inc"
 }
+#undef PIRGPU_SCAN_DB_OF
 
-#undef PIRGPU_UNIT_OF
+// The same pass over several databases of one shape (a context with tables): group g -- a run of
+// queries that named the same table -- multiplies its packed selectors with the operand layout at grp.db[g].  One
+// launch for all runs of a batch group instead of one launch per run; the whole ring, group-major units.
+#define PIRGPU_SCAN_DB_OF(g_) grp.db[g_]
+template <int L, int KS, int NW, bool TOP4, bool F64F = false>
+__global__ void __launch_bounds__(NW * 64)
+scan_mfma_runs_kernel(const DevParams* __restrict__ P, ScanGroupsDb grp, uint32_t rows, uint32_t RT, uint32_t KG,
+                      uint64_t chunk_stride, ChunkPlan plan, uint32_t GC, uint32_t nslots, uint64_t out_qstride) {
+  constexpr uint32_t slot0 = 0, blk_major = 0;
+  const uint32_t out_rstride = nslots;
+#include "scan_mfma_body.inc"
+}
+#undef PIRGPU_SCAN_DB_OF
 
 // Slot-sharded multi-GPU step: the row sums of a rank's own nq_total queries arrive from every rank h as
 // [query][row, comp][slots of h] (the all-to-all's receive buffer; rank h's block starts at word nq_total * RC * cut[h]);
@@ -829,6 +658,58 @@ hipError_t launch_scan_mfma_groups(hipStream_t st, const DevParams* P, const Mfm
   PIRGPU_MFMA_CASE(7, 3, 4) PIRGPU_MFMA_CASE(7, 4, 4) PIRGPU_MFMA_CASE(7, 5, 4) PIRGPU_MFMA_CASE(7, 6, 4)
 #undef PIRGPU_MFMA_CASE
 #undef PIRGPU_MFMA_ARGS
+  return hipErrorInvalidValue;
+}
+
+// Runs of a batch group over their own tables (8-wave geometries: the narrow matrices many small tables have; a matrix
+// wide enough for the 4-wave kernel scans long enough per run that the launches do not matter, and keeps them).
+// (<6, 3, 8> -- only reachable with the 4-wave kernel forced off -- spills and is not built for runs either)
+bool scan_mfma_runs_supported(const MfmaGeom& gm) {
+  return gm.L >= 5 && gm.L <= 7 && gm.NW == 8 && gm.KS >= 1 && gm.KS <= (gm.L == 5 ? 3u : 2u);
+}
+
+template <int L, int KS, bool TOP4, bool F64F>
+static void launch_scan_mfma_runs_variant(hipStream_t st, const DevParams* P, const MfmaGeom& gm, const ScanGroupsDb& grp,
+                                          uint32_t rows, uint64_t chunk_stride, uint32_t wgs_req, uint32_t kN,
+                                          uint64_t out_qstride) {
+  constexpr int NW = 8;
+  const uint32_t wgs = wgs_req ? std::min(wgs_req, scan_wgs_all()) : scan_wgs_all();
+  ChunkPlan plan{};
+  plan.nchunks = gm.nchunks;
+  const uint32_t units = kN / NW * grp.n;
+  const uint32_t share = std::min<uint32_t>(units, std::max<uint32_t>(1, wgs / std::min<uint32_t>(gm.nchunks, wgs)));
+  for (uint32_t c = 0; c <= gm.nchunks; ++c) plan.first[c] = c * share;
+  hipLaunchKernelGGL((scan_mfma_runs_kernel<L, KS, NW, TOP4, F64F>), dim3(gm.nchunks * share), dim3(NW * 64), 0, st, P, grp,
+                     rows, gm.RT, gm.KG, chunk_stride, plan, gm.GC, kN, out_qstride);
+}
+
+hipError_t launch_scan_mfma_runs(hipStream_t st, const DevParams* P, const MfmaGeom& gm, const ScanGroupsDb& grp,
+                                 uint32_t rows, uint32_t kN, uint64_t chunk_stride, uint32_t wgs, bool f64_fold,
+                                 uint64_t out_qstride) {
+  if (grp.n == 0 || grp.n > (uint32_t)kMaxScanGroups || kN == 0 || kN % 8 || !scan_mfma_runs_supported(gm))
+    return hipErrorInvalidValue;
+  for (uint32_t g = 0; g < grp.n; ++g)
+    if (!grp.db[g] || !grp.sel[g] || !grp.out[g] || grp.nq[g] == 0 || grp.nq[g] > kMaxMfmaQueries) return hipErrorInvalidValue;
+#define PIRGPU_RUNS_ARGS st, P, gm, grp, rows, chunk_stride, wgs, kN, out_qstride
+#define PIRGPU_RUNS_CASE(L_, KS_)                                                          \
+  if (gm.L == L_ && gm.KS == KS_) {                                                        \
+    if constexpr (L_ <= 6) {                                                               \
+      if (gm.top4) {                                                                       \
+        if (f64_fold) launch_scan_mfma_runs_variant<L_, KS_, true, true>(PIRGPU_RUNS_ARGS); \
+        else launch_scan_mfma_runs_variant<L_, KS_, true, false>(PIRGPU_RUNS_ARGS);        \
+        return hipGetLastError();                                                          \
+      }                                                                                    \
+    }                                                                                      \
+    if (gm.top4) return hipErrorInvalidValue;                                              \
+    if (f64_fold) launch_scan_mfma_runs_variant<L_, KS_, false, true>(PIRGPU_RUNS_ARGS);   \
+    else launch_scan_mfma_runs_variant<L_, KS_, false, false>(PIRGPU_RUNS_ARGS);           \
+    return hipGetLastError();                                                              \
+  }
+  PIRGPU_RUNS_CASE(5, 1) PIRGPU_RUNS_CASE(5, 2) PIRGPU_RUNS_CASE(5, 3)
+  PIRGPU_RUNS_CASE(6, 1) PIRGPU_RUNS_CASE(6, 2)
+  PIRGPU_RUNS_CASE(7, 1) PIRGPU_RUNS_CASE(7, 2)
+#undef PIRGPU_RUNS_CASE
+#undef PIRGPU_RUNS_ARGS
   return hipErrorInvalidValue;
 }
 

@@ -34,6 +34,14 @@
 
 #include "../../include/pirgpu.h"
 
+// The context's table hooks (ctx.hip) are WEAK references here: this file is also linked against
+// stand-in contexts that know no tables (the host-only build of tests/cpp/wire_windows_test.cpp).  Where they are absent
+// the context has one table and every request is served on it -- what a context without tables does.
+#pragma weak pirgpu_tables
+#pragma weak pirgpu_current_table
+#pragma weak pirgpu_query_use_table
+#pragma weak pirgpu_batch_set_tables
+
 namespace pirgpu {
 namespace wire {
 
@@ -251,6 +259,8 @@ struct OutBuf {
   }
 };
 
+uint32_t ctx_tables(pirgpu_ctx* ctx) { return pirgpu_tables ? pirgpu_tables(ctx) : 1u; }
+
 struct RelinCache;
 struct Job {
   const uint8_t* request = nullptr;
@@ -262,6 +272,7 @@ struct Job {
   // filled while serving
   ParsedRequest pr;
   uint32_t slot = 0;          // resident key set of this client
+  uint32_t table = 0;         // table the request is answered from (contexts with tables; beside the request, not in it)
   bool uniform = true;        // every query has the ciphertext count the dimensions call for (server.cpp:154)
   bool unverified = false;    // the slot was taken on its fingerprint alone: the key bytes are compared under the GPU work
   bool mismatch = false;      // ... and differed: install this client's keys and serve the request again
@@ -553,12 +564,16 @@ void run_single(const Server& sv, Job& job, const std::pair<const uint8_t*, size
   // (round-tripping it through a handle would have re-validated it against the slot's next tenant)
   uint32_t callers_sel[2];
   pirgpu_keyset_selection_get(sv.ctx, callers_sel);
+  const bool with_tables = ctx_tables(sv.ctx) > 1;
+  const uint32_t callers_table = with_tables ? pirgpu_current_table(sv.ctx) : 0;   // ... and so does its table selection
   int rc = pirgpu_query_use_keyset(sv.ctx, job.slot);
+  if (!rc && with_tables) rc = pirgpu_query_use_table(sv.ctx, job.table);
   uint64_t got = 0;
   if (!rc) rc = pirgpu_query_stage_async(sv.ctx, hq, nq);   // pinned staging, untouched until the fetch below returns
   if (!rc) rc = pirgpu_query_run(sv.ctx);      // asynchronous: every kernel of the path is queued
   const std::string msg = rc ? pirgpu_last_error(sv.ctx) : "";
   pirgpu_keyset_selection_set(sv.ctx, callers_sel);
+  if (with_tables) (void)pirgpu_query_use_table(sv.ctx, callers_table);
   if (rc) throw Err{rc, msg};
   if (while_running) {
     try {
@@ -603,6 +618,7 @@ struct Window {
   std::vector<Item> chunk;           // the queries queued, in reply order
   std::vector<std::pair<uint32_t, uint32_t>> runs;   // [first, end) items of one request
   std::vector<uint32_t> slots;
+  std::vector<uint32_t> tables;      // table of every queued query (contexts with tables)
   uint64_t *hq = nullptr, *hr = nullptr;
   uint32_t room = 0;
   bool queued = false;               // the batch pipeline holds this window's work
@@ -705,6 +721,7 @@ void begin_window(const Server& sv, Window& w, const std::vector<Item>& items, T
   // queries of requests that failed or turned non-uniform are dropped from the window
   w.chunk.clear();
   w.slots.clear();
+  w.tables.clear();
   for (size_t i = 0; i < items.size(); ++i) {
     const Job& job = *items[i].job;
     if (job.rc || !job.uniform || job.mismatch) continue;
@@ -712,6 +729,7 @@ void begin_window(const Server& sv, Window& w, const std::vector<Item>& items, T
     if (keep != i) memmove(w.hq + keep * qwords, w.hq + i * qwords, qwords * 8);
     w.chunk.push_back(items[i]);
     w.slots.push_back(job.slot);
+    w.tables.push_back(job.table);
   }
   trace.mark("load queries", w.id);
   if (w.chunk.empty()) return;
@@ -743,6 +761,7 @@ void begin_window(const Server& sv, Window& w, const std::vector<Item>& items, T
     int rc = pirgpu_set_concurrency(sv.ctx, std::max<uint32_t>(before, 16));
     if (!rc) rc = pirgpu_batch_stage_async(sv.ctx, w.hq, sv.nq_expected, count);   // piecewise: group 0 starts after 1 MB
     if (!rc) rc = pirgpu_batch_set_keysets(sv.ctx, w.slots.data(), count);
+    if (!rc && ctx_tables(sv.ctx) > 1) rc = pirgpu_batch_set_tables(sv.ctx, w.tables.data(), count);
     // every group sends its replies to the pinned buffer as soon as they exist: finish_window only waits
     if (!rc) rc = pirgpu_batch_set_host_replies(sv.ctx, w.hr, (uint64_t)w.room * sv.n_reply);
     if (!rc) rc = pirgpu_batch_run(sv.ctx);      // asynchronous: the window's kernels are queued
@@ -1151,12 +1170,26 @@ void pirgpu_wire_forget(pirgpu_ctx* ctx) {
 
 int pirgpu_process_request(pirgpu_ctx* ctx, const uint8_t* request, size_t request_len, uint8_t** response,
                            size_t* response_len) {
+  return pirgpu_process_request_table(ctx, 0, request, request_len, response, response_len);
+}
+
+static std::string table_range_error(pirgpu_ctx* ctx, uint32_t table) {
+  return "table " + std::to_string(table) + " out of range (tables = " + std::to_string(ctx_tables(ctx)) + ")";
+}
+
+int pirgpu_process_request_table(pirgpu_ctx* ctx, uint32_t table, const uint8_t* request, size_t request_len,
+                                 uint8_t** response, size_t* response_len) {
   if (!ctx || (!request && request_len) || !response || !response_len) return PIRGPU_INVALID_ARGUMENT;
   *response = nullptr;
   *response_len = 0;
   Job job;
   job.request = request;
   job.request_len = request_len;
+  job.table = table;
+  if (table >= ctx_tables(ctx)) {   // before anything is queued
+    fail_job(job, PIRGPU_INVALID_ARGUMENT, table_range_error(ctx, table));
+    return finish(ctx, job, response, response_len);
+  }
   std::shared_ptr<Combiner> cb = combiner_for(ctx);
   const int allowed = sets_allowed_for(ctx);   // (asks the context: before the combiner's lock is taken)
   {
@@ -1189,6 +1222,12 @@ int pirgpu_process_request(pirgpu_ctx* ctx, const uint8_t* request, size_t reque
 
 int pirgpu_process_requests(pirgpu_ctx* ctx, uint32_t n, const uint8_t* const* requests, const size_t* request_lens,
                             uint8_t** responses, size_t* response_lens, int* status) {
+  return pirgpu_process_requests_tables(ctx, n, requests, request_lens, nullptr, responses, response_lens, status);
+}
+
+// tables == nullptr: every request on table 0 (pirgpu_process_requests)
+int pirgpu_process_requests_tables(pirgpu_ctx* ctx, uint32_t n, const uint8_t* const* requests, const size_t* request_lens,
+                                   const uint32_t* tables, uint8_t** responses, size_t* response_lens, int* status) {
   if (!ctx || (n && (!requests || !request_lens || !responses || !response_lens || !status))) return PIRGPU_INVALID_ARGUMENT;
   std::vector<Job> jobs(n);
   std::vector<Job*> ptrs(n);
@@ -1199,6 +1238,9 @@ int pirgpu_process_requests(pirgpu_ctx* ctx, uint32_t n, const uint8_t* const* r
     jobs[i].request_len = request_lens[i];
     ptrs[i] = &jobs[i];
     if (!requests[i] && request_lens[i]) fail_job(jobs[i], PIRGPU_INVALID_ARGUMENT, "null request");
+    jobs[i].table = tables ? tables[i] : 0;
+    if (!jobs[i].rc && jobs[i].table >= ctx_tables(ctx))
+      fail_job(jobs[i], PIRGPU_INVALID_ARGUMENT, table_range_error(ctx, jobs[i].table));
   }
   Trace trace;
   std::shared_ptr<Combiner> cb = combiner_for(ctx);

@@ -54,6 +54,8 @@ int pirgpu_query_fetch_begin(struct pirgpu_ctx* ctx, uint64_t* reply, uint64_t c
 int pirgpu_query_fetch_wait(struct pirgpu_ctx* ctx, int part);
 // Queries in flight as last set with pirgpu_set_concurrency (1 by default).
 uint32_t pirgpu_get_concurrency(struct pirgpu_ctx* ctx);
+// the table selected with pirgpu_query_use_table (read and put back around a request)
+uint32_t pirgpu_current_table(struct pirgpu_ctx* ctx);
 #ifdef __cplusplus
 }
 #endif

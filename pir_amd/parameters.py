@@ -136,6 +136,8 @@ class PIRParameters:
     plaintexts_per_item: int = 1      # wide items (not in the reference): planes an item is spread over
     result_primes: int = 0            # modulus-switched results (not in the reference): data primes a level result and
                                       # the reply keep; 0 = all of them
+    tables: int = 0                   # tables (not in the reference): databases of exactly these parameters one server
+                                      # context holds, every query naming its table in the clear; 0 / 1 = one
 
     @property
     def planes(self) -> int:
@@ -172,7 +174,7 @@ class PIRParameters:
 def create_pir_parameters(dbsize: int, bytes_per_item: int = 0, dimensions: int = 1,
                           enc: Optional[EncryptionParams] = None, use_ciphertext_multiplication: bool = False,
                           bits_per_coeff_: int = 0, max_plaintexts_per_item: int = 1,
-                          result_primes: int = 0) -> PIRParameters:
+                          result_primes: int = 0, tables: int = 0) -> PIRParameters:
     """CreatePIRParameters (parameters.cpp:56-107); raises ValueError where it returns InvalidArgument.
 
     max_plaintexts_per_item > 1 (not in the reference) opts in to wide items: an item that does not fit one plaintext is
@@ -180,7 +182,13 @@ def create_pir_parameters(dbsize: int, bytes_per_item: int = 0, dimensions: int 
 
     result_primes = r >= 1 (not in the reference) opts in to modulus-switched results: the server switches every level
     result and the reply down to the first r data primes (r below their number), which shrinks the re-encoding and the
-    reply; the client must be created with the same parameters."""
+    reply; the client must be created with the same parameters.
+
+    tables = T > 1 (not in the reference): everything above describes ONE table -- dbsize items, its plaintexts, its
+    dimensions -- and the server context holds T of them; a query names its table beside the request.  The client is
+    created with these parameters (tables does not concern it) and indexes inside its table."""
+    if tables < 0 or tables >= 1 << 32:
+        raise ValueError("tables must be in [0, 2^32)")
     if enc is None:
         enc = generate_encryption_params()
     N, t = enc.poly_modulus_degree, enc.plain_modulus
@@ -210,7 +218,9 @@ def create_pir_parameters(dbsize: int, bytes_per_item: int = 0, dimensions: int 
         bpi = N * bpc // 8                            # string_encoder.cpp:29-31
         ipp = 1
         num_pt = dbsize
+    if tables > 1 and planes > 1:
+        raise ValueError("tables > 1 with wide items (plaintexts_per_item > 1) is not supported")
     return PIRParameters(num_items=dbsize, num_pt=num_pt, dimensions=calculate_dimensions(num_pt, dimensions),
                          encryption_parameters=enc, bytes_per_item=bpi, items_per_plaintext=ipp,
                          bits_per_coeff=bits_per_coeff_, use_ciphertext_multiplication=use_ciphertext_multiplication,
-                         plaintexts_per_item=planes, result_primes=result_primes)
+                         plaintexts_per_item=planes, result_primes=result_primes, tables=tables)

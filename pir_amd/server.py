@@ -121,13 +121,39 @@ class PIRDatabase:
         else:
             items = list(rawdb)
             n = len(items)
-            if n != self.params.num_items:
-                raise PirGpuError(3, "Database size %d does not match params value %d" % (n, self.params.num_items))
+            if n != self.tables() * self.params.num_items:       # (tables: all of them, table-major)
+                raise PirGpuError(3, "Database size %d does not match params value %d"
+                                  % (n, self.tables() * self.params.num_items))
             width = self.params.bytes_per_item
             if any(len(it) != width for it in items):
                 raise PirGpuError(3, "item size does not match parameters")
             buf = np.frombuffer(b"".join(items), dtype=np.uint8)
         self._check(self.lib.pirgpu_db_load_items(self._h, buf.ctypes.data_as(capi.u8p), n, width))
+
+    def load_table(self, table: int, rawdb) -> None:
+        """Tables: loads or reloads table `table` alone (pirgpu_db_load_table_items) -- num_items items as a uint8
+        array [num_items, bytes_per_item] or a sequence of byte strings; the other tables stay as they are."""
+        if isinstance(rawdb, np.ndarray) and rawdb.dtype == np.uint8 and rawdb.ndim == 2:
+            n, width = rawdb.shape
+            buf = np.ascontiguousarray(rawdb)
+        else:
+            items = list(rawdb)
+            n, width = len(items), self.params.bytes_per_item
+            if any(len(it) != width for it in items):
+                raise PirGpuError(3, "item size does not match parameters")
+            buf = np.frombuffer(b"".join(items), dtype=np.uint8)
+        if buf.size == 0:
+            buf = np.zeros(1, dtype=np.uint8)
+        self._check(self.lib.pirgpu_db_load_table_items(self._h, int(table), buf.ctypes.data_as(capi.u8p), n, width))
+
+    def tables(self) -> int:
+        """Tables of the context (params.tables resolved: at least 1).  Plaintext and item indices of read_plaintext,
+        populate_coeffs, update_plaintexts and update_items are table-major: table * num_pt + pt, table * num_items + i."""
+        return int(self.lib.pirgpu_tables(self._h))
+
+    def table_zero_plaintexts(self, table: int) -> int:
+        """Identically-zero plaintexts of one table: what makes the queries that name it fail as transparent."""
+        return int(self.lib.pirgpu_table_zero_plaintexts(self._h, int(table)))
 
     def populate_coeffs(self, coeffs, first_pt: int = 0) -> None:
         """Plaintexts given as coefficient rows (< t), e.g. IntegerEncoder output (database.cpp:60-82)."""
@@ -276,7 +302,8 @@ class PIRServer:
     def Create(cls, db: PIRDatabase, params: PIRParameters) -> "PIRServer":
         """server.cpp:35-42"""
         full = db._cparams.shard_begin == 0 and db._cparams.shard_end in (0, params.dimensions[0])
-        if full and params.num_pt * getattr(params, "planes", 1) != db.size():
+        # (tables are loaded one by one and served as soon as they are complete: no size to compare with here)
+        if full and db.tables() == 1 and params.num_pt * getattr(params, "planes", 1) != db.size():
             raise PirGpuError(3, "database size mismatch")
         return cls(db, params)
 
@@ -334,6 +361,16 @@ class PIRServer:
         set installed with set_galois_keys."""
         self._check(self.lib.pirgpu_query_use_keyset(self.db.handle, slot))
 
+    def use_table(self, table: int) -> None:
+        """Tables: the table the single-query entry points (process_query, run_staged, multiply, check_ready) answer
+        from; sticky, default 0."""
+        self._check(self.lib.pirgpu_query_use_table(self.db.handle, int(table)))
+
+    def set_batch_tables(self, tables: Sequence[int]) -> None:
+        """One table per query of the staged batch (stage_batch resets them to the table selected with use_table)."""
+        arr = (C.c_uint32 * max(len(tables), 1))(*[int(x) for x in tables])
+        self._check(self.lib.pirgpu_batch_set_tables(self.db.handle, arr, len(tables)))
+
     def set_batch_keysets(self, slots: Sequence[int]) -> None:
         """One key set slot per query of the staged batch (stage_batch resets them to 0)."""
         arr = (C.c_uint32 * len(slots))(*[int(x) for x in slots])
@@ -356,28 +393,33 @@ class PIRServer:
         self._check(self.lib.pirgpu_process_query(self.db.handle, _ptr(q), q.shape[0], _ptr(out), n, C.byref(cnt)))
         return out[: cnt.value]
 
-    def ProcessRequest(self, request: bytes) -> bytes:
-        """server.cpp:44-65: serialized pir.Request -> serialized pir.Response."""
+    def ProcessRequest(self, request: bytes, table: int = 0) -> bytes:
+        """server.cpp:44-65: serialized pir.Request -> serialized pir.Response.  table: the table the request is answered
+        from (contexts with tables; it travels beside the request bytes, not in them)."""
         buf = np.frombuffer(request, dtype=np.uint8)
         resp = C.c_void_p()
         rlen = C.c_size_t(0)
-        self._check(self.lib.pirgpu_process_request(self.db.handle, buf.ctypes.data_as(capi.u8p), len(request),
-                                                    C.byref(resp), C.byref(rlen)))
+        self._check(self.lib.pirgpu_process_request_table(self.db.handle, int(table), buf.ctypes.data_as(capi.u8p),
+                                                          len(request), C.byref(resp), C.byref(rlen)))
         try:
             return C.string_at(resp.value, rlen.value)
         finally:
             self.lib.pirgpu_free(resp)
 
-    def ProcessRequests(self, requests: Sequence[bytes]):
-        """n independent requests (different clients) served together: [(status, response bytes or error text)]."""
+    def ProcessRequests(self, requests: Sequence[bytes], tables: Optional[Sequence[int]] = None):
+        """n independent requests (different clients) served together: [(status, response bytes or error text)].
+        tables: one table per request (contexts with tables; default: table 0 for all)."""
         n = len(requests)
+        if tables is not None and len(tables) != n:
+            raise PirGpuError(3, "%d tables for %d requests" % (len(tables), n))
+        tabs = (C.c_uint32 * max(n, 1))(*[int(t) for t in tables]) if tables is not None else None
         bufs = [np.frombuffer(r, dtype=np.uint8) for r in requests]
         ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
         lens = (C.c_size_t * n)(*[len(r) for r in requests])
         resp = (C.c_void_p * n)()
         rlen = (C.c_size_t * n)()
         status = (C.c_int * n)()
-        self.lib.pirgpu_process_requests(self.db.handle, n, ptrs, lens, resp, rlen, status)
+        self.lib.pirgpu_process_requests_tables(self.db.handle, n, ptrs, lens, tabs, resp, rlen, status)
         out = []
         for i in range(n):
             if status[i] == 0:
@@ -480,11 +522,16 @@ class PIRServer:
     def set_concurrency(self, n_workers: int) -> None:
         self._check(self.lib.pirgpu_set_concurrency(self.db.handle, n_workers))
 
-    def stage_batch(self, queries) -> None:
-        """queries: [count, nq, 2, k, N]"""
+    def stage_batch(self, queries, tables: Optional[Sequence[int]] = None) -> None:
+        """queries: [count, nq, 2, k, N]; tables: one table per query (contexts with tables; default: the table selected
+        with use_table for all)."""
         q = self._cts(queries, 5, "queries")
+        if tables is not None and len(tables) != q.shape[0]:
+            raise PirGpuError(3, "%d tables for %d queries" % (len(tables), q.shape[0]))
         self._batch_count = q.shape[0]
         self._check(self.lib.pirgpu_batch_stage(self.db.handle, _ptr(q), q.shape[1], q.shape[0]))
+        if tables is not None:
+            self.set_batch_tables(tables)
 
     def run_batch(self) -> None:
         self._check(self.lib.pirgpu_batch_run(self.db.handle))
@@ -623,11 +670,11 @@ class PIRServer:
     def reduce_fixup_device_n(self, device_ptr: int, n_cts: int) -> None:
         self._check(self.lib.pirgpu_reduce_fixup_device(self.db.handle, C.c_void_p(device_ptr), n_cts))
 
-    def process_batch(self, queries, n_workers: Optional[int] = None) -> np.ndarray:
+    def process_batch(self, queries, n_workers: Optional[int] = None, tables: Optional[Sequence[int]] = None) -> np.ndarray:
         """All queries of one request: [count, nq, 2, k, N] -> [count, reply_cts, 2, reply_k, N]."""
         if n_workers is not None:
             self.set_concurrency(n_workers)
-        self.stage_batch(queries)
+        self.stage_batch(queries, tables=tables)
         self.run_batch()
         return self.fetch_batch()
 
