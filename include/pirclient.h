@@ -76,7 +76,9 @@ uint32_t pirclient_query_ct_count(const pirclient* c);
 /* PIRClient::createQueryFor -- client.cpp:92-144.  query_out: [query_ct_count][2][k][N]. */
 int pirclient_create_query(pirclient* c, uint64_t index, uint64_t* query_out, size_t cap_cts, uint32_t* n_cts);
 /* The serialized-once keys of initialize() as residues: KSwitchKey for Galois element `elt`
- * (must be one of generate_galois_elts(N)); key_out [k][2][k+1][N]. */
+ * (must be one of generate_galois_elts(N)); key_out [k][2][k+1][N].  elt = 1, which is none of them, names the
+ * relinearisation key (RelinKeys index 0): the element a server in ciphertext-multiplication mode keeps it under
+ * (pirgpu.h, PIRGPU_CREATE_CT_MULTIPLY). */
 int pirclient_galois_key(const pirclient* c, uint32_t elt, uint64_t* key_out);
 /* PIRClient::ProcessReply -- client.cpp:187-255 (ProcessReplyCiphertextDecomp: decrypt, CiphertextReencoder::Decode,
  * repeat once per dimension).  reply [n_cts][2][k][N] -> plaintext_out [N].  With wide items (plaintexts_per_item > 1)

@@ -65,7 +65,8 @@ typedef struct pirgpu_params {
   uint32_t bytes_per_item;                 /* PIRParameters.bytes_per_item */
   uint32_t items_per_plaintext;            /* PIRParameters.items_per_plaintext */
   uint32_t bits_per_coeff;                 /* PIRParameters.bits_per_coeff (0 = floor(log2 t)) */
-  uint32_t use_ciphertext_multiplication;  /* must be 0: CT x CT mode is Unimplemented */
+  uint32_t use_ciphertext_multiplication;  /* 0, or 1 together with PIRGPU_CREATE_CT_MULTIPLY (pirgpu_create_ex); 1 at
+                                              plain pirgpu_create is Unimplemented */
   int32_t device;                          /* HIP device ordinal */
   /* Row sharding for multi-GPU (not in the reference): this context holds the
    * top-level indices [shard_begin, shard_end) of dimension 0 and produces the
@@ -143,6 +144,23 @@ int pirgpu_create(const pirgpu_params* params, pirgpu_ctx** out);
  * context whose int8-MFMA scan is off (fewer than 8 rows, a modulus of 2^55 or more, option scan_mfma = 0) is created,
  * but its first load returns FailedPrecondition before anything is allocated for the database. */
 #define PIRGPU_CREATE_STREAMED_DB 1u
+/* PIRGPU_CREATE_CT_MULTIPLY: the reference's ciphertext-multiplication mode (PIRParameters.use_ciphertext_multiplication,
+ * database.cpp:196-212,238-254).  The upper levels multiply the lower level's results by the
+ * selectors, ciphertext by ciphertext, and relinearise: every level result and the reply are ONE ciphertext
+ * (pirgpu_reply_ct_count = 1 for every d, reply [2][k][N]) instead of (2 ExpansionRatio)^(d-1).  The product is the EXACT
+ * BFV product -- x0 = a0 b0, x1 = a0 b1 + a1 b0, x2 = a1 b1 over Z[x]/(x^N + 1) on the centred lifts, d_i = floor((t x_i +
+ * (Q - 1) / 2) / Q) -- the quantity SEAL's Evaluator::multiply (BEHZ) approximates: a valid BFV ciphertext the reference
+ * client decrypts, NOT claimed bit-equal to a SEAL build; that is why the mode needs this flag beside the field.  The
+ * flag needs use_ciphertext_multiplication = 1 (InvalidArgument otherwise); the field without the flag stays
+ * Unimplemented.  Row sums (scan + inverse transform) and d = 1 are the existing path, bit for bit.  d >= 2 needs the
+ * client's relinearisation key, installed as the key of Galois element 1 of the query's key set (pirgpu_set_galois_key /
+ * pirgpu_keyset_set_key with galois_elt = 1; expansion never uses that element): a query without it is InvalidArgument
+ * ("RelinKeys missing") -- the reference would go on with size-3 ciphertexts, this server does not.  One GPU: with a row or
+ * slot shard, plaintexts_per_item > 1, result_primes, tables > 1, PIRGPU_CREATE_STREAMED_DB, N = 32768, more than 6 data
+ * primes or a chain whose auxiliary base does not hold the product (pirgpu_ctmult_plan) the create is InvalidArgument,
+ * and the multi-GPU entry points return FailedPrecondition on such a context.  Option "ct_scratch_mb" (default 256, before
+ * first use) bounds the scratch the products of one worker / lane run in. */
+#define PIRGPU_CREATE_CT_MULTIPLY 4u   /* (bit 1 stays unassigned: flags 2 and 3 remain InvalidArgument) */
 int pirgpu_create_ex(const pirgpu_params* params, uint32_t flags, pirgpu_ctx** out);
 void pirgpu_destroy(pirgpu_ctx* ctx);
 /* Message of the calling thread's last failed call on this context (falls back to the context's last
@@ -304,6 +322,20 @@ uint64_t pirgpu_reply_ct_words(const pirgpu_ctx* ctx);
 /* Test hook for the modulus switch: cts = n coefficient-form ciphertexts [2][k][N] of canonical residues, out =
  * [n][2][r][N]; any 1 <= r < k on any context, whatever its result_primes (the launcher of the query path). */
 int pirgpu_mod_switch(pirgpu_ctx* ctx, const uint64_t* cts, uint64_t n, uint32_t r, uint64_t* out);
+
+/* Ciphertext-multiplication mode, host only (no context, no device; like pirgpu_plan_table_runs): the auxiliary base a
+ * context of this chain multiplies in -- the k + 2 largest primes == 1 (mod 2N) below 2^bits, bits = the size of the
+ * largest data prime, descending, that are neither data primes nor the special prime -- into aux_primes[0 .. k + 2)
+ * (*n_aux = k + 2), after checking in integers that Q B > 2 (t N (Q - 1)^2 / 2 + Q) and B > 2 (t N Q + 2).  InvalidArgument
+ * (message: pirgpu_create_error) for k > 6, when there are not enough such primes, or when a bound fails. */
+int pirgpu_ctmult_plan(uint32_t poly_modulus_degree, uint32_t num_data_primes, const uint64_t* coeff_modulus,
+                       uint64_t special_prime, uint64_t plain_modulus, uint64_t* aux_primes, uint32_t* n_aux);
+/* Test hooks of the mode (FailedPrecondition on a context without PIRGPU_CREATE_CT_MULTIPLY).  ct_multiply: n pairs of
+ * coefficient-form ciphertexts a, b [n][2][k][N] -> out [n][3][k][N] = (d0, d1, d2), the exact product.  relinearize:
+ * in [n][3][k][N] -> out [n][2][k][N] = (d0 + KS0(d2), d1 + KS1(d2)) with the relinearisation key of the selected key set
+ * (pirgpu_query_use_keyset; the key of Galois element 1). */
+int pirgpu_ct_multiply(pirgpu_ctx* ctx, const uint64_t* a, const uint64_t* b, uint64_t n, uint64_t* out);
+int pirgpu_relinearize(pirgpu_ctx* ctx, const uint64_t* in, uint64_t n, uint64_t* out);
 
 /* Device-resident split of pirgpu_process_query for pipelining and measurement:
  * stage = H2D of the query, run = every kernel of the path (asynchronous on the

@@ -148,6 +148,10 @@ class PIRClient:
         self._check(self.lib.pirclient_galois_key(self._h, int(elt), _ptr(out)))
         return out
 
+    def relin_key(self) -> np.ndarray:
+        """The relinearisation key of initialize() (client.cpp:52) as residues, for PIRServer.set_relin_key."""
+        return self.galois_key(1)
+
     def galois_keys(self) -> Dict[int, np.ndarray]:
         """The keys of initialize() (client.cpp:47) as residues, for PIRServer.set_galois_keys."""
         return {g: self.galois_key(g) for g in generate_galois_elts(self.N)}

@@ -639,6 +639,7 @@ struct pirclient {
   uint32_t planes() const { return prm.plaintexts_per_item > 1 ? prm.plaintexts_per_item : 1; }
   uint64_t plane_bytes() const { return (uint64_t)N * bits_per_coeff / 8; }   // StringEncoder::max_bytes_per_plaintext
   uint64_t plane_reply_ct_count() const {
+    if (prm.use_ciphertext_multiplication) return 1;   // client.cpp:196-203: one ciphertext whatever d
     uint64_t n = 1;
     for (uint32_t d = 1; d < prm.num_dimensions; ++d) n *= reply_ratio();
     return n;
@@ -982,6 +983,10 @@ int pirclient_galois_key(const pirclient* cc, uint32_t elt, uint64_t* key_out) {
   pirclient* c = const_cast<pirclient*>(cc);
   if (!c || !key_out) return PIRGPU_INVALID_ARGUMENT;
   return guarded(c, [&] {
+    if (elt == 1) {   // the relinearisation key, under the element a ciphertext-multiplication server keeps it as
+      memcpy(key_out, c->relin.data(), c->relin.size() * 8);
+      return;
+    }
     auto it = c->galois.find(elt);
     if (it == c->galois.end()) throw Err{PIRGPU_INVALID_ARGUMENT, "no Galois key for element " + std::to_string(elt)};
     memcpy(key_out, it->second.data(), it->second.size() * 8);

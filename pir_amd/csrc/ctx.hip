@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "../../include/pirgpu.h"
+#include "ctmult.h"
 #include "device_params.h"
 #include "host_math.h"
 #include "kernels.h"
@@ -161,6 +162,16 @@ struct Stage {
                                 // the compact switch writes the reply from there to lvl[0]
   bool rows_inverted = false;   // the row sums in lvl[d - 1] are in coefficient form already (slot-sharded step: the
                                 // inverse transform gathered them out of the exchange buffer)
+  uint32_t ksets[kMaxMfmaQueries] = {};   // ciphertext-multiplication mode: key set of every query (its relinearisation key)
+};
+
+// Ciphertext-multiplication mode: the scratch one owner of a multiply (a worker, a lane) runs its products in, allocated
+// on its first level (CT contexts only) and kept.
+struct CtmScratch {
+  uint64_t* buf = nullptr;    // the products of one block of children (post_scan_ctm)
+  size_t words = 0;
+  uint64_t* selc = nullptr;   // coefficient-form selectors of the level being served
+  size_t selc_words = 0;
 };
 
 // One client's Galois keys on the device.  The reference deserialises the keys of every request into a local
@@ -355,6 +366,17 @@ struct pirgpu_ctx {
   hipEvent_t ev_fork = nullptr;             // pirgpu_fork: the main stream's position
   hipEvent_t ev_main_join = nullptr;        // pirgpu_join_stream onto a caller's stream: the main stream's position
 
+  // ciphertext-multiplication mode (pirgpu_create_ex, PIRGPU_CREATE_CT_MULTIPLY): the upper levels
+  // multiply ciphertext by ciphertext (exact BFV product + relinearisation) instead of re-encoding: E = 1 at every level
+  bool ctm = false;
+  uint32_t kb = 0;                          // primes of the auxiliary base (k + 2)
+  uint64_t aux_primes[PIRGPU_MAX_PRIMES]{};
+  DevParams hp_aux{};                       // the auxiliary base as the "data primes" of a second parameter block:
+  DevParams* dp_aux = nullptr;              // ntt_batch transforms at B with the context's own kernels and flavour
+  CtmParams* d_ctm = nullptr;               // constants of the exact base conversions (ctmult.h)
+  uint64_t ctm_scratch_words = (256ull << 20) / 8;   // product scratch per owner (option CT_SCRATCH_MB)
+  std::map<hipStream_t, CtmScratch> ctm_ws; // per owner of a multiply, keyed by its stream
+
   bool prof = false;
   // batch pipeline under profiling: HIP events around the scan launches of the groups (the launch that serves the
   // headline step runs on `scan_wgs_batch` workgroups beside the other lane's kernels -- not the full-chip single-query
@@ -451,17 +473,11 @@ int guarded(pirgpu_ctx* c, F&& f) {
   }
 }
 
-void build_tables(pirgpu_ctx* c) {
-  const uint32_t N = c->N, k = c->k;
-  DevParams& hp = c->hp;
-  hp.N = N;
-  hp.logN = c->logN;
-  hp.k = k;
+// Modulus i of a parameter block: Barrett ratio, twiddle tables (integer and fp64 form) on the device.
+void fill_modulus(pirgpu_ctx* c, DevParams& hp, uint32_t i, uint64_t q) {
+  const uint32_t N = c->N;
   std::vector<Twiddle> tw(N), itw(N);
-  uint64_t qmax = 0;
-  for (uint32_t i = 0; i <= k; ++i) {
-    const uint64_t q = i < k ? c->prm.coeff_modulus[i] : c->prm.special_prime;
-    qmax = std::max(qmax, q);
+  {
     hp.mod[i].q = q;
     hm::u128 ratio = (~(hm::u128)0) / q;  // floor((2^128 - 1) / q) == floor(2^128 / q) for odd q > 1
     hp.mod[i].br_lo = (uint64_t)ratio;
@@ -502,6 +518,20 @@ void build_tables(pirgpu_ctx* c) {
     hp.tab[i].iw1n_f = centered(iw1n);
     hp.tab[i].qd = (double)q;
     hp.tab[i].qinvd = 1.0 / (double)q;
+  }
+}
+
+void build_tables(pirgpu_ctx* c) {
+  const uint32_t N = c->N, k = c->k;
+  DevParams& hp = c->hp;
+  hp.N = N;
+  hp.logN = c->logN;
+  hp.k = k;
+  uint64_t qmax = 0;
+  for (uint32_t i = 0; i <= k; ++i) {
+    const uint64_t q = i < k ? c->prm.coeff_modulus[i] : c->prm.special_prime;
+    qmax = std::max(qmax, q);
+    fill_modulus(c, hp, i, q);
   }
   // NTT arithmetic flavour (ntt_core.h).  PIRGPU_NTT_MODE=0 forces the integer path.
   c->mode = qmax < (1ull << 46) ? kNttF64 : (qmax < (1ull << 49) ? kNttF64Wide : kNttInt);
@@ -570,6 +600,27 @@ void build_tables(pirgpu_ctx* c) {
   hp.lazy_limit = 1u << std::min(30, std::max(0, room));
   c->dp = c->dalloc<DevParams>(1);
   HIP_TRY(hipMemcpy(c->dp, &hp, sizeof(DevParams), hipMemcpyHostToDevice));
+}
+
+// Ciphertext-multiplication mode: the auxiliary base as a parameter block of its own (the transforms at B are the
+// context's ntt_batch in the context's flavour: the auxiliary primes have the size of the largest data prime, so every
+// bound the flavour was chosen by holds for them) and the constants of the base conversions.  After build_tables.
+void build_ctm_tables(pirgpu_ctx* c) {
+  DevParams& hp = c->hp_aux;
+  hp = DevParams{};
+  hp.N = c->N;
+  hp.logN = c->logN;
+  hp.k = c->kb;
+  for (uint32_t i = 0; i < c->kb; ++i) fill_modulus(c, hp, i, c->aux_primes[i]);
+  hp.ntt_mode = c->mode;
+  hp.f64_lazy_inv = c->hp.f64_lazy_inv;
+  hp.lazy_limit = c->hp.lazy_limit;
+  c->dp_aux = c->dalloc<DevParams>(1);
+  HIP_TRY(hipMemcpy(c->dp_aux, &hp, sizeof(DevParams), hipMemcpyHostToDevice));
+  CtmParams cp;
+  ctm::fill_params(cp, c->N, c->k, c->prm.coeff_modulus, c->aux_primes, c->prm.plain_modulus);
+  c->d_ctm = c->dalloc<CtmParams>(1);
+  HIP_TRY(hipMemcpy(c->d_ctm, &cp, sizeof(CtmParams), hipMemcpyHostToDevice));
 }
 
 uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
@@ -817,7 +868,10 @@ void ensure_workspace(pirgpu_ctx* c) {
     // selectors as doubles inside a lane: every query ciphertext must go through ks_last_ntt_kernel (>= 2 items each)
     const uint64_t rem = c->dim_sum % N;
     c->sel_f64 = c->want_sel_f64 && c->mfma_on && c->mode != kNttInt && c->fuse_last_level && c->last_level_ntt &&
-                 !c->split_upper && c->dim_sum >= 2 && rem != 1;
+                 !c->split_upper && c->dim_sum >= 2 && rem != 1 && !c->ctm;   // (the products read u64 selectors)
+    //   CT_SCRATCH_MB  ciphertext-multiplication mode: megabytes of product scratch per worker / lane; the children of a
+    //   level are multiplied in blocks that fit it (at least one child of every query of a group)
+    if (c->ctm) c->ctm_scratch_words = (uint64_t)std::max<int64_t>(1, option(c, "CT_SCRATCH_MB", 256)) * (1ull << 20) / 8;
     //   DB_STREAM_MB  streamed database: megabytes of encoded plaintexts per load chunk, rounded down to whole row bands
     //   (at least one)
     if (c->streamed && c->mfma_on) {
@@ -1189,6 +1243,13 @@ void refuse_switched(const pirgpu_ctx* c) {
                                            "multi-GPU entry points do not serve it"};
 }
 
+// Ciphertext-multiplication mode serves one GPU (the rounding of a product does not commute with the sum over shards).
+void refuse_ctm(const pirgpu_ctx* c) {
+  if (c->ctm)
+    throw Fail{PIRGPU_FAILED_PRECONDITION, "this context multiplies ciphertexts (PIRGPU_CREATE_CT_MULTIPLY): the multi-GPU "
+                                           "entry points do not serve it"};
+}
+
 // d = 1 with result_primes: the scan's sums are level 0 at k primes -- they go to the worker's `last` buffer
 uint64_t* scan_out(const pirgpu_ctx* c, Worker& w) { return c->rp && c->d == 1 ? w.last : w.lvl[c->d - 1]; }
 
@@ -1359,6 +1420,113 @@ void scan_on_device(pirgpu_ctx* c, Worker& w) {
                                  base_out));
 }
 
+// ---- ciphertext-multiplication mode: products of one block of pairs in an owner's scratch ----
+// Regions of the scratch for `cap` pairs.  The tree-form input of the key switch reuses xq, its output yq: both are dead
+// once the tensor / the scale kernel has read them.
+struct CtmRegions {
+  uint64_t *xq, *xb, *yq, *yb, *d, *dig, *prod;
+};
+size_t ctm_pair_words(const pirgpu_ctx* c) {
+  const size_t k = c->k, kb = c->kb;
+  return (4 * k + 4 * kb + 3 * k + 3 * kb + 3 * k + (k + 1) * k + 2 * (k + 1)) * c->N;
+}
+uint32_t ctm_cap_pairs(const pirgpu_ctx* c) {
+  return (uint32_t)std::min<uint64_t>(16383, std::max<uint64_t>(kMaxMfmaQueries, c->ctm_scratch_words / ctm_pair_words(c)));
+}
+CtmRegions ctm_regions(const pirgpu_ctx* c, uint64_t* buf, size_t cap) {
+  const size_t k = c->k, kb = c->kb, N = c->N;
+  CtmRegions r;
+  r.xq = buf;
+  r.xb = r.xq + cap * 4 * k * N;
+  r.yq = r.xb + cap * 4 * kb * N;
+  r.yb = r.yq + cap * 3 * k * N;
+  r.d = r.yb + cap * 3 * kb * N;
+  r.dig = r.d + cap * 3 * k * N;
+  r.prod = r.dig + cap * (k + 1) * k * N;
+  return r;
+}
+CtmScratch& ctm_scratch(pirgpu_ctx* c, hipStream_t st) {
+  if (!c->ctm) throw Fail{PIRGPU_FAILED_PRECONDITION, "not a ciphertext-multiplication context (pirgpu_create_ex with PIRGPU_CREATE_CT_MULTIPLY)"};
+  CtmScratch& ws = c->ctm_ws[st];
+  if (!ws.buf) {
+    ws.words = (size_t)ctm_cap_pairs(c) * ctm_pair_words(c);
+    ws.buf = c->dalloc<uint64_t>(ws.words);
+    uint32_t dmax = 1;
+    for (uint32_t l = 0; l + 1 < c->d; ++l) dmax = std::max(dmax, c->dims[l]);
+    ws.selc_words = (size_t)kMaxMfmaQueries * dmax * c->ctw;
+    ws.selc = c->dalloc<uint64_t>(ws.selc_words);
+  }
+  return ws;
+}
+
+// n pairs (pair p = jj * nq + q: ciphertext a + q * a_qstride + (j0 + jj) * ctw times selector b + (q * dim + (j0 + jj) %
+// dim) * ctw, all coefficient form) -> r.d [n][d0, d2, d1][k][N]: lift, transforms at Q and B, tensor, inverse
+// transforms, scale.
+void ctm_products(pirgpu_ctx* c, hipStream_t st, const CtmRegions& r, const uint64_t* a, uint64_t a_qstride, const uint64_t* b,
+                  uint32_t dim, uint32_t nq, uint32_t j0, uint32_t n) {
+  const uint32_t N = c->N, k = c->k, kb = c->kb;
+  HIP_TRY(launch_ctm_lift(st, c->d_ctm, k, N, a, a_qstride, b, dim, nq, j0, n, r.xq, r.xb));
+  HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp, r.xq, (uint64_t)n * 4 * k, k, 0, false));
+  HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp_aux, r.xb, (uint64_t)n * 4 * kb, kb, 0, false));
+  HIP_TRY(launch_ctm_tensor(st, c->dp, k, N, r.xq, r.yq, n));
+  HIP_TRY(launch_ctm_tensor(st, c->dp_aux, kb, N, r.xb, r.yb, n));
+  HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp, r.yq, (uint64_t)n * 3 * k, k, 0, true));
+  HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp_aux, r.yb, (uint64_t)n * 3 * kb, kb, 0, true));
+  HIP_TRY(launch_ctm_scale(st, c->d_ctm, k, N, r.yq, r.yb, r.d, n));
+}
+
+// The relinearisation key of every query of a group: stored as the key of Galois element 1 of its key set (expansion
+// never uses element 1; the wire codec maps RelinKeys index 0 the same way).
+KeyPtrs relin_keys_for(pirgpu_ctx* c, const uint32_t* ksets, uint32_t nq) {
+  for (uint32_t q = 0; q < nq; ++q) {
+    const uint32_t slot = ksets[q];
+    if (slot >= c->keysets.size() || !c->keysets[slot].keys.count(1))
+      throw Fail{PIRGPU_INVALID_ARGUMENT, "RelinKeys missing: ciphertext multiplication at d >= 2 needs the client's "
+                                          "relinearisation key (installed as the key of Galois element 1)"};
+  }
+  return keys_for(c, 1, ksets, nq);
+}
+
+// r.d [n][d0, d2, d1] -> r.yq [n][2][k][N] = (d0 + KS0(d2), KS1(d2)), canonical: the key-switch launches of one
+// expansion level with Galois element 1 (the identity) and without the tree step; pair p is switched with key.p[p % B].
+void ctm_relinearize(pirgpu_ctx* c, hipStream_t st, const CtmRegions& r, uint32_t n, const KeyPtrs& key) {
+  const uint32_t N = c->N, k = c->k;
+  const uint64_t pw = (uint64_t)k * N;
+  HIP_TRY(launch_tree_convert(st, c->dp, c->mode, r.d, r.xq, (uint64_t)n * 2 * pw, true, 2 * pw, 3 * pw));
+  HIP_TRY(c->ops->ks_digit(st, c->mode, c->dp, k, r.xq, 1, n, r.dig, c->pack40, nullptr, false, false));
+  HIP_TRY(c->ops->ks_mac_intt(st, c->mode, c->dp, k, r.dig, key, n, r.prod, c->pack40, 0, k + 1));
+  HIP_TRY(launch_ks_combine(st, c->dp, c->mode, N, k, r.xq, r.prod, 1, n, 0, false, 0, c->pack40, r.yq, c->pack_bytes));
+  if (c->mode != kNttInt) HIP_TRY(launch_tree_convert(st, c->dp, c->mode, r.yq, r.yq, (uint64_t)n * 2 * pw, false));
+}
+
+// One upper level in ciphertext-multiplication mode (reference database.cpp:196-212,238-254):
+// lvl[l][row] = sum over the children i that exist of relin(mul(lvl[l + 1][row * dims[l] + i], sel_l[i])).
+void post_scan_ctm_level(pirgpu_ctx* c, const Stage& sg, uint32_t l) {
+  const uint32_t N = c->N, k = c->k, nq = sg.n, dim = c->dims[l];
+  const size_t ctw = c->ctw;
+  const uint64_t nch = c->lvl_rows[l + 1], rows = c->lvl_rows[l];
+  hipStream_t st = sg.stream;
+  if (nq > (uint32_t)kMaxMfmaQueries || sg.local_rows || sg.sel_f64) throw Fail{PIRGPU_INTERNAL, "unexpected stage in ciphertext-multiplication mode"};
+  const KeyPtrs key = relin_keys_for(c, sg.ksets, nq);
+  CtmScratch& ws = ctm_scratch(c, st);
+  const uint32_t cap = ctm_cap_pairs(c);
+  const CtmRegions r = ctm_regions(c, ws.buf, cap);
+  // the level's selectors back in coefficient form (canonical residues), query-major
+  if ((size_t)nq * dim * ctw > ws.selc_words) throw Fail{PIRGPU_INTERNAL, "selector scratch undersized"};
+  for (uint32_t q = 0; q < nq; ++q)
+    HIP_TRY(hipMemcpyAsync(ws.selc + (size_t)q * dim * ctw, static_cast<const uint64_t*>(sg.sel.p[q]) + (size_t)c->sv_off[l] * ctw,
+                           (size_t)dim * ctw * 8, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp, ws.selc, (uint64_t)nq * dim * 2 * k, k, 0, true));
+  const uint32_t bj = std::max<uint32_t>(1, cap / nq);   // children per block (of every query of the group)
+  for (uint64_t j0 = 0; j0 < nch; j0 += bj) {
+    const uint32_t nj = (uint32_t)std::min<uint64_t>(bj, nch - j0), n = nj * nq;
+    ctm_products(c, st, r, sg.lvl[l + 1], c->lvl_cts[l + 1] * ctw, ws.selc, dim, nq, (uint32_t)j0, n);
+    ctm_relinearize(c, st, r, n, key);
+    HIP_TRY(launch_ctm_accumulate(st, c->dp, k, N, r.yq, r.d, sg.lvl[l], c->lvl_cts[l] * ctw, dim, nq, (uint32_t)j0, nj,
+                                  (uint32_t)rows));
+  }
+}
+
 // Everything after the scan: inverse NTT of the row sums and the upper recursion levels
 // (reference database.cpp:196-254).  Leaves the reply in lvl[0].
 void post_scan_stage(pirgpu_ctx* c, const Stage& sg, Worker* profiled) {
@@ -1393,6 +1561,11 @@ void post_scan_stage(pirgpu_ctx* c, const Stage& sg, Worker* profiled) {
   // then one kernel folds the chunk sums and applies the inverse NTT
   uint64_t C = 1;  // ciphertexts per child
   for (int l = (int)d - 2; l >= 0; --l) {
+    if (c->ctm) {   // ciphertext by ciphertext: one result ciphertext per node at every level, nothing re-encoded
+      if (l == 0 && profiled) record(c, *profiled, PH_FINAL);
+      post_scan_ctm_level(c, sg, (uint32_t)l);
+      continue;
+    }
     const uint64_t nch = ceil_div(shard_pts, c->stride[l + 1]);
     const uint64_t rows = c->lvl_rows[l];
     // dimension-0 selectors: the query's whole selection vector at index sv_off[0] + shard_begin + i, or (packed
@@ -1467,6 +1640,7 @@ void post_scan_on_device(pirgpu_ctx* c, Worker& w) {
   Stage sg{w.stream, w.lvl.data(), w.pt_buf, 1, MfmaPtrs{}, w.sv_rows != nullptr, &w.up_scratch, &w.up_scratch_words};
   sg.sel.p[0] = w.sv_rows ? w.sv_rows : (w.sv_cur ? w.sv_cur : w.sv_ntt);
   sg.last = w.last;
+  sg.ksets[0] = w.keyset;
   post_scan_stage(c, sg, &w);
 }
 
@@ -1483,6 +1657,7 @@ void run_staged(pirgpu_ctx* c, Worker& w, bool profile) {
   c->prof_cur = -1;
   w.keyset = current_keyset(c);
   w.table = c->cur_table;
+  if (c->ctm && c->d >= 2) (void)relin_keys_for(c, &w.keyset, 1);   // before anything is queued
   // a batch group that borrowed this worker's selection vector (its multiply runs on a lane stream) must be done
   HIP_TRY(hipStreamWaitEvent(w.stream, w.ev_done, 0));
   if (profile) begin_profiled_run(c);
@@ -1527,17 +1702,43 @@ int pirgpu_create_ex(const pirgpu_params* p, uint32_t flags, pirgpu_ctx** out) {
     return code;
   };
   try {
-    if (flags & ~PIRGPU_CREATE_STREAMED_DB)
+    if (flags & ~(PIRGPU_CREATE_STREAMED_DB | PIRGPU_CREATE_CT_MULTIPLY))
       return bail(PIRGPU_INVALID_ARGUMENT, "unknown pirgpu_create_ex flags " + std::to_string(flags));
     c->streamed = (flags & PIRGPU_CREATE_STREAMED_DB) != 0;
+    c->ctm = (flags & PIRGPU_CREATE_CT_MULTIPLY) != 0;
     c->prm = *p;
     const uint32_t N = p->poly_modulus_degree, k = p->num_data_primes;
     if (N < 2048 || N > 32768 || (N & (N - 1)))
       return bail(PIRGPU_INVALID_ARGUMENT, "poly_modulus_degree must be 2048, 4096, 8192, 16384 or 32768");
     if (k < 1 || k > PIRGPU_MAX_PRIMES) return bail(PIRGPU_INVALID_ARGUMENT, "invalid number of data primes");
-    if (p->use_ciphertext_multiplication)
+    if (p->use_ciphertext_multiplication && !c->ctm)
       return bail(PIRGPU_UNIMPLEMENTED,
-                  "use_ciphertext_multiplication is not supported by the MI355X path (decomposition mode only)");
+                  "use_ciphertext_multiplication is not supported by the MI355X path (decomposition mode only) unless the "
+                  "context is created with pirgpu_create_ex and PIRGPU_CREATE_CT_MULTIPLY");
+    if (c->ctm) {
+      // the mode is opt-in twice: the reference's field says what the client expects, the flag that the caller accepts
+      // this project's exact product (not SEAL's BEHZ approximation)
+      if (!p->use_ciphertext_multiplication)
+        return bail(PIRGPU_INVALID_ARGUMENT, "PIRGPU_CREATE_CT_MULTIPLY needs use_ciphertext_multiplication = 1 in the parameters");
+      if (c->streamed)
+        return bail(PIRGPU_INVALID_ARGUMENT, "PIRGPU_CREATE_CT_MULTIPLY with PIRGPU_CREATE_STREAMED_DB is not supported");
+      if (N == 32768)
+        return bail(PIRGPU_INVALID_ARGUMENT, "PIRGPU_CREATE_CT_MULTIPLY is not supported at poly_modulus_degree 32768");
+      if (k > (uint32_t)kCtmMaxQ)
+        return bail(PIRGPU_INVALID_ARGUMENT, "PIRGPU_CREATE_CT_MULTIPLY serves at most 6 data primes (num_data_primes; the "
+                                             "auxiliary base of k + 2 primes must fit 8)");
+      if (p->shard_begin || p->shard_end)
+        return bail(PIRGPU_INVALID_ARGUMENT, "PIRGPU_CREATE_CT_MULTIPLY is served by one GPU: a row shard (shard_begin / "
+                                             "shard_end) is not supported");
+      if (p->slot_begin || p->slot_end)
+        return bail(PIRGPU_INVALID_ARGUMENT, "PIRGPU_CREATE_CT_MULTIPLY is served by one GPU: a slot shard (slot_begin / "
+                                             "slot_end) is not supported");
+      if (p->plaintexts_per_item > 1)
+        return bail(PIRGPU_INVALID_ARGUMENT, "PIRGPU_CREATE_CT_MULTIPLY with plaintexts_per_item > 1 is not supported");
+      if (p->result_primes)
+        return bail(PIRGPU_INVALID_ARGUMENT, "PIRGPU_CREATE_CT_MULTIPLY with result_primes > 0 is not supported");
+      if (p->tables > 1) return bail(PIRGPU_INVALID_ARGUMENT, "PIRGPU_CREATE_CT_MULTIPLY with tables > 1 is not supported");
+    }
     if (p->special_prime == 0)
       return bail(PIRGPU_INVALID_ARGUMENT, "a key-switching special prime is required (SEAL: keyswitching unsupported)");
     for (uint32_t i = 0; i <= k; ++i) {
@@ -1647,8 +1848,18 @@ int pirgpu_create_ex(const pirgpu_params* p, uint32_t flags, pirgpu_ctx** out) {
     HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     c->ops = ntt_ops_for(N);
     if (!c->ops) return bail(PIRGPU_INVALID_ARGUMENT, "poly_modulus_degree must be 2048, 4096, 8192, 16384 or 32768");
+    if (c->ctm) {
+      // the auxiliary base and its bound, in integers, before anything is allocated for it
+      if (const char* why = ctm::plan(N, k, p->coeff_modulus, p->special_prime, p->plain_modulus, c->aux_primes))
+        return bail(PIRGPU_INVALID_ARGUMENT, why);
+      c->kb = k + 2;
+    }
     build_tables(c);
     HIP_TRY(c->ops->configure(c->mode));
+    if (c->ctm) {
+      build_ctm_tables(c);
+      c->E = 1;   // every level result is ONE ciphertext per node: nothing is re-encoded (er keeps ExpansionRatio)
+    }
     c->reply_cts = c->planes;   // every plane answers with its own (2 ExpansionRatio)^(d-1) ciphertexts
     for (uint32_t l = 1; l < c->d; ++l) c->reply_cts *= c->E;
     const uint64_t shard_pts = c->pt_end - c->pt_begin;
@@ -1770,6 +1981,7 @@ static const struct { const char* name; bool early; } kOptions[] = {
     {"SCAN_MFMA", true}, {"SCAN_MFMA_WIDE", true}, {"SCAN_MFMA_TOP4", true}, {"SCAN_MFMA_NQ", true}, {"SCAN_MFMA_SINGLE", true},
     {"HEAD_LEVELS", true}, {"HEAD_MODE", true}, {"SCAN_F64_FOLD", true}, {"SCAN_F64_FOLD_BATCH", true}, {"LOOP_TRANSFORMS", true},
     {"SLOTS_SCAN_WGS", false}, {"SLOTS_GATHER_NTT", false}, {"SLOTS_SCAN_BLK_MAJOR", false}, {"DB_STREAM_MB", true},
+    {"CT_SCRATCH_MB", true},
     // contexts with tables: 0 = one database-pass launch per run of equal tables instead of one per group (A/B);
     // SCAN_LAUNCHES is a COUNTER, not a choice: get returns the database-pass launches the batch pipeline queued so far,
     // set overwrites the count (0 to start over)
@@ -1865,6 +2077,86 @@ int pirgpu_mod_switch(pirgpu_ctx* c, const uint64_t* cts, uint64_t n, uint32_t r
     return PIRGPU_OK;
   });
 }
+int pirgpu_ctmult_plan(uint32_t N, uint32_t k, const uint64_t* coeff_modulus, uint64_t special_prime, uint64_t plain_modulus,
+                       uint64_t* aux_primes, uint32_t* n_aux) {
+  if (!coeff_modulus || !aux_primes) return PIRGPU_INVALID_ARGUMENT;
+  if (n_aux) *n_aux = 0;
+  uint64_t aux[kCtmMaxB] = {};
+  if (const char* why = ctm::plan(N, k, coeff_modulus, special_prime, plain_modulus, aux)) {
+    g_create_error = why;
+    return PIRGPU_INVALID_ARGUMENT;
+  }
+  for (uint32_t i = 0; i < k + 2; ++i) aux_primes[i] = aux[i];
+  if (n_aux) *n_aux = k + 2;
+  return PIRGPU_OK;
+}
+
+int pirgpu_ct_multiply(pirgpu_ctx* c, const uint64_t* a, const uint64_t* b, uint64_t n, uint64_t* out) {
+  return guarded(c, [&]() -> int {
+    if (!c->ctm) return fail(c, PIRGPU_FAILED_PRECONDITION, "not a ciphertext-multiplication context (PIRGPU_CREATE_CT_MULTIPLY)");
+    if ((!a || !b || !out) && n) return fail(c, PIRGPU_INVALID_ARGUMENT, "null buffer");
+    ensure_workspace(c);
+    CtmScratch& ws = ctm_scratch(c, c->stream);
+    const uint32_t cap = ctm_cap_pairs(c);
+    const CtmRegions r = ctm_regions(c, ws.buf, cap);
+    const size_t ctw = c->ctw, pw = (size_t)c->k * c->N;
+    DevScratch in;
+    uint64_t* d_in = in.get<uint64_t>((size_t)std::min<uint64_t>(cap, std::max<uint64_t>(n, 1)) * 2 * ctw * 8);
+    std::vector<uint64_t> host;
+    for (uint64_t p0 = 0; p0 < n; p0 += cap) {
+      const uint32_t m = (uint32_t)std::min<uint64_t>(cap, n - p0);
+      uint64_t* d_b = d_in + (size_t)m * ctw;
+      HIP_TRY(hipMemcpyAsync(d_in, a + p0 * ctw, (size_t)m * ctw * 8, hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(hipMemcpyAsync(d_b, b + p0 * ctw, (size_t)m * ctw * 8, hipMemcpyHostToDevice, c->stream));
+      ctm_products(c, c->stream, r, d_in, 0, d_b, m, 1, 0, m);
+      host.resize((size_t)m * 3 * pw);
+      HIP_TRY(hipMemcpyAsync(host.data(), r.d, host.size() * 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      for (uint32_t p = 0; p < m; ++p) {   // the device keeps (d0, d2, d1)
+        const uint64_t* src = host.data() + (size_t)p * 3 * pw;
+        uint64_t* dst = out + (p0 + p) * 3 * pw;
+        memcpy(dst, src, pw * 8);
+        memcpy(dst + pw, src + 2 * pw, pw * 8);
+        memcpy(dst + 2 * pw, src + pw, pw * 8);
+      }
+    }
+    return PIRGPU_OK;
+  });
+}
+
+int pirgpu_relinearize(pirgpu_ctx* c, const uint64_t* in, uint64_t n, uint64_t* out) {
+  return guarded(c, [&]() -> int {
+    if (!c->ctm) return fail(c, PIRGPU_FAILED_PRECONDITION, "not a ciphertext-multiplication context (PIRGPU_CREATE_CT_MULTIPLY)");
+    if ((!in || !out) && n) return fail(c, PIRGPU_INVALID_ARGUMENT, "null buffer");
+    ensure_workspace(c);
+    const uint32_t slot = current_keyset(c);
+    const KeyPtrs key = relin_keys_for(c, &slot, 1);
+    CtmScratch& ws = ctm_scratch(c, c->stream);
+    const uint32_t cap = ctm_cap_pairs(c);
+    const CtmRegions r = ctm_regions(c, ws.buf, cap);
+    const size_t ctw = c->ctw, pw = (size_t)c->k * c->N;
+    std::vector<uint64_t> host;
+    for (uint64_t p0 = 0; p0 < n; p0 += cap) {
+      const uint32_t m = (uint32_t)std::min<uint64_t>(cap, n - p0);
+      host.resize((size_t)m * 3 * pw);
+      for (uint32_t p = 0; p < m; ++p) {   // (d0, d1, d2) -> the device's (d0, d2, d1)
+        const uint64_t* src = in + (p0 + p) * 3 * pw;
+        uint64_t* dst = host.data() + (size_t)p * 3 * pw;
+        memcpy(dst, src, pw * 8);
+        memcpy(dst + pw, src + 2 * pw, pw * 8);
+        memcpy(dst + 2 * pw, src + pw, pw * 8);
+      }
+      HIP_TRY(hipMemcpyAsync(r.d, host.data(), host.size() * 8, hipMemcpyHostToDevice, c->stream));
+      ctm_relinearize(c, c->stream, r, m, key);
+      // + d1 on component 1: the accumulation of the query path with one child per row
+      HIP_TRY(launch_ctm_accumulate(c->stream, c->dp, c->k, c->N, r.yq, r.d, r.yb, 0, 1, 1, 0, m, m));
+      HIP_TRY(hipMemcpyAsync(out + p0 * ctw, r.yb, (size_t)m * ctw * 8, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return PIRGPU_OK;
+  });
+}
+
 uint32_t pirgpu_expansion_ratio(const pirgpu_ctx* c) { return c ? c->er : 0; }
 uint64_t pirgpu_scan_bytes(const pirgpu_ctx* cc) {
   pirgpu_ctx* c = const_cast<pirgpu_ctx*>(cc);
@@ -2974,6 +3266,7 @@ uint64_t* pirgpu_reply_device_ptr(pirgpu_ctx* c) { return (c && c->ws_ready) ? c
 int pirgpu_reply_copy_to_device(pirgpu_ctx* c, uint64_t* dst, uint64_t cap) {
   return guarded(c, [&]() -> int {
     refuse_switched(c);
+    refuse_ctm(c);
     if (c->workers.empty()) return fail(c, PIRGPU_FAILED_PRECONDITION, "no query has been run");
     Worker& w = c->workers[0];
     if (!w.reply_valid) return fail(c, PIRGPU_FAILED_PRECONDITION, "no query has been run");
@@ -3094,6 +3387,7 @@ int pirgpu_multiply(pirgpu_ctx* c, const uint64_t* sv, uint64_t sv_count, uint64
     w.sv_cur = nullptr;
     w.sv_rows = nullptr;
     w.table = c->cur_table;
+    w.keyset = current_keyset(c);
     multiply_on_device(c, w);
     HIP_TRY(hipMemcpyAsync(reply, w.lvl[0], c->reply_cts * c->rctw * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -3485,6 +3779,8 @@ static void batch_run_mfma(pirgpu_ctx* c, uint32_t count, const uint64_t* ext_sv
       if (direct_reply) lvl_ptrs[0] = reply_base(c) + (size_t)first * rwords;
       Stage sg{ln.stream, lvl_ptrs, ln.pt_buf, B, MfmaPtrs{}, pk != nullptr, &ln.up_scratch, &ln.up_scratch_words};
       sg.last = ln.last;   // result_primes: level 0 lands there, the compact switch writes the replies to lvl_ptrs[0]
+      for (uint32_t q = 0; q < B; ++q)
+        sg.ksets[q] = oq(first + q) < c->bs().batch_keysets.size() ? c->bs().batch_keysets[oq(first + q)] : 0;
       MfmaPtrs col{};
       if (pk) {
         const uint32_t groups_per_rank = (pk->per_rank + kMaxMfmaQueries - 1) / kMaxMfmaQueries;
@@ -3601,6 +3897,11 @@ static void batch_run_impl_body(pirgpu_ctx* c, uint32_t count, const uint64_t* e
   const uint32_t* qtab = qtab_v.empty() ? nullptr : qtab_v.data();
   check_reply_target(c, count);
   if (!ext_sv) check_staged_keysets(c);
+  if (c->ctm && c->d >= 2)   // every query's relinearisation key, before anything is queued
+    for (uint32_t i = 0; i < count; ++i) {
+      const uint32_t slot = i < c->bs().batch_keysets.size() ? c->bs().batch_keysets[i] : 0;
+      (void)relin_keys_for(c, &slot, 1);
+    }
   ensure_packed(c);
   c->prof_cur = -1;
   if (c->mfma_on) {
@@ -3674,6 +3975,7 @@ static void batch_run_impl_body(pirgpu_ctx* c, uint32_t count, const uint64_t* e
     }
     for (uint32_t j = 0; j < n; ++j) {
       Worker& w = c->workers[j];
+      w.keyset = oq(base + j) < c->bs().batch_keysets.size() ? c->bs().batch_keysets[oq(base + j)] : 0;
       post_scan_on_device(c, w);
       HIP_TRY(hipMemcpyAsync(reply_base(c) + (size_t)oq(base + j) * rwords, w.lvl[0], rwords * 8, hipMemcpyDeviceToDevice,
                              w.stream));
@@ -3755,6 +4057,7 @@ static int batch_expand_packed_impl(pirgpu_ctx* c, uint32_t first_query, uint32_
     refuse_wide(c);
     refuse_tables(c);
     refuse_switched(c);
+    refuse_ctm(c);
     ensure_workspace(c);
     if (c->d != 2 || !c->mfma_on)
       return fail(c, PIRGPU_FAILED_PRECONDITION, "packed selector exchange needs d = 2 and the int8-MFMA scan");
@@ -3824,6 +4127,7 @@ int pirgpu_batch_run_packed(pirgpu_ctx* c, const uint8_t* device_packed, uint32_
     refuse_wide(c);
     refuse_tables(c);
     refuse_switched(c);
+    refuse_ctm(c);
     ensure_workspace(c);
     if (c->d != 2 || !c->mfma_on)
       return fail(c, PIRGPU_FAILED_PRECONDITION, "packed selector exchange needs d = 2 and the int8-MFMA scan");
@@ -3898,6 +4202,7 @@ void check_slots_ctx(pirgpu_ctx* c) {
   refuse_wide(c);
   refuse_tables(c);
   refuse_switched(c);
+  refuse_ctm(c);
   ensure_workspace(c);
   if (c->d != 2 || !c->mfma_on || c->mg.nchunks != 1 || c->sb != 0 || c->se != c->dims[0])
     throw Fail{PIRGPU_FAILED_PRECONDITION, "the slot-sharded step needs d = 2, all rows and the int8-MFMA scan in one column chunk"};
@@ -4058,6 +4363,7 @@ int pirgpu_slots_finish_async(pirgpu_ctx* c, const uint64_t* device_rowsums, uin
 int pirgpu_batch_reply_copy_to_device(pirgpu_ctx* c, uint64_t* dst, uint64_t cap) {
   return guarded(c, [&]() -> int {
     refuse_switched(c);
+    refuse_ctm(c);
     if (!c->bs().batch_valid) return fail(c, PIRGPU_FAILED_PRECONDITION, "no batch has been run");
     const uint64_t total = (uint64_t)c->bs().batch_count * c->reply_cts;
     if (!dst || cap < total) return fail(c, PIRGPU_INVALID_ARGUMENT, "reply buffer too small");
@@ -4073,6 +4379,7 @@ int pirgpu_batch_reply_copy_to_device(pirgpu_ctx* c, uint64_t* dst, uint64_t cap
 int pirgpu_batch_reply_copy_to_device_async(pirgpu_ctx* c, uint64_t* dst, uint64_t cap) {
   int rc = guarded(c, [&]() -> int {
     refuse_switched(c);
+    refuse_ctm(c);
     return PIRGPU_OK;
   });
   if (rc) return rc;
@@ -4141,6 +4448,7 @@ int pirgpu_ntt_inverse(pirgpu_ctx* c, uint64_t* polys, uint64_t count, int key_l
 int pirgpu_reduce_fixup_device(pirgpu_ctx* c, uint64_t* device_ptr, uint64_t count) {
   return guarded(c, [&]() -> int {
     refuse_switched(c);
+    refuse_ctm(c);
     if (!device_ptr) return fail(c, PIRGPU_INVALID_ARGUMENT, "null buffer");
     HIP_TRY(launch_reduce_splits(c->stream, c->dp, device_ptr, 1, count * c->ctw, device_ptr));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -4151,6 +4459,7 @@ int pirgpu_reduce_fixup_device(pirgpu_ctx* c, uint64_t* device_ptr, uint64_t cou
 int pirgpu_reduce_fixup_device_async(pirgpu_ctx* c, uint64_t* device_ptr, uint64_t count, void* stream) {
   return guarded(c, [&]() -> int {
     refuse_switched(c);
+    refuse_ctm(c);
     if (!device_ptr) return fail(c, PIRGPU_INVALID_ARGUMENT, "null buffer");
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     HIP_TRY(launch_reduce_splits(st, c->dp, device_ptr, 1, count * c->ctw, device_ptr));

@@ -277,6 +277,8 @@ struct Job {
   bool unverified = false;    // the slot was taken on its fingerprint alone: the key bytes are compared under the GPU work
   bool mismatch = false;      // ... and differed: install this client's keys and serve the request again
   bool relin_checked = false; // the RelinKeys field (if any) has been validated
+  std::vector<uint8_t> key_id;  // ciphertext-multiplication contexts: GaloisKeys bytes + RelinKeys bytes, what identifies
+                                // this client's key set there (key_id_of); empty elsewhere: the GaloisKeys bytes do
   int pins = 0;               // times `slot` is pinned for this request (pirgpu_keyset_pin; once per window in flight
                               // that holds queries of it): unpinned as the windows finish
 };
@@ -292,7 +294,20 @@ struct Server {               // what serving needs to know about a context
   uint32_t nq_expected;
   struct RelinCache* relin = nullptr;   // per context (Combiner)
   size_t relin_keep = 256;
+  bool ctm = false;           // the context multiplies ciphertexts at its upper levels (PIRGPU_CREATE_CT_MULTIPLY, d >= 2):
+                              // a request's RelinKeys are part of its key set (uploaded as the key of Galois element 1)
 };
+
+// What identifies a client's resident key set: the serialized GaloisKeys object; on a ciphertext-multiplication context
+// the RelinKeys object behind it as well (both are self-delimiting SEAL objects), since the set holds both.
+const uint8_t* key_id_of(const Job& job, size_t* len) {
+  if (job.key_id.empty()) {
+    *len = job.pr.galois_keys_len;
+    return job.pr.galois_keys;
+  }
+  *len = job.key_id.size();
+  return job.key_id.data();
+}
 
 // Response.reply (payload.proto:39-42) for one query: n ciphertexts, written straight into the response buffer
 // Upper bound of what append_reply adds for a reply of n ciphertexts (tags and varint lengths: < 32 bytes each)
@@ -494,9 +509,20 @@ void resolve_keys(const Server& sv, Job& job, bool speculative, bool* unverified
   if (unverified) *unverified = false;
   uint32_t slot = 0;
   int rc = 0;
+  if (sv.ctm) {
+    // (the reference would go on with size-3 ciphertexts when the field is empty, server.cpp:53; this server does not)
+    if (!job.pr.relin_keys_len)
+      throw Err{PIRGPU_INVALID_ARGUMENT, "RelinKeys missing: ciphertext multiplication at d >= 2 needs Request.relin_keys"};
+    if (job.key_id.empty() && job.pr.galois_keys_len) {
+      job.key_id.assign(job.pr.galois_keys, job.pr.galois_keys + job.pr.galois_keys_len);
+      job.key_id.insert(job.key_id.end(), job.pr.relin_keys, job.pr.relin_keys + job.pr.relin_keys_len);
+    }
+  }
+  size_t id_len = 0;
+  const uint8_t* id = key_id_of(job, &id_len);
   CtxLock lock(sv.ctx);   // lookup + pin (or claim + upload + pin) are one step with respect to other windows
   if (job.pr.galois_keys_len) {
-    rc = pirgpu_keyset_lookup(sv.ctx, job.pr.galois_keys, job.pr.galois_keys_len, speculative ? 0 : 1, &slot);
+    rc = pirgpu_keyset_lookup(sv.ctx, id, id_len, speculative ? 0 : 1, &slot);
     if (rc) throw Err{rc, pirgpu_last_error(sv.ctx)};
   }
   if (slot) {
@@ -512,7 +538,15 @@ void resolve_keys(const Server& sv, Job& job, bool speculative, bool* unverified
   load_kswitch_keys_parallel(sv.sh, job.pr.galois_keys, job.pr.galois_keys_len,
                              [](size_t n, const std::function<void(size_t)>& fn) { Pool::get().parallel_for(n, 16, fn); },
                              parsed);
-  rc = pirgpu_keyset_claim(sv.ctx, job.pr.galois_keys, job.pr.galois_keys_len, &slot);
+  std::vector<uint64_t> relin_key;   // ciphertext-multiplication contexts: RelinKeys index 0, validated like the rest
+  if (sv.ctm) {
+    load_kswitch_keys(sv.sh, job.pr.relin_keys, job.pr.relin_keys_len, [&](uint64_t i, const uint64_t* key) {
+      if (i == 0) relin_key.assign(key, key + (size_t)sv.sh.k * 2 * (sv.sh.k + 1) * sv.sh.N);
+    });
+    if (relin_key.empty()) throw Err{PIRGPU_INVALID_ARGUMENT, "RelinKeys holds no key"};
+    job.relin_checked = true;
+  }
+  rc = pirgpu_keyset_claim(sv.ctx, id, id_len, &slot);
   if (rc) throw Err{rc, pirgpu_last_error(sv.ctx)};
   {
     std::vector<uint32_t> elts;
@@ -520,6 +554,10 @@ void resolve_keys(const Server& sv, Job& job, bool speculative, bool* unverified
     for (auto& kv : parsed) {
       elts.push_back((uint32_t)(2 * kv.first + 1));
       ptrs.push_back(kv.second.data());
+    }
+    if (sv.ctm) {   // the relinearisation key rides as the key of element 1, which expansion never uses
+      elts.push_back(1);
+      ptrs.push_back(relin_key.data());
     }
     rc = pirgpu_keyset_set_keys(sv.ctx, slot, (uint32_t)elts.size(), elts.data(), ptrs.data());   // one wait for the set
     if (rc) {
@@ -655,7 +693,9 @@ void verify_keys_of(const Server& sv, Window& w) {
     if (job->unverified) {
       const uint8_t* r = resident[i].first;
       const size_t len = resident[i].second;
-      job->mismatch = !(r && len == job->pr.galois_keys_len && memcmp(r, job->pr.galois_keys, len) == 0);
+      size_t id_len = 0;
+      const uint8_t* id = key_id_of(*job, &id_len);
+      job->mismatch = !(r && len == id_len && memcmp(r, id, len) == 0);
       job->unverified = false;
     }
     if (job->pr.relin_keys_len && !job->relin_checked && !job->mismatch) {
@@ -886,6 +926,7 @@ void serve(pirgpu_ctx* ctx, Combiner& cb, int first_set, Job* const* jobs, size_
   for (uint32_t l = 0; l < sv.prm.num_dimensions; ++l) dim_sum += sv.prm.dimensions[l];
   sv.nq_expected = (uint32_t)(dim_sum / sv.sh.N + 1);  // server.cpp:154
   sv.relin = &cb.relin;
+  sv.ctm = sv.prm.use_ciphertext_multiplication != 0 && sv.prm.num_dimensions >= 2;   // (the field is only accepted with the flag)
   Trace trace;
   // this thread's pinned staging and batch state are those of the set it owns (the lone-query and the sequential paths
   // use them too); the calling thread's default selection (0) is restored when the call returns
@@ -956,7 +997,9 @@ void serve(pirgpu_ctx* ctx, Combiner& cb, int first_set, Job* const* jobs, size_
       try {
         bool verified = true;
         run_single(sv, job, job.pr.queries[0], [&]() {   // the byte-for-byte key compare runs under the GPU work
-          if (job.unverified) verified = pirgpu_keyset_verify(sv.ctx, job.slot, job.pr.galois_keys, job.pr.galois_keys_len) != 0;
+          size_t id_len = 0;
+          const uint8_t* id = key_id_of(job, &id_len);
+          if (job.unverified) verified = pirgpu_keyset_verify(sv.ctx, job.slot, id, id_len) != 0;
           if (verified) check_relin_keys(sv, job);       // ... and so does the RelinKeys validation (throws -> the job fails)
         });
         if (!verified) {

@@ -60,11 +60,12 @@ class PIRDatabase:
     """reference database.h:37-133.  Owns the device context and the HBM-resident encoded database."""
 
     def __init__(self, params: PIRParameters, device: int = 0, shard: Optional[Sequence[int]] = None,
-                 slots: Optional[Sequence[int]] = None, streamed: bool = False):
+                 slots: Optional[Sequence[int]] = None, streamed: bool = False, ct_multiplication: bool = False):
         """shard: rows [begin, end) of dimension 0 this context holds; slots: NTT slots [begin, end) of every plaintext
         it holds (multi-GPU partitionings; default: the whole database).  streamed: loads go in
         row bands straight into the scan's operand layout, the u64 staging copy is never allocated (pirgpu_create_ex,
-        DESIGN.md section 6.3)."""
+        DESIGN.md section 6.3).  ct_multiplication: the reference's ciphertext-multiplication mode with this project's
+        exact product (PIRGPU_CREATE_CT_MULTIPLY; needs params.use_ciphertext_multiplication)."""
         self.params = params
         enc = params.encryption_parameters
         self.N = enc.poly_modulus_degree
@@ -73,7 +74,8 @@ class PIRDatabase:
         p = capi.make_params(params, device=device, shard=shard, slots=slots)
         self._cparams = p
         h = C.c_void_p()
-        rc = self.lib.pirgpu_create_ex(C.byref(p), capi.CREATE_STREAMED_DB if streamed else 0, C.byref(h))
+        flags = (capi.CREATE_STREAMED_DB if streamed else 0) | (capi.CREATE_CT_MULTIPLY if ct_multiplication else 0)
+        rc = self.lib.pirgpu_create_ex(C.byref(p), flags, C.byref(h))
         if rc != 0:
             raise PirGpuError(rc, self.lib.pirgpu_create_error().decode())
         self._h = h
@@ -106,9 +108,9 @@ class PIRDatabase:
     # -- reference interface ------------------------------------------------------
     @classmethod
     def Create(cls, params: PIRParameters, rawdb=None, device: int = 0, shard=None, slots=None,
-               streamed: bool = False) -> "PIRDatabase":
+               streamed: bool = False, ct_multiplication: bool = False) -> "PIRDatabase":
         """database.cpp:40-58: Create(params) / Create(rawdb, params)."""
-        db = cls(params, device=device, shard=shard, slots=slots, streamed=streamed)
+        db = cls(params, device=device, shard=shard, slots=slots, streamed=streamed, ct_multiplication=ct_multiplication)
         if rawdb is not None:
             db.populate(rawdb)
         return db
@@ -265,6 +267,26 @@ class PIRDatabase:
         self._check(self.lib.pirgpu_mod_switch(self._h, _ptr(c), c.shape[0], int(r), _ptr(out)))
         return out
 
+    def ct_multiply(self, a, b) -> np.ndarray:
+        """Test hook (ciphertext-multiplication contexts): n pairs [n, 2, k, N] x [n, 2, k, N] -> the exact BFV products
+        [n, 3, k, N] = (d0, d1, d2)."""
+        a, b = _u64(a), _u64(b)
+        if a.ndim != 4 or a.shape[1:] != (2, self.k, self.N) or b.shape != a.shape:
+            raise PirGpuError(3, "operands must both have shape [n, 2, %d, %d], got %s and %s"
+                              % (self.k, self.N, list(a.shape), list(b.shape)))
+        out = np.empty((a.shape[0], 3, self.k, self.N), dtype=np.uint64)
+        self._check(self.lib.pirgpu_ct_multiply(self._h, _ptr(a), _ptr(b), a.shape[0], _ptr(out)))
+        return out
+
+    def relinearize(self, cts) -> np.ndarray:
+        """Test hook: [n, 3, k, N] -> [n, 2, k, N] with the relinearisation key of the selected key set."""
+        c = _u64(cts)
+        if c.ndim != 4 or c.shape[1:] != (3, self.k, self.N):
+            raise PirGpuError(3, "size-3 ciphertexts must have shape [n, 3, %d, %d], got %s" % (self.k, self.N, list(c.shape)))
+        out = np.empty((c.shape[0], 2, self.k, self.N), dtype=np.uint64)
+        self._check(self.lib.pirgpu_relinearize(self._h, _ptr(c), c.shape[0], _ptr(out)))
+        return out
+
     def multiply(self, selection_vector) -> np.ndarray:
         """database.cpp:290-316: selection vector [dim_sum, 2, k, N] (coefficient form) -> reply cts."""
         sv = _u64(selection_vector)
@@ -329,13 +351,28 @@ class PIRServer:
                                   % (self.k, self.k + 1, self.N, list(key.shape)))
             self._check(self.lib.pirgpu_set_galois_key(self.db.handle, int(g), _ptr(key)))
 
+    def set_relin_key(self, key: np.ndarray) -> None:
+        """Ciphertext-multiplication mode: install what SEALDeserialize<RelinKeys> yields (server.cpp:53-58), in the shape
+        of a Galois key.  It is kept as the key of Galois element 1 of the default key set -- after set_galois_keys,
+        which empties that set."""
+        key = _u64(key)
+        if key.shape != (self.k, 2, self.k + 1, self.N):
+            raise PirGpuError(3, "relinearisation key must have shape [%d, 2, %d, %d], got %s"
+                              % (self.k, self.k + 1, self.N, list(key.shape)))
+        self._check(self.lib.pirgpu_set_galois_key(self.db.handle, 1, _ptr(key)))
+
     # -- per-client key sets (keys are per request in the reference, server.cpp:46-48) ------------
     def set_keyset_capacity(self, capacity: int) -> None:
         self._check(self.lib.pirgpu_set_keyset_capacity(self.db.handle, capacity))
 
-    def install_keyset(self, client_id: bytes, galois_keys: Dict[int, np.ndarray]) -> int:
+    def install_keyset(self, client_id: bytes, galois_keys: Dict[int, np.ndarray],
+                       relin_key: Optional[np.ndarray] = None) -> int:
         """Makes one client's Galois keys resident under `client_id` (any bytes that identify the client; the wire
-        layer uses the serialized GaloisKeys object) and returns the slot; a resident set is reused, not re-uploaded."""
+        layer uses the serialized GaloisKeys object) and returns the slot; a resident set is reused, not re-uploaded.
+        relin_key: the client's relinearisation key (ciphertext-multiplication mode), kept as the key of element 1."""
+        if relin_key is not None:
+            galois_keys = dict(galois_keys)
+            galois_keys[1] = relin_key
         ident = np.frombuffer(client_id, dtype=np.uint8)
         slot = C.c_uint32(0)
         self._check(self.lib.pirgpu_keyset_lookup(self.db.handle, ident.ctypes.data_as(capi.u8p), len(client_id), 1,
