@@ -159,7 +159,8 @@ int pirgpu_create(const pirgpu_params* params, pirgpu_ctx** out);
  * slot shard, plaintexts_per_item > 1, result_primes, tables > 1, PIRGPU_CREATE_STREAMED_DB, N = 32768, more than 6 data
  * primes or a chain whose auxiliary base does not hold the product (pirgpu_ctmult_plan) the create is InvalidArgument,
  * and the multi-GPU entry points return FailedPrecondition on such a context.  Option "ct_scratch_mb" (default 256, before
- * first use) bounds the scratch the products of one worker / lane run in. */
+ * first use) bounds the scratch the products of one worker / lane run in; "ct_blocks" is a counter: get returns the
+ * product blocks the upper levels have queued so far, set overwrites the count (0 to start over). */
 #define PIRGPU_CREATE_CT_MULTIPLY 4u   /* (bit 1 stays unassigned: flags 2 and 3 remain InvalidArgument) */
 int pirgpu_create_ex(const pirgpu_params* params, uint32_t flags, pirgpu_ctx** out);
 void pirgpu_destroy(pirgpu_ctx* ctx);

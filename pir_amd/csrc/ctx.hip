@@ -264,6 +264,7 @@ struct pirgpu_ctx {
   std::vector<uint64_t> tbl_loaded, tbl_zero;   // per table: plaintexts loaded / identically zero (tables > 1)
   std::vector<uint8_t> tbl_packed;    // per table: its operand layout is up to date (tables > 1)
   uint64_t scan_launches = 0;         // database-pass launches of the batch pipeline so far (option SCAN_LAUNCHES reads it)
+  uint64_t ct_blocks = 0;             // product blocks post_scan_ctm_level queued so far (option CT_BLOCKS reads it)
   uint32_t bits = 0;           // bits per coefficient for item packing
 
   int device = 0;
@@ -1520,6 +1521,7 @@ void post_scan_ctm_level(pirgpu_ctx* c, const Stage& sg, uint32_t l) {
   const uint32_t bj = std::max<uint32_t>(1, cap / nq);   // children per block (of every query of the group)
   for (uint64_t j0 = 0; j0 < nch; j0 += bj) {
     const uint32_t nj = (uint32_t)std::min<uint64_t>(bj, nch - j0), n = nj * nq;
+    ++c->ct_blocks;
     ctm_products(c, st, r, sg.lvl[l + 1], c->lvl_cts[l + 1] * ctw, ws.selc, dim, nq, (uint32_t)j0, n);
     ctm_relinearize(c, st, r, n, key);
     HIP_TRY(launch_ctm_accumulate(st, c->dp, k, N, r.yq, r.d, sg.lvl[l], c->lvl_cts[l] * ctw, dim, nq, (uint32_t)j0, nj,
@@ -1986,6 +1988,9 @@ static const struct { const char* name; bool early; } kOptions[] = {
     // SCAN_LAUNCHES is a COUNTER, not a choice: get returns the database-pass launches the batch pipeline queued so far,
     // set overwrites the count (0 to start over)
     {"TABLES_ONE_LAUNCH", false}, {"SCAN_LAUNCHES", false},
+    // CT_BLOCKS is a counter of the same kind: the product blocks the upper levels of the ciphertext-multiplication mode
+    // queued so far (one per level and query or group when the level's children fit CT_SCRATCH_MB)
+    {"CT_BLOCKS", false},
 };
 
 int pirgpu_set_option(pirgpu_ctx* c, const char* name, int64_t value) {
@@ -1999,6 +2004,10 @@ int pirgpu_set_option(pirgpu_ctx* c, const char* name, int64_t value) {
         return fail(c, PIRGPU_FAILED_PRECONDITION, "option " + up + " shapes the workspace: set it before the context is first used");
       if (up == "SCAN_LAUNCHES") {
         c->scan_launches = (uint64_t)std::max<int64_t>(0, value);
+        return PIRGPU_OK;
+      }
+      if (up == "CT_BLOCKS") {
+        c->ct_blocks = (uint64_t)std::max<int64_t>(0, value);
         return PIRGPU_OK;
       }
       c->opts[up] = value;
@@ -2019,6 +2028,7 @@ int pirgpu_get_option(pirgpu_ctx* c, const char* name, int64_t* value) {
         bool present = false;
         *value = option(c, o.name, -1, &present);   // -1: not set anywhere, the built-in default applies
         if (up == "SCAN_LAUNCHES") *value = (int64_t)c->scan_launches;
+        if (up == "CT_BLOCKS") *value = (int64_t)c->ct_blocks;
         return PIRGPU_OK;
       }
     return fail(c, PIRGPU_INVALID_ARGUMENT, "unknown option " + up);

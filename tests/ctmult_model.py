@@ -65,8 +65,12 @@ def _unpack(v, n, W):
 
 
 def negacyclic_mul(a, b):
-    """a, b: N signed ints each -> their product in Z[x] / (x^N + 1), by Kronecker substitution."""
+    """a, b: N signed ints each -> their product in Z[x] / (x^N + 1), by Kronecker substitution (a constant operand
+    multiplies coefficient by coefficient)."""
     N = len(a)
+    for u, v in ((a, b), (b, a)):
+        if not any(v[1:]):
+            return [x * v[0] for x in u]
     bound = max(1, max(abs(x) for x in a)) * max(1, max(abs(x) for x in b)) * N
     W = (bound.bit_length() + 2 + 7) // 8 * 8
     full = _unpack(_pack(a, W) * _pack(b, W), 2 * N - 1, W) + [0]
@@ -119,6 +123,14 @@ def plan(N, q, special, t):
     ok = Q * Bp > 2 * (t * N * (Q - 1) ** 2 // 2 + Q) and Bp > 2 * (t * N * Q + 2)
     return aux, ok
 
+
+# The chains of the GPU ladder (tests/test_gpu_ctmult_ladder.py): (id, N, bits of the data primes,
+# bits of t).  The chain is oracle.coeff_modulus_create(N, bits + [max(bits)]), t = oracle.plain_modulus_batching(N, t_bits).
+LADDER = [("k1", 2048, [54], 20), ("k2-tight", 4096, [30, 30], 46), ("k3-mixed", 4096, [30, 36, 40], 20),
+          ("k3-wide", 4096, [47, 47, 47], 20), ("k3-pack7", 8192, [48, 48, 48], 20), ("k5", 4096, [41] * 5, 20),
+          ("k6-f64", 4096, [40] * 6, 20), ("k6-int", 4096, [60] * 6, 59), ("n16384", 16384, [46, 46], 20)]
+# The pairs of hook_inputs a rung with k >= 5 or N = 16384 keeps
+SUB_FAMILY = ["random 0", "all q_j - 1", "full h", "full h + 1", "delta -1", "delta 0", "delta 1"]
 
 # ---------------------------------------------------------------------------------------------- RNS formulation
 
@@ -278,15 +290,17 @@ def process_response_ct(client, params, index, reply):
 # ---------------------------------------------------------------------------------------------- the hook's input family
 
 
-def hook_inputs(q, t, N, rng):
+def hook_inputs(q, t, N, rng, names=None):
     """One batch of pairs for pirgpu_ct_multiply: (names, A [n][2][k][N], B [n][2][k][N]).  Random pairs, all zero, every
     residue q_j - 1, the centring boundary h and h + 1 as constants and as full polynomials (all four polynomials at h in
     every coefficient puts the top coefficient of x0 at the magnitude bound N h^2, of x1 at twice that), and the constants
-    a0 = c((delta - h) / t mod Q), b0 = 1 for delta in {-1, 0, 1}, which put (t x + h) mod Q at Q - 1, 0 and 1."""
+    a0 = c((delta - h) / t mod Q), b0 = 1 for delta in {-1, 0, 1}, which put (t x + h) mod Q at Q - 1, 0 and 1.
+    `names`: keep these pairs only (a sub-family for the expensive chains; the random pairs drawn are the same either
+    way).  check_hook_inputs needs "full h", "full h + 1" and the three "delta" pairs among them."""
     q = [int(x) for x in q]
     k, Q = len(q), prod(q)
     h = (Q - 1) // 2
-    names, As, Bs = [], [], []
+    keep, names, As, Bs = names, [], [], []
 
     def const_ct(v0, v1, full=False):
         ct = np.zeros((2, k, N), dtype=np.uint64)
@@ -305,6 +319,8 @@ def hook_inputs(q, t, N, rng):
         return ct
 
     def add(name, A, B):
+        if keep is not None and name not in keep:
+            return
         names.append(name)
         As.append(A)
         Bs.append(B)
@@ -321,6 +337,7 @@ def hook_inputs(q, t, N, rng):
     add("full h + 1", const_ct(h + 1, h + 1, True), const_ct(h + 1, h + 1, True))
     for delta in (-1, 0, 1):
         add("delta %d" % delta, const_ct((delta - h) * pow(t, -1, Q) % Q, 0), const_ct(1, 0))
+    assert keep is None or sorted(keep) == sorted(names), "unknown pair name in names="
     return names, np.stack(As), np.stack(Bs)
 
 

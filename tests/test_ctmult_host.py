@@ -1,6 +1,7 @@
 """Host side of the ciphertext-multiplication mode, no GPU: pirgpu_ctmult_plan against the Python
-restatement in tests/ctmult_model.py over the supported chains, the refusals that need no device, the new symbols and
-the flag value."""
+restatement in tests/ctmult_model.py over the supported chains and the chains of the GPU ladder, the bound at its edge
+(the largest plain modulus two 30-bit primes take), the refusals that need no device, the new symbols and the flag
+value."""
 import ctypes as C
 import os
 import re
@@ -29,7 +30,7 @@ CHAINS = [(2048, [54], 16), (2048, [27, 27], 16), (4096, [36, 36], 16), (4096, [
           (16384, [48, 48, 48, 49, 49], 20), (16384, [60] * 6, 59), (8192, [30, 40, 50], 20)]
 
 
-@pytest.mark.parametrize("N,bits,t_bits", CHAINS)
+@pytest.mark.parametrize("N,bits,t_bits", CHAINS + [c[1:] for c in M.LADDER], ids=[None] * len(CHAINS) + [c[0] for c in M.LADDER])
 def test_plan_matches_the_restatement(N, bits, t_bits):
     moduli = oracle.coeff_modulus_create(N, bits + [max(bits)])
     q, special = moduli[:-1], moduli[-1]
@@ -44,6 +45,38 @@ def test_plan_matches_the_restatement(N, bits, t_bits):
         assert oracle.is_prime(b) and b % (2 * N) == 1 and b.bit_length() == top
     Q, B = M.prod(q), M.prod(aux)
     assert Q * B > 2 * (t * N * (Q - 1) ** 2 // 2 + Q) and B > 2 * (t * N * Q + 2)
+
+
+def test_the_bound_is_tight_for_two_30_bit_primes():
+    """(4096, [30, 30]): of the batching primes of 14 ... 60 bits the plan takes every one up to 46 bits and none above,
+    in the library and in the restatement alike.  At 46 bits both bounds are within a factor 8 of failing -- Q B over
+    t N (Q - 1)^2 + 2 Q is about 2^2, B over 2 (t N Q + 2) about 2^1 -- against 2^43 for the default chain and a 16-bit t:
+    the GPU rung "k2-tight" multiplies at this t, where a bound too generous by more than that would give wrong bits."""
+    N = 4096
+    moduli = oracle.coeff_modulus_create(N, [30, 30, 30])
+    q, special = moduli[:-1], moduli[-1]
+    verdict = {}
+    for t_bits in range(14, 61):
+        try:
+            t = oracle.plain_modulus_batching(N, t_bits)
+        except ValueError:                      # no prime == 1 mod 2N of that size (14 bits)
+            continue
+        rc, aux, msg = plan(N, q, special, t)
+        want, ok = M.plan(N, q, special, t)
+        assert (rc == 0) == ok, t_bits
+        if ok:
+            assert aux == want
+        else:
+            assert rc == capi.INVALID_ARGUMENT and aux == [] and "auxiliary base" in msg, t_bits
+        verdict[t_bits] = ok
+    assert len(verdict) >= 40 and 60 in verdict
+    assert max(b for b, ok in verdict.items() if ok) == 46
+    assert [b for b, ok in verdict.items() if not ok] == [b for b in verdict if b > 46]
+    t = oracle.plain_modulus_batching(N, 46)
+    Q, B = M.prod(q), M.prod(M.plan(N, q, special, t)[0])
+    slack1, slack2 = Q * B / (t * N * (Q - 1) ** 2 + 2 * Q), B / (2 * (t * N * Q + 2))
+    print("46-bit t: slack of the two bounds 2^%.2f and 2^%.2f" % (np.log2(slack1), np.log2(slack2)))
+    assert 1 < slack1 < 8 and 1 < slack2 < 4
 
 
 def test_the_special_prime_is_skipped():

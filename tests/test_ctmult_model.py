@@ -27,10 +27,11 @@ def test_product_decrypts_to_the_product_of_the_plaintexts():
     assert np.array_equal(cl.decrypt(ct), want)
 
 
-@pytest.mark.parametrize("N,bits,t_bits", [(4096, [36, 36], 16), (8192, [43, 43, 44, 44], 42), (4096, [60, 60, 60], 20)])
+@pytest.mark.parametrize("N,bits,t_bits", [(4096, [36, 36], 16), (8192, [43, 43, 44, 44], 42), (4096, [60, 60, 60], 20)] +
+                         [c[1:] for c in M.LADDER], ids=[None] * 3 + [c[0] for c in M.LADDER])
 def test_rns_formulation_agrees_with_the_integers(N, bits, t_bits):
     """Polynomials of 64 coefficients (the formulation is per coefficient; the bounds of the plan are those of the full
-    ring degree, which cover the shorter products)."""
+    ring degree, which cover the shorter products), on the chains of the GPU ladder too."""
     moduli = oracle.coeff_modulus_create(N, bits + [max(bits)])
     q, t = moduli[:-1], oracle.plain_modulus_batching(N, t_bits)
     aux, ok = M.plan(N, q, moduli[-1], t)
@@ -43,6 +44,23 @@ def test_rns_formulation_agrees_with_the_integers(N, bits, t_bits):
             want = M.to_residues(M.crt_lift(A[i, c], q), aux)
             assert np.array_equal(M.rns_lift(A[i, c], q, aux), want), name
         assert np.array_equal(M.rns_multiply_ct(A[i], B[i], q, aux, t), M.multiply_ct(A[i], B[i], q, t)), name
+
+
+def test_rns_formulation_at_the_full_degree_on_the_tightest_chain():
+    """(4096, [30, 30]) with the 46-bit t, the largest the plan takes (tests/test_ctmult_host.py): N = 4096 coefficients at h,
+    which 64 coefficients cannot reach -- the top coefficient of x1 is 2 N h^2, the magnitude the bounds are stated for."""
+    N = 4096
+    moduli = oracle.coeff_modulus_create(N, [30, 30, 30])
+    q, t = moduli[:-1], oracle.plain_modulus_batching(N, 46)
+    aux, ok = M.plan(N, q, moduli[-1], t)
+    assert ok
+    names, A, B = M.hook_inputs(q, t, N, np.random.default_rng(N), names=["full h", "full h + 1"])
+    assert names == ["full h", "full h + 1"]
+    h = (M.prod(q) - 1) // 2
+    for i, name in enumerate(names):
+        x = M.tensor(A[i], B[i], q)
+        assert x[0][N - 1] == N * h * h and x[1][N - 1] == 2 * N * h * h, name
+        assert np.array_equal(M.rns_multiply_ct(A[i], B[i], q, aux, t), M.scaled_residues(x, q, t)), name
 
 
 TUPLES = [(4096, 16, 9, 10, [1, 5]), (4096, 16, 500, 6, [9, 125]), (8192, 42, 87, 0, [5, 33, 86])]

@@ -5,7 +5,8 @@ the CPU model of tests/ctmult_model.py:
     three remainders around the rounding step -- in the default flavour, the integer flavour and at N = 8192 / k = 4;
     pirgpu_relinearize on its outputs with a random key;
   * whole replies against process_query_ct: d = 2 on the 64-bit and the int8-MFMA scan, d = 3, d = 1, a batch of 9 under
-    two clients' keys, a database that ends mid-row;
+    two clients' keys, a database that ends mid-row, a level multiplied in two blocks (the block split at large:
+    tests/test_gpu_ctmult_blocks.py; every k, flavour and width of the hooks: tests/test_gpu_ctmult_ladder.py);
   * the wire round trip with the product client on the reference's three d = 2 tuples, seeded and expanded keys;
   * the refusals, and the untouched default.
 
@@ -36,9 +37,11 @@ def ct_params(p):
     return pp
 
 
-def ct_server(s, keys=True, **kw):
+def ct_server(s, keys=True, ct_scratch_mb=None, **kw):
     pp = ct_params(s.params)
     db = pir_amd.PIRDatabase.Create(pp, ct_multiplication=True, **kw)
+    if ct_scratch_mb is not None:
+        db.set_option("ct_scratch_mb", ct_scratch_mb)       # (shapes the workspace: before the first use)
     db.populate(s.raw)
     srv = pir_amd.PIRServer(db, pp)
     if keys:
@@ -125,20 +128,33 @@ def test_multiply_and_relinearize_hooks_match_the_model(monkeypatch, N, moduli, 
 
 # ------------------------------------------------------------------------------------------------ whole replies
 
+_SINGLE = {}
+
+
+def single_case(dbsize, d):
+    """setup, index, query and the model's reply of one single-query shape, computed once (the block tests run the
+    d = 2, 100-item case again under a small scratch)."""
+    if (dbsize, d) not in _SINGLE:
+        # (9 items: the reference's tuple, correctness_test.cpp:99 -- 16-bit t, 10 bits per coefficient, index 5)
+        s = setup(dbsize, d, bpc=10 if dbsize == 9 else 0)
+        index = 5 if dbsize == 9 else dbsize - 2
+        q = s.client.create_query_for(s.params, index)
+        _SINGLE[dbsize, d] = (s, index, q, expected(s, q))
+    return _SINGLE[dbsize, d]
+
+
 @pytest.mark.parametrize("dbsize,d,mfma", [(9, 2, 0), (100, 2, 1), (27, 3, 1), (10, 1, 0)])
 def test_single_queries_match_the_model(dbsize, d, mfma):
-    # (9 items: the reference's tuple, correctness_test.cpp:99 -- 16-bit t, 10 bits per coefficient, index 5)
-    s = setup(dbsize, d, bpc=10 if dbsize == 9 else 0)
+    s, index, q, want = single_case(dbsize, d)
     assert s.params.dimensions == {9: [3, 3], 100: [10, 10], 27: [3, 3, 3], 10: [10]}[dbsize]
     db, srv = ct_server(s, keys=d > 1)
     if d == 1:
         srv.set_galois_keys(s.galois_keys)      # d = 1 needs no relinearisation key
     assert db.reply_ct_count() == 1 and db.reply_ct_words() == 2 * s.orc.k * s.orc.N
     assert srv.scan_info()["mfma"] == mfma
-    index = 5 if dbsize == 9 else dbsize - 2
-    q = s.client.create_query_for(s.params, index)
-    want = expected(s, q)
+    db.set_option("ct_blocks", 0)
     got = srv.process_query(q)
+    assert db.get_option("ct_blocks") == d - 1          # the default scratch holds every level in one block
     assert got.shape == want.shape == (1, 2, s.orc.k, s.orc.N)
     bad = np.argwhere(got != want)
     assert bad.size == 0, "first mismatch at [ct, poly, residue, coefficient] = %s" % bad[:1].tolist()
@@ -163,41 +179,58 @@ def test_database_ending_mid_row():
     db.close()
 
 
-def test_batch_of_nine_under_two_clients_keys():
-    """8 x 2 plaintexts (the int8-MFMA scan, groups of 8 + 1 on the lanes): every product of a group is relinearised with
-    its own query's key."""
-    s = setup(16, 2, dims=[8, 2])
-    db, srv = ct_server(s)
-    assert srv.scan_info()["mfma"] == 1
-    other = Client(s.orc, seed=7)
-    clients = [(s.client, s.galois_keys, s.rk), (other, other.galois_keys(), M.relin_key(other))]
+_NINE = []
+
+
+def nine_case():
+    """8 x 2 plaintexts, 9 queries alternating two clients' key sets, and the model's reply to each with its own keys:
+    (setup, [(client, galois keys, relinearisation key)] * 2, queries [9], replies [9]), computed once."""
+    if not _NINE:
+        s = setup(16, 2, dims=[8, 2])
+        other = Client(s.orc, seed=7)
+        clients = [(s.client, s.galois_keys, s.rk), (other, other.galois_keys(), M.relin_key(other))]
+        idx = [(5 * i + 3) % 16 for i in range(9)]
+        qs = np.stack([clients[i % 2][0].create_query_for(s.params, x) for i, x in enumerate(idx)])
+        want = [expected(s, qs[i], clients[i % 2][1], clients[i % 2][2]) for i in range(9)]
+        _NINE.append((s, clients, qs, want))
+    return _NINE[0]
+
+
+def run_nine(srv, clients, qs):
+    """The batch of nine_case on one server: key sets installed, groups of 8 + 1 on the lanes -> replies [9]."""
     slots = [srv.install_keyset(b"client-%d" % i, keys, relin_key=rk) for i, (_, keys, rk) in enumerate(clients)]
-    idx = [(5 * i + 3) % 16 for i in range(9)]
-    qs = np.stack([clients[i % 2][0].create_query_for(s.params, x) for i, x in enumerate(idx)])
     srv.set_concurrency(8)
     srv.stage_batch(qs)
     srv.set_batch_keysets([slots[i % 2] for i in range(9)])
     srv.run_batch()
-    out = srv.fetch_batch()
+    return srv.fetch_batch()
+
+
+def test_batch_of_nine_under_two_clients_keys():
+    """8 x 2 plaintexts (the int8-MFMA scan, groups of 8 + 1 on the lanes): every product of a group is relinearised with
+    its own query's key."""
+    s, clients, qs, want = nine_case()
+    db, srv = ct_server(s)
+    assert srv.scan_info()["mfma"] == 1
+    out = run_nine(srv, clients, qs)
     assert out.shape == (9, 1, 2, s.orc.k, s.orc.N)
     for i in range(9):
-        cl, keys, rk = clients[i % 2]
-        assert np.array_equal(out[i], expected(s, qs[i], keys, rk)), "query %d of the batch" % i
+        assert np.array_equal(out[i], want[i]), "query %d of the batch" % i
+    assert db.get_option("ct_blocks") == 2              # one block per group: 8 x 8 and 1 x 8 pairs
     db.close()
 
 
 def test_small_scratch_blocks_give_the_same_bits():
-    """ct_scratch_mb = 1: one child of every query per block, the sums carried from block to block."""
-    s = setup(9, 2)
-    pp = ct_params(s.params)
-    db = pir_amd.PIRDatabase.Create(pp, ct_multiplication=True)
-    db.set_option("ct_scratch_mb", 1)
-    db.populate(s.raw)
-    srv = pir_amd.PIRServer(db, pp)
-    srv.set_galois_keys(s.galois_keys)
-    srv.set_relin_key(s.rk)
-    q = s.client.create_query_for(s.params, 4)
-    assert np.array_equal(srv.process_query(q), expected(s, q))
+    """ct_scratch_mb = 1 on 10 x 10 plaintexts: the scratch is floored at 8 pairs, so the 10 children of the one upper
+    level are multiplied in the blocks {0 .. 7} and {8, 9}, the row's sum carried from the first to the second.  The
+    query selects row 9: its product is in the second block, and the reply is right only if the first block's sum
+    (the noise of eight products with encryptions of zero) is carried."""
+    s, index, q, want = single_case(100, 2)
+    assert index // 10 == 9
+    db, srv = ct_server(s, ct_scratch_mb=1)
+    got = srv.process_query(q)
+    assert db.get_option("ct_blocks") == 2
+    assert np.array_equal(got, want)
     db.close()
 
 
