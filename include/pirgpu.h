@@ -162,6 +162,16 @@ int pirgpu_create(const pirgpu_params* params, pirgpu_ctx** out);
  * first use) bounds the scratch the products of one worker / lane run in; "ct_blocks" is a counter: get returns the
  * product blocks the upper levels have queued so far, set overwrites the count (0 to start over). */
 #define PIRGPU_CREATE_CT_MULTIPLY 4u   /* (bit 1 stays unassigned: flags 2 and 3 remain InvalidArgument) */
+/* PIRGPU_CREATE_CT_DEFERRED: deferred rounding ("lazy relinearisation"), a second definition of the
+ * upper levels of PIRGPU_CREATE_CT_MULTIPLY and valid only together with it (alone: InvalidArgument).  The tensor
+ * products of a row's children are summed over the integers before the one rounding: X_m = sum_i x_m,i, D_m = floor((t X_m
+ * + (Q - 1) / 2) / Q), row = relinearise(D) -- one scale and one key switch per row and query instead of one per child.
+ * The reply is a valid ciphertext of the same item with the same noise budget to within a rounding, NOT the bits of the
+ * per-child form.  A sum of n = max(dimensions[l], l < d - 1) products must fit the auxiliary base
+ * (pirgpu_ctmult_plan_terms): InvalidArgument at create otherwise.  Everything PIRGPU_CREATE_CT_MULTIPLY refuses stays
+ * refused; d = 1 and the row sums are unchanged.  Counter option "ct_relins" (get / set like "ct_blocks", both forms of
+ * the mode): the ciphertexts the upper levels have key-switched so far -- pairs, or rows x queries here. */
+#define PIRGPU_CREATE_CT_DEFERRED 8u
 int pirgpu_create_ex(const pirgpu_params* params, uint32_t flags, pirgpu_ctx** out);
 void pirgpu_destroy(pirgpu_ctx* ctx);
 /* Message of the calling thread's last failed call on this context (falls back to the context's last
@@ -335,7 +345,17 @@ int pirgpu_ctmult_plan(uint32_t poly_modulus_degree, uint32_t num_data_primes, c
  * coefficient-form ciphertexts a, b [n][2][k][N] -> out [n][3][k][N] = (d0, d1, d2), the exact product.  relinearize:
  * in [n][3][k][N] -> out [n][2][k][N] = (d0 + KS0(d2), d1 + KS1(d2)) with the relinearisation key of the selected key set
  * (pirgpu_query_use_keyset; the key of Galois element 1). */
+/* pirgpu_ctmult_plan with the bound of a sum of up to `terms` products (deferred rounding): Q B > t terms N (Q - 1)^2 + 2 Q
+ * and B > 2 (t terms N Q + 2).  terms = 1 is pirgpu_ctmult_plan. */
+int pirgpu_ctmult_plan_terms(uint32_t poly_modulus_degree, uint32_t num_data_primes, const uint64_t* coeff_modulus,
+                             uint64_t special_prime, uint64_t plain_modulus, uint64_t terms, uint64_t* aux_primes,
+                             uint32_t* n_aux);
 int pirgpu_ct_multiply(pirgpu_ctx* ctx, const uint64_t* a, const uint64_t* b, uint64_t n, uint64_t* out);
+/* Test hook of the deferred rounding, on any ciphertext-multiplication context: n pairs a, b [n][2][k][N] in coefficient
+ * form -> out [3][k][N] = (D0, D1, D2) of the SUM of their tensor products, run as one row of n children through the
+ * blocks of the query path (ct_scratch_mb, carried accumulators, the row-sum kernel, one scale).  InvalidArgument when the
+ * auxiliary base does not hold a sum of n products. */
+int pirgpu_ct_multiply_sum(pirgpu_ctx* ctx, const uint64_t* a, const uint64_t* b, uint64_t n, uint64_t* out);
 int pirgpu_relinearize(pirgpu_ctx* ctx, const uint64_t* in, uint64_t n, uint64_t* out);
 
 /* Device-resident split of pirgpu_process_query for pipelining and measurement:

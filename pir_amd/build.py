@@ -10,7 +10,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpirgpu.so")
 SOURCES = ["kernels.hip", "scan_mfma.hip", "ctx.hip", "wire.cpp", "wire_codec.cpp",
            "ntt_ring32k.hip",        # N = 32768: two-pass transforms, integer flavour only (built once)
-           "ctmult.hip"]             # ciphertext-multiplication mode: lift, tensor, scale, accumulate
+           "ctmult.hip",             # ciphertext-multiplication mode: lift, tensor, scale, accumulate
+           "ctmult_rowsum.hip"]      # ... its deferred rounding: the tensor summed over the children of a row
 NTT_SOURCE = "ntt_kernels.hip"      # compiled once per ring degree (-DPIRGPU_LOGN)
 NTT_LOGNS = [11, 12, 13, 14]
 NTT_PACK_BYTES = [5, 6, 7]          # ... and once per width of the packed key-switch intermediates (-DPIRGPU_PACK_BYTES)

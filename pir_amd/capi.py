@@ -11,6 +11,7 @@ MAX_PRIMES, MAX_DIMS = 8, 8
 OK, INVALID_ARGUMENT, FAILED_PRECONDITION, UNIMPLEMENTED, INTERNAL = 0, 3, 9, 12, 13
 CREATE_STREAMED_DB = 1          # pirgpu_create_ex flags
 CREATE_CT_MULTIPLY = 4
+CREATE_CT_DEFERRED = 8
 
 u64p = C.POINTER(C.c_uint64)
 u8p = C.POINTER(C.c_uint8)
@@ -170,7 +171,10 @@ SIGNATURES = {
     "pirgpu_reply_ct_words": (C.c_uint64, [C.c_void_p]),
     "pirgpu_mod_switch": (C.c_int, [C.c_void_p, u64p, C.c_uint64, C.c_uint32, u64p]),
     "pirgpu_ctmult_plan": (C.c_int, [C.c_uint32, C.c_uint32, u64p, C.c_uint64, C.c_uint64, u64p, C.POINTER(C.c_uint32)]),
+    "pirgpu_ctmult_plan_terms": (C.c_int, [C.c_uint32, C.c_uint32, u64p, C.c_uint64, C.c_uint64, C.c_uint64, u64p,
+                                           C.POINTER(C.c_uint32)]),
     "pirgpu_ct_multiply": (C.c_int, [C.c_void_p, u64p, u64p, C.c_uint64, u64p]),
+    "pirgpu_ct_multiply_sum": (C.c_int, [C.c_void_p, u64p, u64p, C.c_uint64, u64p]),
     "pirgpu_relinearize": (C.c_int, [C.c_void_p, u64p, C.c_uint64, u64p]),
     "pirgpu_query_stage": (C.c_int, [C.c_void_p, u64p, C.c_uint32]),
     "pirgpu_query_stage_async": (C.c_int, [C.c_void_p, u64p, C.c_uint32]),

@@ -1,5 +1,5 @@
 // ctmult.h -- ciphertext-multiplication mode: the auxiliary base, the constants of the exact base
-// conversions and the launch wrappers of ctmult.hip.
+// conversions and the launch wrappers of ctmult.hip and ctmult_rowsum.hip (deferred rounding).
 //
 // The product of two ciphertexts is the EXACT BFV product: x0 = a0 b0, x1 = a0 b1 + a1 b0, x2 = a1 b1 over Z[x]/(x^N + 1)
 // on the centred lifts, d_i = floor((t x_i + h) / Q), h = (Q - 1) / 2.  The ring products run as dyadic products at the
@@ -117,11 +117,14 @@ inline Nat product(const uint64_t* p, uint32_t n) {
 // prime, found descending, that are neither in the chain nor the special prime.  Returns 0, or a message: more than
 // kCtmMaxQ data primes, not enough primes of that size, or a base too small for
 //   Q B > 2 (t N (Q - 1)^2 / 2 + Q)   (t x + h does not wrap at Q B)   and   B > 2 (t N Q + 2)   (nor the quotient at B).
-inline const char* plan(uint32_t N, uint32_t k, const uint64_t* q, uint64_t special, uint64_t t, uint64_t* aux) {
+// terms = n > 1 (deferred rounding: x is a sum of up to n tensor products):
+//   Q B > t n N (Q - 1)^2 + 2 Q   and   B > 2 (t n N Q + 2).
+inline const char* plan(uint32_t N, uint32_t k, const uint64_t* q, uint64_t special, uint64_t t, uint64_t* aux,
+                        uint64_t terms = 1) {
   if (k < 1 || k > (uint32_t)kCtmMaxQ) return "ciphertext multiplication serves at most 6 data primes (the auxiliary base of k + 2 primes must fit 8)";
   uint64_t qmax = 0;
   for (uint32_t j = 0; j < k; ++j) qmax = std::max(qmax, q[j]);
-  if (qmax < 2 || N < 2 || (N & (N - 1))) return "invalid chain";
+  if (qmax < 2 || N < 2 || (N & (N - 1)) || terms < 1) return "invalid chain";
   const uint32_t bits = 64 - (uint32_t)__builtin_clzll(qmax);
   uint32_t found = 0;
   for (uint64_t v = (1ull << bits) - 2ull * N + 1; found < k + 2 && v > (1ull << (bits - 1)); v -= 2ull * N) {
@@ -133,12 +136,14 @@ inline const char* plan(uint32_t N, uint32_t k, const uint64_t* q, uint64_t spec
   if (found < k + 2) return "ciphertext multiplication: not enough NTT-friendly primes of the data primes' size for the auxiliary base";
   const Nat Q = product(q, k), B = product(aux, k + 2);
   const Nat Qm1 = sub_small(Q, 1);
-  const Nat tN = mul(nat(t), nat(N));
+  const Nat tN = mul(mul(nat(t), nat(terms)), nat(N));
   // 2 (t N (Q - 1)^2 / 2 + Q) = t N (Q - 1)^2 + 2 Q   ((Q - 1)^2 is a multiple of 4)
   const Nat need1 = add(mul(tN, mul(Qm1, Qm1)), add(Q, Q));
   const Nat need2 = add(mul(nat(2), mul(tN, Q)), nat(4));
   if (cmp(mul(Q, B), need1) <= 0 || cmp(B, need2) <= 0)
-    return "ciphertext multiplication: the auxiliary base of k + 2 primes does not hold t N Q (plain modulus too large for this chain)";
+    return terms > 1 ? "ciphertext multiplication: the auxiliary base of k + 2 primes does not hold t n N Q for a sum of n "
+                       "products (deferred rounding)"
+                     : "ciphertext multiplication: the auxiliary base of k + 2 primes does not hold t N Q (plain modulus too large for this chain)";
   return nullptr;
 }
 
@@ -216,5 +221,13 @@ hipError_t launch_ctm_scale(hipStream_t st, const CtmParams* P, uint32_t k, uint
 hipError_t launch_ctm_accumulate(hipStream_t st, const DevParams* P, uint32_t k, uint32_t N, const uint64_t* r,
                                  const uint64_t* d, uint64_t* out, uint64_t out_qstride, uint32_t dim, uint32_t nq, uint32_t j0,
                                  uint32_t nj, uint32_t rows);
+// Deferred rounding: the dyadic tensor summed over the children of a row, at the km "data primes" of P.  x [nj * nq][4][km][N]
+// (NTT form, canonical) holds the children [j0, j0 + nj) of every query; acc [(row - j0 / dim) * nq + q][3][km][N] receives,
+// for every row with a child in the block, the sum of (x0, x1, x2) over those children, canonical; a row whose first child
+// lies before j0 adds to what its accumulator holds.  splits > 1 (<= nj): the block's children are shared out over that
+// many workgroups per output word, whose partial sums go to acc + (s + 1) * rows * nq accumulators and are folded by a
+// second launch: acc needs room for (splits + 1) * rows * nq accumulators then.
+hipError_t launch_ctm_tensor_rowsum(hipStream_t st, const DevParams* P, uint32_t km, uint32_t N, const uint64_t* x,
+                                    uint64_t* acc, uint32_t dim, uint32_t nq, uint32_t j0, uint32_t nj, uint32_t splits);
 
 }  // namespace pirgpu

@@ -4,6 +4,7 @@
 //   ctm_tensor_kernel      (x0, x1, x2) = (a0 b0, a0 b1 + a1 b0, a1 b1), dyadic, at one base
 //   ctm_scale_kernel       d = floor((t x + h) / Q): exact, through B and back
 //   ctm_accumulate_kernel  sum of the relinearised products over the children of a row
+// (deferred rounding sums the tensor over the children of a row instead: ctmult_rowsum.hip)
 //
 // All four are elementwise over coefficients, one thread per coefficient, 64-bit integer arithmetic (arith.h).  The
 // per-modulus arrays are indexed by unrolled constants only (the kernels are instantiated per k), so they stay in

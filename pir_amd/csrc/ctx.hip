@@ -265,6 +265,7 @@ struct pirgpu_ctx {
   std::vector<uint8_t> tbl_packed;    // per table: its operand layout is up to date (tables > 1)
   uint64_t scan_launches = 0;         // database-pass launches of the batch pipeline so far (option SCAN_LAUNCHES reads it)
   uint64_t ct_blocks = 0;             // product blocks post_scan_ctm_level queued so far (option CT_BLOCKS reads it)
+  uint64_t ct_relins = 0;             // ciphertexts its levels have key-switched so far (option CT_RELINS)
   uint32_t bits = 0;           // bits per coefficient for item packing
 
   int device = 0;
@@ -370,6 +371,7 @@ struct pirgpu_ctx {
   // ciphertext-multiplication mode (pirgpu_create_ex, PIRGPU_CREATE_CT_MULTIPLY): the upper levels
   // multiply ciphertext by ciphertext (exact BFV product + relinearisation) instead of re-encoding: E = 1 at every level
   bool ctm = false;
+  bool ctm_deferred = false;                // PIRGPU_CREATE_CT_DEFERRED: one rounding and one key switch per row
   uint32_t kb = 0;                          // primes of the auxiliary base (k + 2)
   uint64_t aux_primes[PIRGPU_MAX_PRIMES]{};
   DevParams hp_aux{};                       // the auxiliary base as the "data primes" of a second parameter block:
@@ -1476,6 +1478,51 @@ void ctm_products(pirgpu_ctx* c, hipStream_t st, const CtmRegions& r, const uint
   HIP_TRY(launch_ctm_scale(st, c->d_ctm, k, N, r.yq, r.yb, r.d, n));
 }
 
+// Deferred rounding (PIRGPU_CREATE_CT_DEFERRED), one block: the children [j0, j0 + nj) of every query are lifted and
+// transformed as above; their tensors are summed per row in the NTT domain, at Q into r.yq and at B into r.yb
+// (accumulator (row - j0 / dim) * nq + q; a row begun in an earlier block is accumulator 0 .. nq - 1 and is added to).  The
+// rows whose last child (of nch in all) lies in the block are then transformed back and scaled:
+// r.d [finished * nq][d0, d2, d1][k][N], row-major, query-minor.  Returns the number of finished rows; the first of them
+// is row j0 / dim.  A row cut by the block's end stays behind them: ctm_carry_row moves it to the front for the next
+// block, once the caller is done with r.yq (the key switch writes its output there).
+constexpr uint64_t kCtmRowsumWgs = 512;   // two workgroups per CU
+uint32_t ctm_rowsum_block(pirgpu_ctx* c, hipStream_t st, const CtmRegions& r, uint32_t cap, const uint64_t* a,
+                          uint64_t a_qstride, const uint64_t* b, uint32_t dim, uint32_t nq, uint64_t nch, uint32_t j0, uint32_t nj) {
+  const uint32_t N = c->N, k = c->k, kb = c->kb, n = nj * nq;
+  const uint64_t end = (uint64_t)j0 + nj;
+  const uint32_t row0 = j0 / dim, rows = (uint32_t)((end - 1) / dim) - row0 + 1;
+  const bool cut = end < nch && end % dim != 0;   // the last row goes on in the next block
+  const uint32_t fin = rows - (cut ? 1 : 0);
+  // few rows in flight: below two workgroups per CU a row's children are shared out over several workgroups (partial
+  // accumulators behind the block's own, folded by a second launch; modular sums are exact in any order)
+  const uint64_t wgs = (uint64_t)rows * nq * k * (N / 256);
+  const uint64_t room = (uint64_t)cap / ((uint64_t)rows * nq);   // accumulators per row and query: its own + the partial sums
+  uint32_t splits = (uint32_t)std::min<uint64_t>({ceil_div(kCtmRowsumWgs, wgs), (uint64_t)nj, room ? room - 1 : 0});
+  //   CT_ROWSUM_SPLITS  (A/B, tests) at most this many workgroups share a row's children; 1: never split; 0: as above
+  const int64_t most = option(c, "CT_ROWSUM_SPLITS", 0);
+  if (most > 0) splits = (uint32_t)std::min<int64_t>(splits, most);
+  if (splits < 2) splits = 1;
+  if ((uint64_t)(splits > 1 ? splits + 1 : 1) * rows * nq > cap) throw Fail{PIRGPU_INTERNAL, "row-sum accumulators exceed the product scratch"};
+  HIP_TRY(launch_ctm_lift(st, c->d_ctm, k, N, a, a_qstride, b, dim, nq, j0, n, r.xq, r.xb));
+  HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp, r.xq, (uint64_t)n * 4 * k, k, 0, false));
+  HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp_aux, r.xb, (uint64_t)n * 4 * kb, kb, 0, false));
+  HIP_TRY(launch_ctm_tensor_rowsum(st, c->dp, k, N, r.xq, r.yq, dim, nq, j0, nj, splits));
+  HIP_TRY(launch_ctm_tensor_rowsum(st, c->dp_aux, kb, N, r.xb, r.yb, dim, nq, j0, nj, splits));
+  if (fin) {
+    HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp, r.yq, (uint64_t)fin * nq * 3 * k, k, 0, true));
+    HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp_aux, r.yb, (uint64_t)fin * nq * 3 * kb, kb, 0, true));
+    HIP_TRY(launch_ctm_scale(st, c->d_ctm, k, N, r.yq, r.yb, r.d, fin * nq));
+  }
+  return fin;
+}
+// After a block that finished `fin` rows and ended inside the next one: that row's accumulators to the front.
+void ctm_carry_row(pirgpu_ctx* c, hipStream_t st, const CtmRegions& r, uint32_t nq, uint32_t fin) {
+  const size_t wq = (size_t)nq * 3 * c->k * c->N, wb = (size_t)nq * 3 * c->kb * c->N;
+  if (!fin) return;
+  HIP_TRY(hipMemcpyAsync(r.yq, r.yq + fin * wq, wq * 8, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipMemcpyAsync(r.yb, r.yb + fin * wb, wb * 8, hipMemcpyDeviceToDevice, st));
+}
+
 // The relinearisation key of every query of a group: stored as the key of Galois element 1 of its key set (expansion
 // never uses element 1; the wire codec maps RelinKeys index 0 the same way).
 KeyPtrs relin_keys_for(pirgpu_ctx* c, const uint32_t* ksets, uint32_t nq) {
@@ -1522,6 +1569,19 @@ void post_scan_ctm_level(pirgpu_ctx* c, const Stage& sg, uint32_t l) {
   for (uint64_t j0 = 0; j0 < nch; j0 += bj) {
     const uint32_t nj = (uint32_t)std::min<uint64_t>(bj, nch - j0), n = nj * nq;
     ++c->ct_blocks;
+    if (c->ctm_deferred) {
+      const uint32_t fin = ctm_rowsum_block(c, st, r, cap, sg.lvl[l + 1], c->lvl_cts[l + 1] * ctw, ws.selc, dim, nq, nch,
+                                            (uint32_t)j0, nj);
+      if (!fin) continue;
+      c->ct_relins += (uint64_t)fin * nq;
+      ctm_relinearize(c, st, r, fin * nq, key);
+      // relin + (0, d1) into the finished rows: the accumulation with one child per row (pirgpu_relinearize's form)
+      HIP_TRY(launch_ctm_accumulate(st, c->dp, k, N, r.yq, r.d, sg.lvl[l] + (size_t)(j0 / dim) * ctw, c->lvl_cts[l] * ctw, 1,
+                                    nq, 0, fin, fin));
+      if ((j0 + nj) % dim != 0 && j0 + nj < nch) ctm_carry_row(c, st, r, nq, fin);
+      continue;
+    }
+    c->ct_relins += n;
     ctm_products(c, st, r, sg.lvl[l + 1], c->lvl_cts[l + 1] * ctw, ws.selc, dim, nq, (uint32_t)j0, n);
     ctm_relinearize(c, st, r, n, key);
     HIP_TRY(launch_ctm_accumulate(st, c->dp, k, N, r.yq, r.d, sg.lvl[l], c->lvl_cts[l] * ctw, dim, nq, (uint32_t)j0, nj,
@@ -1704,10 +1764,13 @@ int pirgpu_create_ex(const pirgpu_params* p, uint32_t flags, pirgpu_ctx** out) {
     return code;
   };
   try {
-    if (flags & ~(PIRGPU_CREATE_STREAMED_DB | PIRGPU_CREATE_CT_MULTIPLY))
+    if (flags & ~(PIRGPU_CREATE_STREAMED_DB | PIRGPU_CREATE_CT_MULTIPLY | PIRGPU_CREATE_CT_DEFERRED))
       return bail(PIRGPU_INVALID_ARGUMENT, "unknown pirgpu_create_ex flags " + std::to_string(flags));
     c->streamed = (flags & PIRGPU_CREATE_STREAMED_DB) != 0;
     c->ctm = (flags & PIRGPU_CREATE_CT_MULTIPLY) != 0;
+    c->ctm_deferred = (flags & PIRGPU_CREATE_CT_DEFERRED) != 0;
+    if (c->ctm_deferred && !c->ctm)
+      return bail(PIRGPU_INVALID_ARGUMENT, "PIRGPU_CREATE_CT_DEFERRED needs PIRGPU_CREATE_CT_MULTIPLY (it is a form of that mode)");
     c->prm = *p;
     const uint32_t N = p->poly_modulus_degree, k = p->num_data_primes;
     if (N < 2048 || N > 32768 || (N & (N - 1)))
@@ -1854,6 +1917,12 @@ int pirgpu_create_ex(const pirgpu_params* p, uint32_t flags, pirgpu_ctx** out) {
       // the auxiliary base and its bound, in integers, before anything is allocated for it
       if (const char* why = ctm::plan(N, k, p->coeff_modulus, p->special_prime, p->plain_modulus, c->aux_primes))
         return bail(PIRGPU_INVALID_ARGUMENT, why);
+      if (c->ctm_deferred) {   // a row's sum has up to dims[l] terms
+        uint64_t terms = 1;
+        for (uint32_t l = 0; l + 1 < c->d; ++l) terms = std::max<uint64_t>(terms, c->dims[l]);
+        if (const char* why = ctm::plan(N, k, p->coeff_modulus, p->special_prime, p->plain_modulus, c->aux_primes, terms))
+          return bail(PIRGPU_INVALID_ARGUMENT, std::string("PIRGPU_CREATE_CT_DEFERRED: ") + why);
+      }
       c->kb = k + 2;
     }
     build_tables(c);
@@ -1991,6 +2060,9 @@ static const struct { const char* name; bool early; } kOptions[] = {
     // CT_BLOCKS is a counter of the same kind: the product blocks the upper levels of the ciphertext-multiplication mode
     // queued so far (one per level and query or group when the level's children fit CT_SCRATCH_MB)
     {"CT_BLOCKS", false},
+    // CT_RELINS, likewise: the ciphertexts those levels have key-switched so far -- one per pair, or (deferred rounding)
+    // one per row and query
+    {"CT_RELINS", false}, {"CT_ROWSUM_SPLITS", false},
 };
 
 int pirgpu_set_option(pirgpu_ctx* c, const char* name, int64_t value) {
@@ -2008,6 +2080,10 @@ int pirgpu_set_option(pirgpu_ctx* c, const char* name, int64_t value) {
       }
       if (up == "CT_BLOCKS") {
         c->ct_blocks = (uint64_t)std::max<int64_t>(0, value);
+        return PIRGPU_OK;
+      }
+      if (up == "CT_RELINS") {
+        c->ct_relins = (uint64_t)std::max<int64_t>(0, value);
         return PIRGPU_OK;
       }
       c->opts[up] = value;
@@ -2029,6 +2105,7 @@ int pirgpu_get_option(pirgpu_ctx* c, const char* name, int64_t* value) {
         *value = option(c, o.name, -1, &present);   // -1: not set anywhere, the built-in default applies
         if (up == "SCAN_LAUNCHES") *value = (int64_t)c->scan_launches;
         if (up == "CT_BLOCKS") *value = (int64_t)c->ct_blocks;
+        if (up == "CT_RELINS") *value = (int64_t)c->ct_relins;
         return PIRGPU_OK;
       }
     return fail(c, PIRGPU_INVALID_ARGUMENT, "unknown option " + up);
@@ -2089,10 +2166,15 @@ int pirgpu_mod_switch(pirgpu_ctx* c, const uint64_t* cts, uint64_t n, uint32_t r
 }
 int pirgpu_ctmult_plan(uint32_t N, uint32_t k, const uint64_t* coeff_modulus, uint64_t special_prime, uint64_t plain_modulus,
                        uint64_t* aux_primes, uint32_t* n_aux) {
+  return pirgpu_ctmult_plan_terms(N, k, coeff_modulus, special_prime, plain_modulus, 1, aux_primes, n_aux);
+}
+
+int pirgpu_ctmult_plan_terms(uint32_t N, uint32_t k, const uint64_t* coeff_modulus, uint64_t special_prime,
+                             uint64_t plain_modulus, uint64_t terms, uint64_t* aux_primes, uint32_t* n_aux) {
   if (!coeff_modulus || !aux_primes) return PIRGPU_INVALID_ARGUMENT;
   if (n_aux) *n_aux = 0;
   uint64_t aux[kCtmMaxB] = {};
-  if (const char* why = ctm::plan(N, k, coeff_modulus, special_prime, plain_modulus, aux)) {
+  if (const char* why = ctm::plan(N, k, coeff_modulus, special_prime, plain_modulus, aux, terms)) {
     g_create_error = why;
     return PIRGPU_INVALID_ARGUMENT;
   }
@@ -2130,6 +2212,41 @@ int pirgpu_ct_multiply(pirgpu_ctx* c, const uint64_t* a, const uint64_t* b, uint
         memcpy(dst + 2 * pw, src + pw, pw * 8);
       }
     }
+    return PIRGPU_OK;
+  });
+}
+
+int pirgpu_ct_multiply_sum(pirgpu_ctx* c, const uint64_t* a, const uint64_t* b, uint64_t n, uint64_t* out) {
+  return guarded(c, [&]() -> int {
+    if (!c->ctm) return fail(c, PIRGPU_FAILED_PRECONDITION, "not a ciphertext-multiplication context (PIRGPU_CREATE_CT_MULTIPLY)");
+    if (!a || !b || !out) return fail(c, PIRGPU_INVALID_ARGUMENT, "null buffer");
+    if (n < 1 || n > (1u << 20)) return fail(c, PIRGPU_INVALID_ARGUMENT, "n must be in [1, 2^20]");
+    uint64_t aux[kCtmMaxB] = {};
+    if (const char* why = ctm::plan(c->N, c->k, c->prm.coeff_modulus, c->prm.special_prime, c->prm.plain_modulus, aux, n))
+      return fail(c, PIRGPU_INVALID_ARGUMENT, why);
+    ensure_workspace(c);
+    CtmScratch& ws = ctm_scratch(c, c->stream);
+    const uint32_t cap = ctm_cap_pairs(c);
+    const CtmRegions r = ctm_regions(c, ws.buf, cap);
+    const size_t ctw = c->ctw, pw = (size_t)c->k * c->N;
+    // one row of n children, one query: child j is a[j], its selector b[j % n]
+    DevScratch in;
+    uint64_t* d_a = in.get<uint64_t>((size_t)n * 2 * ctw * 8);
+    uint64_t* d_b = d_a + (size_t)n * ctw;
+    HIP_TRY(hipMemcpyAsync(d_a, a, (size_t)n * ctw * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_b, b, (size_t)n * ctw * 8, hipMemcpyHostToDevice, c->stream));
+    uint32_t fin = 0;
+    for (uint64_t j0 = 0; j0 < n; j0 += cap) {
+      const uint32_t nj = (uint32_t)std::min<uint64_t>(cap, n - j0);
+      fin += ctm_rowsum_block(c, c->stream, r, cap, d_a, 0, d_b, (uint32_t)n, 1, n, (uint32_t)j0, nj);   // (nothing to carry forward)
+    }
+    if (fin != 1) throw Fail{PIRGPU_INTERNAL, "the row did not finish in its last block"};
+    std::vector<uint64_t> host(3 * pw);
+    HIP_TRY(hipMemcpyAsync(host.data(), r.d, host.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    memcpy(out, host.data(), pw * 8);   // the device keeps (d0, d2, d1)
+    memcpy(out + pw, host.data() + 2 * pw, pw * 8);
+    memcpy(out + 2 * pw, host.data() + pw, pw * 8);
     return PIRGPU_OK;
   });
 }

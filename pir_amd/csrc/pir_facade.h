@@ -93,9 +93,11 @@ class PIRDatabase {
   // database.cpp:40-44.  streamed (not in the reference): loads go in row bands straight into the scan's operand layout,
   // the u64 staging copy is never allocated (pirgpu_create_ex, PIRGPU_CREATE_STREAMED_DB).  ct_multiplication: serve
   // params->use_ciphertext_multiplication with this project's exact product (PIRGPU_CREATE_CT_MULTIPLY); without it the
-  // field stays Unimplemented as before
+  // field stays Unimplemented as before.  ct_deferred (with ct_multiplication only): one rounding and one
+  // relinearisation per row of an upper level instead of one per child (PIRGPU_CREATE_CT_DEFERRED)
   static StatusOr<std::shared_ptr<PIRDatabase>> Create(std::shared_ptr<PIRParameters> params, int device = 0,
-                                                       bool streamed = false, bool ct_multiplication = false) {
+                                                       bool streamed = false, bool ct_multiplication = false,
+                                                       bool ct_deferred = false) {
     if (params->coeff_modulus.size() < 2 || params->coeff_modulus.size() > PIRGPU_MAX_PRIMES + 1 ||
         params->dimensions.empty() || params->dimensions.size() > PIRGPU_MAX_DIMS)
       return InvalidArgumentError("invalid parameters");
@@ -118,7 +120,8 @@ class PIRDatabase {
     p.tables = params->tables;
     p.device = device;
     pirgpu_ctx* ctx = nullptr;
-    int rc = pirgpu_create_ex(&p, (streamed ? PIRGPU_CREATE_STREAMED_DB : 0u) | (ct_multiplication ? PIRGPU_CREATE_CT_MULTIPLY : 0u),
+    int rc = pirgpu_create_ex(&p, (streamed ? PIRGPU_CREATE_STREAMED_DB : 0u) | (ct_multiplication ? PIRGPU_CREATE_CT_MULTIPLY : 0u) |
+                                      (ct_deferred ? PIRGPU_CREATE_CT_DEFERRED : 0u),
                               &ctx);
     if (rc) return detail::FromRc(nullptr, rc);
     return std::shared_ptr<PIRDatabase>(new PIRDatabase(ctx, std::move(params)));
@@ -127,8 +130,9 @@ class PIRDatabase {
   // database.cpp:52-58
   static StatusOr<std::shared_ptr<PIRDatabase>> Create(const std::vector<std::string>& rawdb,
                                                        std::shared_ptr<PIRParameters> params, int device = 0,
-                                                       bool streamed = false, bool ct_multiplication = false) {
-    auto db = Create(std::move(params), device, streamed, ct_multiplication);
+                                                       bool streamed = false, bool ct_multiplication = false,
+                                                       bool ct_deferred = false) {
+    auto db = Create(std::move(params), device, streamed, ct_multiplication, ct_deferred);
     if (!db.ok()) return db.status();
     Status s = (*db)->populate(rawdb);
     if (!s.ok()) return s;

@@ -60,12 +60,15 @@ class PIRDatabase:
     """reference database.h:37-133.  Owns the device context and the HBM-resident encoded database."""
 
     def __init__(self, params: PIRParameters, device: int = 0, shard: Optional[Sequence[int]] = None,
-                 slots: Optional[Sequence[int]] = None, streamed: bool = False, ct_multiplication: bool = False):
+                 slots: Optional[Sequence[int]] = None, streamed: bool = False, ct_multiplication: bool = False,
+                 ct_deferred: bool = False):
         """shard: rows [begin, end) of dimension 0 this context holds; slots: NTT slots [begin, end) of every plaintext
         it holds (multi-GPU partitionings; default: the whole database).  streamed: loads go in
         row bands straight into the scan's operand layout, the u64 staging copy is never allocated (pirgpu_create_ex,
         DESIGN.md section 6.3).  ct_multiplication: the reference's ciphertext-multiplication mode with this project's
-        exact product (PIRGPU_CREATE_CT_MULTIPLY; needs params.use_ciphertext_multiplication)."""
+        exact product (PIRGPU_CREATE_CT_MULTIPLY; needs params.use_ciphertext_multiplication).  ct_deferred
+        (with ct_multiplication only): one rounding and one relinearisation per row instead of one per child
+        (PIRGPU_CREATE_CT_DEFERRED)."""
         self.params = params
         enc = params.encryption_parameters
         self.N = enc.poly_modulus_degree
@@ -75,6 +78,7 @@ class PIRDatabase:
         self._cparams = p
         h = C.c_void_p()
         flags = (capi.CREATE_STREAMED_DB if streamed else 0) | (capi.CREATE_CT_MULTIPLY if ct_multiplication else 0)
+        flags |= capi.CREATE_CT_DEFERRED if ct_deferred else 0
         rc = self.lib.pirgpu_create_ex(C.byref(p), flags, C.byref(h))
         if rc != 0:
             raise PirGpuError(rc, self.lib.pirgpu_create_error().decode())
@@ -108,9 +112,10 @@ class PIRDatabase:
     # -- reference interface ------------------------------------------------------
     @classmethod
     def Create(cls, params: PIRParameters, rawdb=None, device: int = 0, shard=None, slots=None,
-               streamed: bool = False, ct_multiplication: bool = False) -> "PIRDatabase":
+               streamed: bool = False, ct_multiplication: bool = False, ct_deferred: bool = False) -> "PIRDatabase":
         """database.cpp:40-58: Create(params) / Create(rawdb, params)."""
-        db = cls(params, device=device, shard=shard, slots=slots, streamed=streamed, ct_multiplication=ct_multiplication)
+        db = cls(params, device=device, shard=shard, slots=slots, streamed=streamed, ct_multiplication=ct_multiplication,
+                 ct_deferred=ct_deferred)
         if rawdb is not None:
             db.populate(rawdb)
         return db
@@ -276,6 +281,17 @@ class PIRDatabase:
                               % (self.k, self.N, list(a.shape), list(b.shape)))
         out = np.empty((a.shape[0], 3, self.k, self.N), dtype=np.uint64)
         self._check(self.lib.pirgpu_ct_multiply(self._h, _ptr(a), _ptr(b), a.shape[0], _ptr(out)))
+        return out
+
+    def ct_multiply_sum(self, a, b) -> np.ndarray:
+        """Test hook (ciphertext-multiplication contexts): n pairs [n, 2, k, N] x [n, 2, k, N] -> [3, k, N] = (D0, D1, D2)
+        of the sum of their tensor products, rounded once (deferred rounding; one row of n children)."""
+        a, b = _u64(a), _u64(b)
+        if a.ndim != 4 or a.shape[1:] != (2, self.k, self.N) or b.shape != a.shape:
+            raise PirGpuError(3, "operands must both have shape [n, 2, %d, %d], got %s and %s"
+                              % (self.k, self.N, list(a.shape), list(b.shape)))
+        out = np.empty((3, self.k, self.N), dtype=np.uint64)
+        self._check(self.lib.pirgpu_ct_multiply_sum(self._h, _ptr(a), _ptr(b), a.shape[0], _ptr(out)))
         return out
 
     def relinearize(self, cts) -> np.ndarray:

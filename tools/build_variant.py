@@ -2,7 +2,7 @@
 """A/B builds of libpirgpu.so: tools/build_variant.py NAME --defs "-DX=1 ..." --tu scan_mfma,ntt12 [--src DIR]
 
 Builds .ab/NAME/libpirgpu.so.  Only the translation units named by --tu are recompiled with the extra definitions
-(kernels, scan_mfma, ctx, wire, wire_codec, ntt_ring32k, ctmult, ntt11..ntt14, or `all`); every other object is taken from the in-tree
+(kernels, scan_mfma, ctx, wire, wire_codec, ntt_ring32k, ctmult, ctmult_rowsum, ntt11..ntt14, or `all`); every other object is taken from the in-tree
 build (pir_amd/csrc/*.o), which must be current.  --src: compile the named units from another source tree (e.g. a
 `git worktree` of an older commit) -- `--tu all --src DIR` gives that commit's library.  The library is selected at run
 time with PIRGPU_LIB=.ab/NAME/libpirgpu.so (pir_amd/capi.py); .ab/ is git-ignored but travels with gpurun.
@@ -19,7 +19,7 @@ from pir_amd import build as B  # noqa: E402
 
 UNITS = {"kernels": ("kernels.hip", None), "scan_mfma": ("scan_mfma.hip", None), "ctx": ("ctx.hip", None),
          "wire": ("wire.cpp", None), "wire_codec": ("wire_codec.cpp", None), "ntt_ring32k": ("ntt_ring32k.hip", None),
-         "ctmult": ("ctmult.hip", None)}
+         "ctmult": ("ctmult.hip", None), "ctmult_rowsum": ("ctmult_rowsum.hip", None)}
 for n in B.NTT_LOGNS:
     for pb in B.NTT_PACK_BYTES:
         UNITS["ntt%d" % n if pb == 5 else "ntt%dp%d" % (n, pb)] = (B.NTT_SOURCE, (n, pb))

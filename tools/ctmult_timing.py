@@ -2,15 +2,17 @@
 
 Shapes: N = 8192 with a 42-bit plain modulus and N = 4096 with a 16-bit one, d = 2, `--items` items of one plaintext each
 (the plain moduli of the reference's own tuples, correctness_test.cpp:99-101: they leave the product a noise budget).
-Variants: a ciphertext-multiplication context and a decomposition-mode context of the same shape; both live in ONE process
-on fresh contexts and alternate, `reps` times after one untimed round; the JSON keeps every sample, the medians and the
+Variants: a ciphertext-multiplication context ("ct": one rounding and one relinearisation per child), one with deferred
+rounding ("ct_deferred", PIRGPU_CREATE_CT_DEFERRED: one per row) and a decomposition-mode context of the same shape; all
+three live in ONE process on fresh contexts and alternate, `reps` times after one untimed round; the JSON keeps every sample, the medians and the
 spread (max - min).
 
   * single query: the phases of pirgpu_last_timings (HIP events: expansion, scan, upper level, final) over 10 runs per
     sample;
   * a batch of 64 queries at the ABI: host clock around pirgpu_batch_stage + _run + pirgpu_sync ("device") and + the
     download of every reply ("total");
-  * reply bytes per query;
+  * reply bytes per query; the counters CT_RELINS and CT_BLOCKS of one single query (ciphertexts key-switched and product
+    blocks queued by the upper level);
   * libpirclient's ProcessResponse on one wire-level response (host clock), and whether it recovered the item.
 
 Nothing here is gated: no ratio is fixed in advance.
@@ -52,10 +54,13 @@ def med(v):
 
 
 class Variant:
-    def __init__(self, enc, items, raw, ct, n_queries, rng):
+    def __init__(self, enc, items, raw, ct, n_queries, rng, deferred=False):
         self.ct = ct
+        self.deferred = deferred
+        self.name = "ct_deferred" if deferred else "ct" if ct else "decomposition"
+        self.counters = None
         self.pp = P.create_pir_parameters(items, 0, 2, enc, ct)
-        self.db = pir_amd.PIRDatabase.Create(self.pp, raw, ct_multiplication=ct)
+        self.db = pir_amd.PIRDatabase.Create(self.pp, raw, ct_multiplication=ct, ct_deferred=deferred)
         self.srv = pir_amd.PIRServer.Create(self.db, self.pp)
         self.client = pir_amd.PIRClient.Create(self.pp, seed=b"ctmult-timing")
         self.srv.set_galois_keys(self.client.galois_keys())
@@ -92,6 +97,17 @@ class Variant:
         t2 = time.perf_counter()
         return (t1 - t0) * 1e3, (t2 - t0) * 1e3
 
+    def count(self):
+        """CT_RELINS and CT_BLOCKS of one single query."""
+        if not self.ct:
+            return
+        for name in ("ct_relins", "ct_blocks"):
+            self.db.set_option(name, 0)
+        self.srv.stage_query(self.queries[0])
+        self.srv.run_staged()
+        self.srv.fetch_reply()
+        self.counters = {name: self.db.get_option(name) for name in ("ct_relins", "ct_blocks")}
+
     def client_pass(self, raw):
         response = self.srv.ProcessRequest(self.request)
         t0 = time.perf_counter()
@@ -113,7 +129,8 @@ class Variant:
 
     def report(self):
         ph = self.samples["phases"]
-        return {"ct_multiplication": self.ct, "reply_cts_per_query": self.db.reply_ct_count(),
+        return {"ct_multiplication": self.ct, "ct_deferred": self.deferred, "single_query_counters": self.counters,
+                "reply_cts_per_query": self.db.reply_ct_count(),
                 "reply_bytes_per_query": self.db.reply_ct_count() * self.db.reply_ct_words() * 8,
                 "response_bytes_one_query": self.response_bytes,
                 "single_query_ms": {p: med([s[p] for s in ph]) for p in ("expand_ms", "scan_ms", "upper_ms", "final_ms",
@@ -128,15 +145,22 @@ def run_shape(name, items, reps, n_queries, res):
     enc = P.generate_encryption_params(N, t_bits)
     width = P.create_pir_parameters(items, 0, 2, enc).bytes_per_item
     raw = np.random.default_rng(2026).integers(0, 256, size=(items, width), dtype=np.uint8)
-    variants = [Variant(enc, items, raw, ct, n_queries, np.random.default_rng(7)) for ct in (True, False)]
+    variants = [Variant(enc, items, raw, ct, n_queries, np.random.default_rng(7), deferred)
+                for ct, deferred in ((True, False), (True, True), (False, False))]
     for v in variants:
         v.round(raw, record=False)
+        v.count()
     for _ in range(reps):
         for v in variants:
             v.round(raw)
     out = {"N": N, "plain_bits": t_bits, "data_prime_bits": [int(q).bit_length() for q in enc.coeff_modulus[:-1]],
            "items": items, "bytes_per_item": width, "dimensions": list(variants[0].pp.dimensions),
-           "variants": {"ct" if v.ct else "decomposition": v.report() for v in variants}}
+           "variants": {v.name: v.report() for v in variants}}
+    ct, de = out["variants"]["ct"]["single_query_ms"], out["variants"]["ct_deferred"]["single_query_ms"]
+    # the one upper level of d = 2 is recorded as the phase `final`
+    out["deferred_over_per_child"] = {p: de[p]["median"] / ct[p]["median"] for p in ("final_ms", "total_ms")}
+    out["deferred_over_per_child"]["batch_device_ms"] = (out["variants"]["ct_deferred"]["batch_device_ms"]["median"] /
+                                                         out["variants"]["ct"]["batch_device_ms"]["median"])
     res["shapes"][name] = out
     for key, o in out["variants"].items():
         s = o["single_query_ms"]
@@ -145,6 +169,9 @@ def run_shape(name, items, reps, n_queries, res):
               (name, key, s["total_ms"]["median"], s["expand_ms"]["median"], s["scan_ms"]["median"], s["upper_ms"]["median"],
                s["final_ms"]["median"], n_queries, o["batch_device_ms"]["median"], o["batch_total_ms"]["median"],
                o["reply_bytes_per_query"], o["client_process_response_ms"]["median"], o["client_recovered_item"]))
+        if o["single_query_counters"]:
+            print("%s %s: %s" % (name, key, o["single_query_counters"]))
+    print("%s deferred / per-child: %s" % (name, out["deferred_over_per_child"]))
     for v in variants:
         v.db.close()
 
@@ -158,8 +185,8 @@ def main() -> int:
     a = ap.parse_args()
     if a.reps < 5:
         ap.error("medians of at least 5 runs")
-    res = {"what": "ciphertext-multiplication mode against decomposition mode on the same shape: the two alternate in one "
-                   "process on fresh contexts; medians of `reps` samples with their spread (max - min)",
+    res = {"what": "ciphertext-multiplication mode, per child and with deferred rounding, against decomposition mode on the "
+                   "same shape: the three alternate in one process on fresh contexts; medians of `reps` samples with their spread (max - min)",
            "commit": os.environ.get("PIRGPU_PROFILED_COMMIT") or head_commit(), "reps": a.reps, "queries": a.queries,
            "shapes": {}}
     for name in SHAPES:
