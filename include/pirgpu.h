@@ -95,7 +95,9 @@ typedef struct pirgpu_params {
    * to the reference's answer on plane j alone.  0 and 1 both mean 1 (the reference's behaviour).  planes > 1 needs
    * items_per_plaintext == 1 and (planes - 1) B < bytes_per_item <= planes B, and serves one GPU only (no row or slot
    * shard).  Plaintext indices at this ABI are plane-major then: plane * num_pt + pt (pirgpu_db_load_coeffs,
-   * pirgpu_db_read_plaintext, pirgpu_db_update_plaintexts; pirgpu_db_size and pirgpu_zero_plaintexts count all planes). */
+   * pirgpu_db_read_plaintext, pirgpu_db_update_plaintexts; pirgpu_db_size and pirgpu_zero_plaintexts count all planes).
+   * With PIRGPU_CREATE_CT_MULTIPLY (below) the usual count is 1: the reply is `planes` ciphertexts, plane j's being
+   * bit-identical to that mode's reply on plane j alone. */
   uint32_t plaintexts_per_item;
   /* Modulus-switched results (not in the reference, which answers at the full data modulus): with 1 <= result_primes =
    * r < k every level result of PIRDatabase::multiply -- the row sums after the scan, every upper level's output, the
@@ -155,12 +157,19 @@ int pirgpu_create(const pirgpu_params* params, pirgpu_ctx** out);
  * Unimplemented.  Row sums (scan + inverse transform) and d = 1 are the existing path, bit for bit.  d >= 2 needs the
  * client's relinearisation key, installed as the key of Galois element 1 of the query's key set (pirgpu_set_galois_key /
  * pirgpu_keyset_set_key with galois_elt = 1; expansion never uses that element): a query without it is InvalidArgument
- * ("RelinKeys missing") -- the reference would go on with size-3 ciphertexts, this server does not.  One GPU: with a row or
- * slot shard, plaintexts_per_item > 1, result_primes, tables > 1, PIRGPU_CREATE_STREAMED_DB, N = 32768, more than 6 data
+ * ("RelinKeys missing") -- the reference would go on with size-3 ciphertexts, this server does not.  Wide items
+ * (plaintexts_per_item > 1) are served, both forms of the mode: one reply ciphertext per plane (pirgpu_reply_ct_count =
+ * planes, plane-major), plane j's bit-identical to the mode's reply on the database made of chunk j of every item.  One
+ * GPU: with a row or slot shard, result_primes, tables > 1, PIRGPU_CREATE_STREAMED_DB, N = 32768, more than 6 data
  * primes or a chain whose auxiliary base does not hold the product (pirgpu_ctmult_plan) the create is InvalidArgument,
  * and the multi-GPU entry points return FailedPrecondition on such a context.  Option "ct_scratch_mb" (default 256, before
  * first use) bounds the scratch the products of one worker / lane run in; "ct_blocks" is a counter: get returns the
- * product blocks the upper levels have queued so far, set overwrites the count (0 to start over). */
+ * product blocks the upper levels have queued so far, set overwrites the count (0 to start over).  Option "ct_shared_sel"
+ * (before first use; default 1 on a context with wide items, 0 on every other): the selector pair of a product, the same
+ * for every row and plane of a level, is lifted to the auxiliary base and transformed once per level and group of queries
+ * instead of once per pair -- exact modular arithmetic either way, the reply bits do not depend on it.  Counter
+ * "ct_lifts" (get / set like "ct_blocks"): the polynomials the upper levels have lifted to the auxiliary base so far --
+ * 4 per pair, or with ct_shared_sel 2 per pair and 2 dimensions[l] per query, level and group. */
 #define PIRGPU_CREATE_CT_MULTIPLY 4u   /* (bit 1 stays unassigned: flags 2 and 3 remain InvalidArgument) */
 /* PIRGPU_CREATE_CT_DEFERRED: deferred rounding ("lazy relinearisation"), a second definition of the
  * upper levels of PIRGPU_CREATE_CT_MULTIPLY and valid only together with it (alone: InvalidArgument).  The tensor

@@ -1,5 +1,5 @@
 // ctmult.h -- ciphertext-multiplication mode: the auxiliary base, the constants of the exact base
-// conversions and the launch wrappers of ctmult.hip and ctmult_rowsum.hip (deferred rounding).
+// conversions and the launch wrappers of ctmult.hip, ctmult_rowsum.hip (deferred rounding) and ctmult_shared.hip (shared selectors).
 //
 // The product of two ciphertexts is the EXACT BFV product: x0 = a0 b0, x1 = a0 b1 + a1 b0, x2 = a1 b1 over Z[x]/(x^N + 1)
 // on the centred lifts, d_i = floor((t x_i + h) / Q), h = (Q - 1) / 2.  The ring products run as dyadic products at the
@@ -229,5 +229,28 @@ hipError_t launch_ctm_accumulate(hipStream_t st, const DevParams* P, uint32_t k,
 // second launch: acc needs room for (splits + 1) * rows * nq accumulators then.
 hipError_t launch_ctm_tensor_rowsum(hipStream_t st, const DevParams* P, uint32_t km, uint32_t N, const uint64_t* x,
                                     uint64_t* acc, uint32_t dim, uint32_t nq, uint32_t j0, uint32_t nj, uint32_t splits);
+// the second launch of the above on its own: acc[slot] = (its own content if `carry` and slot < nq: the carried row is the
+// block's first) + the `splits` partial sums behind the block's rows * nq accumulators
+hipError_t launch_ctm_fold_partials(hipStream_t st, const DevParams* P, uint32_t km, uint32_t N, uint64_t* acc, uint32_t nq,
+                                    uint32_t rows, uint32_t splits, bool carry);
+
+// ---- shared selectors (ctmult_shared.hip, option CT_SHARED_SEL): the selector pair of pair p = jj * nq + q is read from
+// sel.p[q] + ((j0 + jj) % dim) * 2 km N, NTT form at the km moduli of the launch: one array [dim][2][km][N] per query,
+// lifted and transformed once per level. ----
+constexpr int kCtmMaxSel = 8;   // queries of a group (kMaxMfmaQueries)
+struct CtmSelPtrs {             // by-value kernel argument
+  const uint64_t* p[kCtmMaxSel];
+};
+// centred lift of 2 n polynomials: ciphertext c < n is a + (c % nq) * a_qstride + (j0 + c / nq) * 2kN (launch_ctm_lift's
+// ciphertext half; nq = 1, j0 = 0: n ciphertexts back to back) -> xb [n][2][kb][N]; xq [n][2][k][N] receives a copy unless null
+hipError_t launch_ctm_lift_polys(hipStream_t st, const CtmParams* P, uint32_t k, uint32_t N, const uint64_t* a,
+                                 uint64_t a_qstride, uint32_t nq, uint32_t j0, uint32_t n, uint64_t* xq, uint64_t* xb);
+// launch_ctm_tensor with a from x [n][2][km][N]
+hipError_t launch_ctm_tensor_sel(hipStream_t st, const DevParams* P, uint32_t km, uint32_t N, const uint64_t* x,
+                                 const CtmSelPtrs& sel, uint32_t dim, uint32_t nq, uint32_t j0, uint64_t* y, uint32_t n);
+// launch_ctm_tensor_rowsum with a from x [nj * nq][2][km][N]
+hipError_t launch_ctm_tensor_rowsum_sel(hipStream_t st, const DevParams* P, uint32_t km, uint32_t N, const uint64_t* x,
+                                        const CtmSelPtrs& sel, uint64_t* acc, uint32_t dim, uint32_t nq, uint32_t j0,
+                                        uint32_t nj, uint32_t splits);
 
 }  // namespace pirgpu

@@ -94,9 +94,15 @@ hipError_t launch_ctm_tensor_rowsum(hipStream_t st, const DevParams* P, uint32_t
   const uint32_t cj = (nj + splits - 1) / splits;
   hipLaunchKernelGGL(ctm_tensor_rowsum_kernel, dim3(N / kBlock, km, rows * nq * splits), dim3(kBlock), 0, st, P, km, N, x,
                      acc, dim, nq, j0, nj, row0, rows, splits, cj);
-  if (splits > 1)
-    hipLaunchKernelGGL(ctm_fold_partials_kernel, dim3(N / kBlock, 3 * km, rows * nq), dim3(kBlock), 0, st, P, km, N, acc, nq,
-                       splits, (uint32_t)((uint64_t)row0 * dim < j0));
+  if (splits > 1) return launch_ctm_fold_partials(st, P, km, N, acc, nq, rows, splits, (uint64_t)row0 * dim < j0);
+  return hipGetLastError();
+}
+
+hipError_t launch_ctm_fold_partials(hipStream_t st, const DevParams* P, uint32_t km, uint32_t N, uint64_t* acc, uint32_t nq,
+                                    uint32_t rows, uint32_t splits, bool carry) {
+  if (N % kBlock || km < 1 || km > (uint32_t)kMaxPrimes || !nq || !rows || (uint64_t)rows * nq > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ctm_fold_partials_kernel, dim3(N / kBlock, 3 * km, rows * nq), dim3(kBlock), 0, st, P, km, N, acc, nq,
+                     splits, (uint32_t)carry);
   return hipGetLastError();
 }
 

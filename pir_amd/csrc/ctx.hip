@@ -172,6 +172,7 @@ struct CtmScratch {
   size_t words = 0;
   uint64_t* selc = nullptr;   // coefficient-form selectors of the level being served
   size_t selc_words = 0;
+  uint64_t* selb = nullptr;   // CT_SHARED_SEL: their centred lifts at the auxiliary base, NTT form [nq][dim][2][kb][N]
 };
 
 // One client's Galois keys on the device.  The reference deserialises the keys of every request into a local
@@ -266,6 +267,7 @@ struct pirgpu_ctx {
   uint64_t scan_launches = 0;         // database-pass launches of the batch pipeline so far (option SCAN_LAUNCHES reads it)
   uint64_t ct_blocks = 0;             // product blocks post_scan_ctm_level queued so far (option CT_BLOCKS reads it)
   uint64_t ct_relins = 0;             // ciphertexts its levels have key-switched so far (option CT_RELINS)
+  uint64_t ct_lifts = 0;              // polynomials its levels have lifted to the auxiliary base so far (option CT_LIFTS)
   uint32_t bits = 0;           // bits per coefficient for item packing
 
   int device = 0;
@@ -378,6 +380,7 @@ struct pirgpu_ctx {
   DevParams* dp_aux = nullptr;              // ntt_batch transforms at B with the context's own kernels and flavour
   CtmParams* d_ctm = nullptr;               // constants of the exact base conversions (ctmult.h)
   uint64_t ctm_scratch_words = (256ull << 20) / 8;   // product scratch per owner (option CT_SCRATCH_MB)
+  bool ctm_shared_sel = false;              // a level's selectors are lifted and transformed once (option CT_SHARED_SEL)
   std::map<hipStream_t, CtmScratch> ctm_ws; // per owner of a multiply, keyed by its stream
 
   bool prof = false;
@@ -875,6 +878,10 @@ void ensure_workspace(pirgpu_ctx* c) {
     //   CT_SCRATCH_MB  ciphertext-multiplication mode: megabytes of product scratch per worker / lane; the children of a
     //   level are multiplied in blocks that fit it (at least one child of every query of a group)
     if (c->ctm) c->ctm_scratch_words = (uint64_t)std::max<int64_t>(1, option(c, "CT_SCRATCH_MB", 256)) * (1ull << 20) / 8;
+    //   CT_SHARED_SEL  ciphertext-multiplication mode: 1 = the selectors of a level, the same for every row and plane, are
+    //   lifted and transformed once per level and group and only the ciphertext half of a pair per block
+    //   (ctmult_shared.hip); 0 = all four polynomials of every pair.  Default: 1 on a context with wide items, 0 elsewhere
+    c->ctm_shared_sel = c->ctm && option(c, "CT_SHARED_SEL", c->planes > 1) != 0;
     //   DB_STREAM_MB  streamed database: megabytes of encoded plaintexts per load chunk, rounded down to whole row bands
     //   (at least one)
     if (c->streamed && c->mfma_on) {
@@ -1458,6 +1465,7 @@ CtmScratch& ctm_scratch(pirgpu_ctx* c, hipStream_t st) {
     for (uint32_t l = 0; l + 1 < c->d; ++l) dmax = std::max(dmax, c->dims[l]);
     ws.selc_words = (size_t)kMaxMfmaQueries * dmax * c->ctw;
     ws.selc = c->dalloc<uint64_t>(ws.selc_words);
+    if (c->ctm_shared_sel) ws.selb = c->dalloc<uint64_t>((size_t)kMaxMfmaQueries * dmax * 2 * c->kb * c->N);
   }
   return ws;
 }
@@ -1478,6 +1486,28 @@ void ctm_products(pirgpu_ctx* c, hipStream_t st, const CtmRegions& r, const uint
   HIP_TRY(launch_ctm_scale(st, c->d_ctm, k, N, r.yq, r.yb, r.d, n));
 }
 
+// The selectors of one level and group for the shared-selector path (CT_SHARED_SEL): per query, the NTT-form pair array
+// [dim][2][km][N] at Q -- the selection vector as the last expansion level wrote it (canonical residues in the order
+// ntt_batch emits) -- and at B (CtmScratch::selb).
+struct CtmSel {
+  CtmSelPtrs q, b;
+};
+// ctm_products with the selectors given in NTT form at both bases: only the ciphertext half of every pair is lifted and
+// transformed, into the first half of r.xq / r.xb (the regions keep the size of the four-polynomial path, so that blocks
+// are cut at the same children either way).
+void ctm_products_sel(pirgpu_ctx* c, hipStream_t st, const CtmRegions& r, const uint64_t* a, uint64_t a_qstride,
+                      const CtmSel& sel, uint32_t dim, uint32_t nq, uint32_t j0, uint32_t n) {
+  const uint32_t N = c->N, k = c->k, kb = c->kb;
+  HIP_TRY(launch_ctm_lift_polys(st, c->d_ctm, k, N, a, a_qstride, nq, j0, n, r.xq, r.xb));
+  HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp, r.xq, (uint64_t)n * 2 * k, k, 0, false));
+  HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp_aux, r.xb, (uint64_t)n * 2 * kb, kb, 0, false));
+  HIP_TRY(launch_ctm_tensor_sel(st, c->dp, k, N, r.xq, sel.q, dim, nq, j0, r.yq, n));
+  HIP_TRY(launch_ctm_tensor_sel(st, c->dp_aux, kb, N, r.xb, sel.b, dim, nq, j0, r.yb, n));
+  HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp, r.yq, (uint64_t)n * 3 * k, k, 0, true));
+  HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp_aux, r.yb, (uint64_t)n * 3 * kb, kb, 0, true));
+  HIP_TRY(launch_ctm_scale(st, c->d_ctm, k, N, r.yq, r.yb, r.d, n));
+}
+
 // Deferred rounding (PIRGPU_CREATE_CT_DEFERRED), one block: the children [j0, j0 + nj) of every query are lifted and
 // transformed as above; their tensors are summed per row in the NTT domain, at Q into r.yq and at B into r.yb
 // (accumulator (row - j0 / dim) * nq + q; a row begun in an earlier block is accumulator 0 .. nq - 1 and is added to).  The
@@ -1487,7 +1517,8 @@ void ctm_products(pirgpu_ctx* c, hipStream_t st, const CtmRegions& r, const uint
 // block, once the caller is done with r.yq (the key switch writes its output there).
 constexpr uint64_t kCtmRowsumWgs = 512;   // two workgroups per CU
 uint32_t ctm_rowsum_block(pirgpu_ctx* c, hipStream_t st, const CtmRegions& r, uint32_t cap, const uint64_t* a,
-                          uint64_t a_qstride, const uint64_t* b, uint32_t dim, uint32_t nq, uint64_t nch, uint32_t j0, uint32_t nj) {
+                          uint64_t a_qstride, const uint64_t* b, uint32_t dim, uint32_t nq, uint64_t nch, uint32_t j0, uint32_t nj,
+                          const CtmSel* sel = nullptr) {   // sel: the shared-selector path (b is not read)
   const uint32_t N = c->N, k = c->k, kb = c->kb, n = nj * nq;
   const uint64_t end = (uint64_t)j0 + nj;
   const uint32_t row0 = j0 / dim, rows = (uint32_t)((end - 1) / dim) - row0 + 1;
@@ -1503,11 +1534,19 @@ uint32_t ctm_rowsum_block(pirgpu_ctx* c, hipStream_t st, const CtmRegions& r, ui
   if (most > 0) splits = (uint32_t)std::min<int64_t>(splits, most);
   if (splits < 2) splits = 1;
   if ((uint64_t)(splits > 1 ? splits + 1 : 1) * rows * nq > cap) throw Fail{PIRGPU_INTERNAL, "row-sum accumulators exceed the product scratch"};
-  HIP_TRY(launch_ctm_lift(st, c->d_ctm, k, N, a, a_qstride, b, dim, nq, j0, n, r.xq, r.xb));
-  HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp, r.xq, (uint64_t)n * 4 * k, k, 0, false));
-  HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp_aux, r.xb, (uint64_t)n * 4 * kb, kb, 0, false));
-  HIP_TRY(launch_ctm_tensor_rowsum(st, c->dp, k, N, r.xq, r.yq, dim, nq, j0, nj, splits));
-  HIP_TRY(launch_ctm_tensor_rowsum(st, c->dp_aux, kb, N, r.xb, r.yb, dim, nq, j0, nj, splits));
+  if (sel) {
+    HIP_TRY(launch_ctm_lift_polys(st, c->d_ctm, k, N, a, a_qstride, nq, j0, n, r.xq, r.xb));
+    HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp, r.xq, (uint64_t)n * 2 * k, k, 0, false));
+    HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp_aux, r.xb, (uint64_t)n * 2 * kb, kb, 0, false));
+    HIP_TRY(launch_ctm_tensor_rowsum_sel(st, c->dp, k, N, r.xq, sel->q, r.yq, dim, nq, j0, nj, splits));
+    HIP_TRY(launch_ctm_tensor_rowsum_sel(st, c->dp_aux, kb, N, r.xb, sel->b, r.yb, dim, nq, j0, nj, splits));
+  } else {
+    HIP_TRY(launch_ctm_lift(st, c->d_ctm, k, N, a, a_qstride, b, dim, nq, j0, n, r.xq, r.xb));
+    HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp, r.xq, (uint64_t)n * 4 * k, k, 0, false));
+    HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp_aux, r.xb, (uint64_t)n * 4 * kb, kb, 0, false));
+    HIP_TRY(launch_ctm_tensor_rowsum(st, c->dp, k, N, r.xq, r.yq, dim, nq, j0, nj, splits));
+    HIP_TRY(launch_ctm_tensor_rowsum(st, c->dp_aux, kb, N, r.xb, r.yb, dim, nq, j0, nj, splits));
+  }
   if (fin) {
     HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp, r.yq, (uint64_t)fin * nq * 3 * k, k, 0, true));
     HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp_aux, r.yb, (uint64_t)fin * nq * 3 * kb, kb, 0, true));
@@ -1565,13 +1604,30 @@ void post_scan_ctm_level(pirgpu_ctx* c, const Stage& sg, uint32_t l) {
     HIP_TRY(hipMemcpyAsync(ws.selc + (size_t)q * dim * ctw, static_cast<const uint64_t*>(sg.sel.p[q]) + (size_t)c->sv_off[l] * ctw,
                            (size_t)dim * ctw * 8, hipMemcpyDeviceToDevice, st));
   HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp, ws.selc, (uint64_t)nq * dim * 2 * k, k, 0, true));
+  // shared selectors: their lifts to B, transformed, once for all rows (and planes) of the level; at Q the selection
+  // vector itself is read
+  const bool shared = c->ctm_shared_sel;
+  CtmSel sel{};
+  if (shared) {
+    if (!ws.selb) throw Fail{PIRGPU_INTERNAL, "shared-selector scratch missing"};
+    for (uint32_t s0 = 0; s0 < nq * dim; s0 += 32767)   // (the launch takes 32 767 ciphertexts)
+      HIP_TRY(launch_ctm_lift_polys(st, c->d_ctm, k, N, ws.selc + (size_t)s0 * ctw, 0, 1, 0, std::min<uint32_t>(32767, nq * dim - s0),
+                                    nullptr, ws.selb + (size_t)s0 * 2 * c->kb * N));
+    HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp_aux, ws.selb, (uint64_t)nq * dim * 2 * c->kb, c->kb, 0, false));
+    c->ct_lifts += (uint64_t)2 * dim * nq;
+    for (uint32_t q = 0; q < nq; ++q) {
+      sel.q.p[q] = static_cast<const uint64_t*>(sg.sel.p[q]) + (size_t)c->sv_off[l] * ctw;
+      sel.b.p[q] = ws.selb + (size_t)q * dim * 2 * c->kb * N;
+    }
+  }
   const uint32_t bj = std::max<uint32_t>(1, cap / nq);   // children per block (of every query of the group)
   for (uint64_t j0 = 0; j0 < nch; j0 += bj) {
     const uint32_t nj = (uint32_t)std::min<uint64_t>(bj, nch - j0), n = nj * nq;
     ++c->ct_blocks;
+    c->ct_lifts += (uint64_t)(shared ? 2 : 4) * n;
     if (c->ctm_deferred) {
       const uint32_t fin = ctm_rowsum_block(c, st, r, cap, sg.lvl[l + 1], c->lvl_cts[l + 1] * ctw, ws.selc, dim, nq, nch,
-                                            (uint32_t)j0, nj);
+                                            (uint32_t)j0, nj, shared ? &sel : nullptr);
       if (!fin) continue;
       c->ct_relins += (uint64_t)fin * nq;
       ctm_relinearize(c, st, r, fin * nq, key);
@@ -1582,7 +1638,10 @@ void post_scan_ctm_level(pirgpu_ctx* c, const Stage& sg, uint32_t l) {
       continue;
     }
     c->ct_relins += n;
-    ctm_products(c, st, r, sg.lvl[l + 1], c->lvl_cts[l + 1] * ctw, ws.selc, dim, nq, (uint32_t)j0, n);
+    if (shared)
+      ctm_products_sel(c, st, r, sg.lvl[l + 1], c->lvl_cts[l + 1] * ctw, sel, dim, nq, (uint32_t)j0, n);
+    else
+      ctm_products(c, st, r, sg.lvl[l + 1], c->lvl_cts[l + 1] * ctw, ws.selc, dim, nq, (uint32_t)j0, n);
     ctm_relinearize(c, st, r, n, key);
     HIP_TRY(launch_ctm_accumulate(st, c->dp, k, N, r.yq, r.d, sg.lvl[l], c->lvl_cts[l] * ctw, dim, nq, (uint32_t)j0, nj,
                                   (uint32_t)rows));
@@ -1798,8 +1857,6 @@ int pirgpu_create_ex(const pirgpu_params* p, uint32_t flags, pirgpu_ctx** out) {
       if (p->slot_begin || p->slot_end)
         return bail(PIRGPU_INVALID_ARGUMENT, "PIRGPU_CREATE_CT_MULTIPLY is served by one GPU: a slot shard (slot_begin / "
                                              "slot_end) is not supported");
-      if (p->plaintexts_per_item > 1)
-        return bail(PIRGPU_INVALID_ARGUMENT, "PIRGPU_CREATE_CT_MULTIPLY with plaintexts_per_item > 1 is not supported");
       if (p->result_primes)
         return bail(PIRGPU_INVALID_ARGUMENT, "PIRGPU_CREATE_CT_MULTIPLY with result_primes > 0 is not supported");
       if (p->tables > 1) return bail(PIRGPU_INVALID_ARGUMENT, "PIRGPU_CREATE_CT_MULTIPLY with tables > 1 is not supported");
@@ -1863,7 +1920,8 @@ int pirgpu_create_ex(const pirgpu_params* p, uint32_t flags, pirgpu_ctx** out) {
         return bail(PIRGPU_INVALID_ARGUMENT, "plaintexts_per_item > 1 needs items_per_plaintext == 1");
       if (p->bytes_per_item <= (c->planes - 1) * B || p->bytes_per_item > c->planes * B)
         return bail(PIRGPU_INVALID_ARGUMENT, "bytes_per_item " + std::to_string(p->bytes_per_item) + " does not need exactly " +
-                                                 std::to_string(c->planes) + " plaintexts of " + std::to_string(B) + " bytes");
+                                                 "plaintexts_per_item = " + std::to_string(c->planes) + " plaintexts of " +
+                                                 std::to_string(B) + " bytes");
       if (c->sb != 0 || c->se != c->dims[0] || c->slot_sharded)
         return bail(PIRGPU_INVALID_ARGUMENT, "wide items (plaintexts_per_item > 1) are served by one GPU: row and slot "
                                              "shards of them are not supported");
@@ -2052,7 +2110,7 @@ static const struct { const char* name; bool early; } kOptions[] = {
     {"SCAN_MFMA", true}, {"SCAN_MFMA_WIDE", true}, {"SCAN_MFMA_TOP4", true}, {"SCAN_MFMA_NQ", true}, {"SCAN_MFMA_SINGLE", true},
     {"HEAD_LEVELS", true}, {"HEAD_MODE", true}, {"SCAN_F64_FOLD", true}, {"SCAN_F64_FOLD_BATCH", true}, {"LOOP_TRANSFORMS", true},
     {"SLOTS_SCAN_WGS", false}, {"SLOTS_GATHER_NTT", false}, {"SLOTS_SCAN_BLK_MAJOR", false}, {"DB_STREAM_MB", true},
-    {"CT_SCRATCH_MB", true},
+    {"CT_SCRATCH_MB", true}, {"CT_SHARED_SEL", true},
     // contexts with tables: 0 = one database-pass launch per run of equal tables instead of one per group (A/B);
     // SCAN_LAUNCHES is a COUNTER, not a choice: get returns the database-pass launches the batch pipeline queued so far,
     // set overwrites the count (0 to start over)
@@ -2063,6 +2121,9 @@ static const struct { const char* name; bool early; } kOptions[] = {
     // CT_RELINS, likewise: the ciphertexts those levels have key-switched so far -- one per pair, or (deferred rounding)
     // one per row and query
     {"CT_RELINS", false}, {"CT_ROWSUM_SPLITS", false},
+    // CT_LIFTS, likewise: the polynomials those levels have lifted to the auxiliary base so far -- 4 per pair, or
+    // (CT_SHARED_SEL) 2 per pair and 2 dims[l] per query, level and group
+    {"CT_LIFTS", false},
 };
 
 int pirgpu_set_option(pirgpu_ctx* c, const char* name, int64_t value) {
@@ -2086,6 +2147,10 @@ int pirgpu_set_option(pirgpu_ctx* c, const char* name, int64_t value) {
         c->ct_relins = (uint64_t)std::max<int64_t>(0, value);
         return PIRGPU_OK;
       }
+      if (up == "CT_LIFTS") {
+        c->ct_lifts = (uint64_t)std::max<int64_t>(0, value);
+        return PIRGPU_OK;
+      }
       c->opts[up] = value;
       if (up == "SCAN_MFMA_WGS_BATCH") c->scan_wgs_batch = (uint32_t)std::max<int64_t>(0, value);
       return PIRGPU_OK;
@@ -2106,6 +2171,9 @@ int pirgpu_get_option(pirgpu_ctx* c, const char* name, int64_t* value) {
         if (up == "SCAN_LAUNCHES") *value = (int64_t)c->scan_launches;
         if (up == "CT_BLOCKS") *value = (int64_t)c->ct_blocks;
         if (up == "CT_RELINS") *value = (int64_t)c->ct_relins;
+        if (up == "CT_LIFTS") *value = (int64_t)c->ct_lifts;
+        // (the default depends on the context: report what applies, not -1)
+        if (up == "CT_SHARED_SEL" && !present) *value = c->ctm && c->planes > 1;
         return PIRGPU_OK;
       }
     return fail(c, PIRGPU_INVALID_ARGUMENT, "unknown option " + up);
