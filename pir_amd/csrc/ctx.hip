@@ -266,6 +266,8 @@ struct pirgpu_ctx {
   std::vector<uint8_t> tbl_packed;    // per table: its operand layout is up to date (tables > 1)
   uint64_t scan_launches = 0;         // database-pass launches of the batch pipeline so far (option SCAN_LAUNCHES reads it)
   uint64_t ct_blocks = 0;             // product blocks post_scan_ctm_level queued so far (option CT_BLOCKS reads it)
+  uint64_t upper_parts = 0;           // chunks (fused) or blocks (split) of children the upper levels queued so far, per
+                                      // level and query or group (option UPPER_PARTS reads it)
   uint64_t ct_relins = 0;             // ciphertexts its levels have key-switched so far (option CT_RELINS)
   uint64_t ct_lifts = 0;              // polynomials its levels have lifted to the auxiliary base so far (option CT_LIFTS)
   uint32_t bits = 0;           // bits per coefficient for item packing
@@ -1727,6 +1729,7 @@ void post_scan_stage(pirgpu_ctx* c, const Stage& sg, Worker* profiled) {
         *sg.up_scratch_words = unit * blk;
       }
       for (uint32_t b0 = 0; b0 < nd; b0 += blk) {
+        ++c->upper_parts;
         HIP_TRY(c->ops->upper_ntt(st, c->mode, c->dp, k, c->E, sg.lvl[l + 1], *sg.up_scratch, (uint32_t)rows, c->dims[l],
                                   (uint32_t)nch, (uint32_t)C, b0, blk, sg.n, c->lvl_cts[l + 1] * ctw, c->loop_transforms));
         if (c->mode == kNttInt)   // N = 32768
@@ -1740,6 +1743,7 @@ void post_scan_stage(pirgpu_ctx* c, const Stage& sg, Worker* profiled) {
       }
       if (l == 0 && profiled) record(c, *profiled, PH_FINAL);
     } else {
+      c->upper_parts += n_chunks;
       HIP_TRY(c->ops->upper_fused(st, c->mode, c->dp, k, c->E, sg.lvl[l + 1], sg.sel, sg.pt_buf, (uint32_t)rows,
                                   c->dims[l], (uint32_t)nch, sv_first, (uint32_t)C, chunk_len, n_chunks, sg.n,
                                   c->lvl_cts[l + 1] * ctw, c->pt_words, sg.sel_f64));
@@ -2118,6 +2122,10 @@ static const struct { const char* name; bool early; } kOptions[] = {
     // CT_BLOCKS is a counter of the same kind: the product blocks the upper levels of the ciphertext-multiplication mode
     // queued so far (one per level and query or group when the level's children fit CT_SCRATCH_MB)
     {"CT_BLOCKS", false},
+    // UPPER_PARTS, likewise: the parts the upper recursion levels cut a row's children into so far -- chunks of the fused
+    // kernel (their sums meet in reduce_splits_kernel) or blocks of the split form (carried in `acc`), counted once per
+    // level and query or group
+    {"UPPER_PARTS", false},
     // CT_RELINS, likewise: the ciphertexts those levels have key-switched so far -- one per pair, or (deferred rounding)
     // one per row and query
     {"CT_RELINS", false}, {"CT_ROWSUM_SPLITS", false},
@@ -2141,6 +2149,10 @@ int pirgpu_set_option(pirgpu_ctx* c, const char* name, int64_t value) {
       }
       if (up == "CT_BLOCKS") {
         c->ct_blocks = (uint64_t)std::max<int64_t>(0, value);
+        return PIRGPU_OK;
+      }
+      if (up == "UPPER_PARTS") {
+        c->upper_parts = (uint64_t)std::max<int64_t>(0, value);
         return PIRGPU_OK;
       }
       if (up == "CT_RELINS") {
@@ -2170,6 +2182,7 @@ int pirgpu_get_option(pirgpu_ctx* c, const char* name, int64_t* value) {
         *value = option(c, o.name, -1, &present);   // -1: not set anywhere, the built-in default applies
         if (up == "SCAN_LAUNCHES") *value = (int64_t)c->scan_launches;
         if (up == "CT_BLOCKS") *value = (int64_t)c->ct_blocks;
+        if (up == "UPPER_PARTS") *value = (int64_t)c->upper_parts;
         if (up == "CT_RELINS") *value = (int64_t)c->ct_relins;
         if (up == "CT_LIFTS") *value = (int64_t)c->ct_lifts;
         // (the default depends on the context: report what applies, not -1)

@@ -121,8 +121,11 @@ class Field:
         st.max_value = max(st.max_value, m)
 
     # ---- ntt_core.h
-    def forward(self, residues, mode):
-        """Canonical residues (coefficients) -> canonical residues in SEAL's NTT order, and the statistics."""
+    def forward(self, residues, mode, canonical=True):
+        """Canonical residues (coefficients) -> canonical residues in SEAL's NTT order, and the statistics.  With
+        `canonical` off the inputs may be signed representatives (the upper level's plain lift) and the signed
+        representatives of the outputs are returned as doubles (ntt_forward<..., CANON = false>, A::signed_fwd: what
+        upper_fused_kernel multiplies and upper_ntt_kernel stores)."""
         assert mode in (1, 2)
         st = Stats()
         N = self.N
@@ -139,7 +142,9 @@ class Field:
             self._seen(a, st)
             st.stage_max.append(float(np.abs(a).max() / self.qd))
             m <<= 1
-        r = self.norm(a, st)                                 # canon_fwd
+        r = self.norm(a, st)                                 # canon_fwd / signed_fwd
+        if not canonical:
+            return r, st
         r = np.where(r < 0, r + self.qd, r)
         return self._canonical(r), st
 

@@ -89,6 +89,15 @@ def device_to_seal_order(a):
     return np.ascontiguousarray(a.reshape(a.shape[:-1] + (16, N // 16)).swapaxes(-1, -2).reshape(a.shape))
 
 
+def seal_to_device_order(a):
+    """The inverse of device_to_seal_order.  N = 32768 keeps SEAL's order on the device (ntt_ring32k.hip)."""
+    a = np.asarray(a)
+    N = a.shape[-1]
+    if N >= 32768:
+        return np.ascontiguousarray(a)
+    return np.ascontiguousarray(a.reshape(a.shape[:-1] + (N // 16, 16)).swapaxes(-1, -2).reshape(a.shape))
+
+
 def all_to_all_in_process(recvs, sends, recv_splits, send_splits):
     """What torch.distributed.all_to_all_single does, between in-process 'ranks' (1-D tensors, element splits)."""
     G = len(sends)
