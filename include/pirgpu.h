@@ -169,7 +169,8 @@ int pirgpu_create(const pirgpu_params* params, pirgpu_ctx** out);
  * for every row and plane of a level, is lifted to the auxiliary base and transformed once per level and group of queries
  * instead of once per pair -- exact modular arithmetic either way, the reply bits do not depend on it.  Counter
  * "ct_lifts" (get / set like "ct_blocks"): the polynomials the upper levels have lifted to the auxiliary base so far --
- * 4 per pair, or with ct_shared_sel 2 per pair and 2 dimensions[l] per query, level and group. */
+ * 4 per pair, or with ct_shared_sel 2 per pair and 2 dimensions[l] per query, level and group.  The test hooks
+ * pirgpu_ct_multiply and pirgpu_ct_multiply_sum count into it as well (see there). */
 #define PIRGPU_CREATE_CT_MULTIPLY 4u   /* (bit 1 stays unassigned: flags 2 and 3 remain InvalidArgument) */
 /* PIRGPU_CREATE_CT_DEFERRED: deferred rounding ("lazy relinearisation"), a second definition of the
  * upper levels of PIRGPU_CREATE_CT_MULTIPLY and valid only together with it (alone: InvalidArgument).  The tensor
@@ -353,7 +354,13 @@ int pirgpu_ctmult_plan(uint32_t poly_modulus_degree, uint32_t num_data_primes, c
 /* Test hooks of the mode (FailedPrecondition on a context without PIRGPU_CREATE_CT_MULTIPLY).  ct_multiply: n pairs of
  * coefficient-form ciphertexts a, b [n][2][k][N] -> out [n][3][k][N] = (d0, d1, d2), the exact product.  relinearize:
  * in [n][3][k][N] -> out [n][2][k][N] = (d0 + KS0(d2), d1 + KS1(d2)) with the relinearisation key of the selected key set
- * (pirgpu_query_use_keyset; the key of Galois element 1). */
+ * (pirgpu_query_use_keyset; the key of Galois element 1).
+ * ct_multiply and ct_multiply_sum honour the option "ct_shared_sel": with 0 (the default of a context without wide
+ * items) every pair lifts and transforms its four polynomials; with 1 the selectors b of the call (of each block of
+ * pairs; of the whole row) are lifted to the auxiliary base and transformed once, in buffers of the call's own, read at
+ * Q from the forward transform of a copy, and the products run in the shared-selector kernels of the query path -- the
+ * same blocks, the same bits.  Both count into "ct_lifts": 4 per pair, or with ct_shared_sel 2 per pair and 2 per
+ * selector lifted (a hook call has one selector per pair: 4 n on n pairs either way). */
 /* pirgpu_ctmult_plan with the bound of a sum of up to `terms` products (deferred rounding): Q B > t terms N (Q - 1)^2 + 2 Q
  * and B > 2 (t terms N Q + 2).  terms = 1 is pirgpu_ctmult_plan. */
 int pirgpu_ctmult_plan_terms(uint32_t poly_modulus_degree, uint32_t num_data_primes, const uint64_t* coeff_modulus,

@@ -1564,6 +1564,25 @@ void ctm_carry_row(pirgpu_ctx* c, hipStream_t st, const CtmRegions& r, uint32_t 
   HIP_TRY(hipMemcpyAsync(r.yb, r.yb + fin * wb, wb * 8, hipMemcpyDeviceToDevice, st));
 }
 
+// The CtmSel of a hook call (pirgpu_ct_multiply, pirgpu_ct_multiply_sum on a CT_SHARED_SEL context): the n selectors b
+// [n][2][k][N], coefficient form, as one query's array of dim = n.  At B their centred lifts, transformed, into selb
+// [n][2][kb][N]; at Q the forward transform of a copy in selq [n][2][k][N] -- canonical residues in the order ntt_batch
+// emits, which is what the query path reads from the selection vector.  Both buffers are the call's own.
+CtmSel ctm_hook_selectors(pirgpu_ctx* c, hipStream_t st, const uint64_t* b, uint64_t n, uint64_t* selq, uint64_t* selb) {
+  const uint32_t N = c->N, k = c->k, kb = c->kb;
+  for (uint64_t s0 = 0; s0 < n; s0 += 32767)   // (the launch takes 32 767 ciphertexts)
+    HIP_TRY(launch_ctm_lift_polys(st, c->d_ctm, k, N, b + (size_t)s0 * c->ctw, 0, 1, 0, (uint32_t)std::min<uint64_t>(32767, n - s0),
+                                  nullptr, selb + (size_t)s0 * 2 * kb * N));
+  HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp_aux, selb, n * 2 * kb, kb, 0, false));
+  HIP_TRY(hipMemcpyAsync(selq, b, (size_t)n * c->ctw * 8, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp, selq, n * 2 * k, k, 0, false));
+  c->ct_lifts += 2 * n;
+  CtmSel sel{};
+  sel.q.p[0] = selq;
+  sel.b.p[0] = selb;
+  return sel;
+}
+
 // The relinearisation key of every query of a group: stored as the key of Galois element 1 of its key set (expansion
 // never uses element 1; the wire codec maps RelinKeys index 0 the same way).
 KeyPtrs relin_keys_for(pirgpu_ctx* c, const uint32_t* ksets, uint32_t nq) {
@@ -2130,7 +2149,8 @@ static const struct { const char* name; bool early; } kOptions[] = {
     // one per row and query
     {"CT_RELINS", false}, {"CT_ROWSUM_SPLITS", false},
     // CT_LIFTS, likewise: the polynomials those levels have lifted to the auxiliary base so far -- 4 per pair, or
-    // (CT_SHARED_SEL) 2 per pair and 2 dims[l] per query, level and group
+    // (CT_SHARED_SEL) 2 per pair and 2 dims[l] per query, level and group; the hooks pirgpu_ct_multiply and
+    // pirgpu_ct_multiply_sum count the same way, 2 per selector of the call
     {"CT_LIFTS", false},
 };
 
@@ -2273,15 +2293,25 @@ int pirgpu_ct_multiply(pirgpu_ctx* c, const uint64_t* a, const uint64_t* b, uint
     const uint32_t cap = ctm_cap_pairs(c);
     const CtmRegions r = ctm_regions(c, ws.buf, cap);
     const size_t ctw = c->ctw, pw = (size_t)c->k * c->N;
+    // CT_SHARED_SEL: behind a and b the block's selectors in NTT form, at Q and at B (pair p reads selector p: dim = m)
+    const bool shared = c->ctm_shared_sel;
+    const size_t selw = shared ? ctw + (size_t)2 * c->kb * c->N : 0;
     DevScratch in;
-    uint64_t* d_in = in.get<uint64_t>((size_t)std::min<uint64_t>(cap, std::max<uint64_t>(n, 1)) * 2 * ctw * 8);
+    uint64_t* d_in = in.get<uint64_t>((size_t)std::min<uint64_t>(cap, std::max<uint64_t>(n, 1)) * (2 * ctw + selw) * 8);
     std::vector<uint64_t> host;
     for (uint64_t p0 = 0; p0 < n; p0 += cap) {
       const uint32_t m = (uint32_t)std::min<uint64_t>(cap, n - p0);
       uint64_t* d_b = d_in + (size_t)m * ctw;
       HIP_TRY(hipMemcpyAsync(d_in, a + p0 * ctw, (size_t)m * ctw * 8, hipMemcpyHostToDevice, c->stream));
       HIP_TRY(hipMemcpyAsync(d_b, b + p0 * ctw, (size_t)m * ctw * 8, hipMemcpyHostToDevice, c->stream));
-      ctm_products(c, c->stream, r, d_in, 0, d_b, m, 1, 0, m);
+      c->ct_lifts += (uint64_t)(shared ? 2 : 4) * m;
+      if (shared) {
+        uint64_t* d_selq = d_b + (size_t)m * ctw;
+        const CtmSel sel = ctm_hook_selectors(c, c->stream, d_b, m, d_selq, d_selq + (size_t)m * ctw);
+        ctm_products_sel(c, c->stream, r, d_in, 0, sel, m, 1, 0, m);
+      } else {
+        ctm_products(c, c->stream, r, d_in, 0, d_b, m, 1, 0, m);
+      }
       host.resize((size_t)m * 3 * pw);
       HIP_TRY(hipMemcpyAsync(host.data(), r.d, host.size() * 8, hipMemcpyDeviceToHost, c->stream));
       HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2311,15 +2341,25 @@ int pirgpu_ct_multiply_sum(pirgpu_ctx* c, const uint64_t* a, const uint64_t* b, 
     const CtmRegions r = ctm_regions(c, ws.buf, cap);
     const size_t ctw = c->ctw, pw = (size_t)c->k * c->N;
     // one row of n children, one query: child j is a[j], its selector b[j % n]
+    // CT_SHARED_SEL: behind a and b the row's n selectors in NTT form, at Q and at B, made once for all blocks
+    const bool shared = c->ctm_shared_sel;
+    const size_t selw = shared ? ctw + (size_t)2 * c->kb * c->N : 0;
     DevScratch in;
-    uint64_t* d_a = in.get<uint64_t>((size_t)n * 2 * ctw * 8);
+    uint64_t* d_a = in.get<uint64_t>((size_t)n * (2 * ctw + selw) * 8);
     uint64_t* d_b = d_a + (size_t)n * ctw;
     HIP_TRY(hipMemcpyAsync(d_a, a, (size_t)n * ctw * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_b, b, (size_t)n * ctw * 8, hipMemcpyHostToDevice, c->stream));
+    CtmSel sel{};
+    if (shared) {
+      uint64_t* d_selq = d_b + (size_t)n * ctw;
+      sel = ctm_hook_selectors(c, c->stream, d_b, n, d_selq, d_selq + (size_t)n * ctw);
+    }
     uint32_t fin = 0;
     for (uint64_t j0 = 0; j0 < n; j0 += cap) {
       const uint32_t nj = (uint32_t)std::min<uint64_t>(cap, n - j0);
-      fin += ctm_rowsum_block(c, c->stream, r, cap, d_a, 0, d_b, (uint32_t)n, 1, n, (uint32_t)j0, nj);   // (nothing to carry forward)
+      c->ct_lifts += (uint64_t)(shared ? 2 : 4) * nj;
+      fin += ctm_rowsum_block(c, c->stream, r, cap, d_a, 0, d_b, (uint32_t)n, 1, n, (uint32_t)j0, nj,
+                              shared ? &sel : nullptr);   // (nothing to carry forward)
     }
     if (fin != 1) throw Fail{PIRGPU_INTERNAL, "the row did not finish in its last block"};
     std::vector<uint64_t> host(3 * pw);

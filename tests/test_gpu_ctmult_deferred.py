@@ -81,18 +81,34 @@ def random_pair(q, N, rng):
 
 # ------------------------------------------------------------------------------------------------ 1. the hook
 
-@pytest.mark.parametrize("rung", ["k1", "k3-mixed", "k3-wide", "k6-f64", "k6-int"])
+SUM_RUNGS = ["k1", "k3-mixed", "k3-wide", "k6-f64", "k6-int"]
+_SUM_CASE = {}
+
+
+def sum_case(rung):
+    """chain, inputs and the model's (D0, D1, D2) of one rung's row, computed once (tests/test_gpu_ctmult_shared.py runs
+    the same row on the shared-selector path)."""
+    if rung not in _SUM_CASE:
+        N, moduli, t = rung_chain(rung)
+        q = moduli[:-1]
+        rng = np.random.default_rng(N + 31 * len(q))
+        names, A, B = M.hook_inputs(q, t, N, rng, names=M.SUB_FAMILY)       # one random pair and the extremes
+        extra = [random_pair(q, N, rng) for _ in range(2)]
+        A = np.concatenate([A, np.stack([e[0] for e in extra])])
+        B = np.concatenate([B, np.stack([e[1] for e in extra])])
+        n = A.shape[0]
+        assert n == len(M.SUB_FAMILY) + 2 and D.plan_terms(N, q, moduli[-1], t, n)[1]
+        want = D.multiply_ct_sum(A, B, q, t)
+        for x in (A, B, want):
+            x.setflags(write=False)
+        _SUM_CASE[rung] = (N, moduli, t, names, A, B, want)
+    return _SUM_CASE[rung]
+
+
+@pytest.mark.parametrize("rung", SUM_RUNGS)
 def test_sum_hook_matches_the_model(rung):
-    N, moduli, t = rung_chain(rung)
+    N, moduli, t, names, A, B, want = sum_case(rung)
     q = moduli[:-1]
-    rng = np.random.default_rng(N + 31 * len(q))
-    names, A, B = M.hook_inputs(q, t, N, rng, names=M.SUB_FAMILY)       # one random pair and the extremes
-    extra = [random_pair(q, N, rng) for _ in range(2)]
-    A = np.concatenate([A, np.stack([e[0] for e in extra])])
-    B = np.concatenate([B, np.stack([e[1] for e in extra])])
-    n = A.shape[0]
-    assert n == len(M.SUB_FAMILY) + 2 and D.plan_terms(N, q, moduli[-1], t, n)[1]
-    want = D.multiply_ct_sum(A, B, q, t)
     db, _ = hook_db(N, moduli, t)
     got = db.ct_multiply_sum(A, B)
     assert got.shape == want.shape == (3, len(q), N)
@@ -113,7 +129,11 @@ def test_lazy_fold_at_its_limit():
 
     First with a scratch that holds the whole row in one block and the split over workgroups off: one thread sums all the
     children of a word, the case the fold is there for.  Then as the library chooses (default scratch: three blocks, each
-    split), and with ct_scratch_mb = 1: blocks of eight children, the accumulators carried sixteen times."""
+    split), and with ct_scratch_mb = 1: blocks of eight children, the accumulators carried sixteen times.
+
+    (The wrap this row would cause is the same 2^128 at every modulus of Q and B, which these six 60-bit primes round
+    away: a fold that comes too late is caught by test_lazy_fold_when_one_modulus_alone_would_wrap[four-polynomial] of
+    tests/test_gpu_ctmult_shared.py, not here.)"""
     N, moduli, t = rung_chain("k6-int")
     q = moduli[:-1]
     k = len(q)
