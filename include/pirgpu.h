@@ -623,14 +623,10 @@ uint64_t pirgpu_scan_bytes(const pirgpu_ctx* ctx);
  * digit of database and selectors is stored as a nibble (L - 1/2 bytes per residue instead of L). */
 int pirgpu_scan_info(pirgpu_ctx* ctx, uint32_t info[8]);
 /* Options by name (case-insensitive), e.g. "scan_mfma" (0 keeps the 64-bit multiply-accumulate scan for d >= 2),
- * "scan_mfma_wide" (0 / 1 forces the 8-wave / 4-wave scan kernel), "upper_blocks", "fuse_last", "last_ntt",
- * "tree40", "sel_f64", "split_upper", "loop_transforms" (0: one transform per workgroup everywhere),
- * "scan_mfma_wgs_batch" (workgroups of a database pass that shares the chip with another group), "tables_one_launch"
- * (0: one database-pass launch per run of equal tables instead of one per batch group), "scan_launches" (a counter: the
- * database-pass launches the batch pipeline queued so far; setting it overwrites the count), "upper_parts" (a counter of the
- * same kind: the parts the upper recursion levels have cut a row's children into so far -- chunks of the fused kernel or
- * blocks of the split form, counted once per level and query or group) -- DESIGN.md section 6
- * lists them.  A name that was not set falls back to the environment variable
+ * "scan_mfma_wgs_batch" (workgroups of a database pass that shares the chip with another group), "scan_launches" (a
+ * counter: the database-pass launches the batch pipeline queued so far; setting it overwrites the count).  The table
+ * under "Options" in DESIGN.md section 6 lists all of them with kind and default; pir_amd/csrc/options.h declares them.
+ * A name that was not set falls back to the environment variable
  * PIRGPU_<NAME> (the A/B scripts under tools/ use that), then to the built-in default; get_option returns -1 for
  * "built-in default".  Options that shape the workspace must be set before the context is first used
  * (FailedPrecondition afterwards).  The arithmetic flavour (PIRGPU_NTT_MODE) is fixed at pirgpu_create.

@@ -7,7 +7,8 @@
 //
 // Map of this file (search for "[n]"):
 //   [1]  state: Worker (one query in flight), BatchLane (a group of 8), KeySet, BatchSet, pirgpu_ctx
-//   [2]  helpers: errors, NTT / Encode tables, options, workspace geometry
+//   [2]  helpers: errors, NTT / Encode tables, workspace geometry; resolve_options turns the options (declared once, in
+//        options.h) into the context's fields
 //   [3]  oblivious expansion: expand_core (levels: ks_digit -> ks_mac_intt -> ks_mac_combine / ks_combine; last level
 //        in the NTT domain), expand_query_to_sv
 //   [4]  multiply: scan_group_mfma / scan_on_device, post_scan_stage (inverse NTT, upper levels, fold)
@@ -39,6 +40,7 @@
 #include "device_params.h"
 #include "host_math.h"
 #include "kernels.h"
+#include "options.h"
 #include "wire.h"
 
 using namespace pirgpu;
@@ -264,12 +266,6 @@ struct pirgpu_ctx {
   uint32_t cur_table = 0;             // table of the single-query entry points and test hooks (pirgpu_query_use_table)
   std::vector<uint64_t> tbl_loaded, tbl_zero;   // per table: plaintexts loaded / identically zero (tables > 1)
   std::vector<uint8_t> tbl_packed;    // per table: its operand layout is up to date (tables > 1)
-  uint64_t scan_launches = 0;         // database-pass launches of the batch pipeline so far (option SCAN_LAUNCHES reads it)
-  uint64_t ct_blocks = 0;             // product blocks post_scan_ctm_level queued so far (option CT_BLOCKS reads it)
-  uint64_t upper_parts = 0;           // chunks (fused) or blocks (split) of children the upper levels queued so far, per
-                                      // level and query or group (option UPPER_PARTS reads it)
-  uint64_t ct_relins = 0;             // ciphertexts its levels have key-switched so far (option CT_RELINS)
-  uint64_t ct_lifts = 0;              // polynomials its levels have lifted to the auxiliary base so far (option CT_LIFTS)
   uint32_t bits = 0;           // bits per coefficient for item packing
 
   int device = 0;
@@ -305,51 +301,59 @@ struct pirgpu_ctx {
   BatchSet sets[kBatchSets];
   BatchSet& bs();
   uint32_t n_active = 1;
-  uint32_t upper_blocks = 512;   // target workgroup count of upper_fused_kernel (PIRGPU_UPPER_BLOCKS)
-  uint32_t upper_blocks_batch = 64;   // the same per query in batch mode, where other queries fill the chip too: fewer
-                                      // chunks = fewer partial sums to write and fold (PIRGPU_UPPER_BLOCKS_BATCH)
-  uint32_t scan_wgs_batch = 128; // persistent workgroups (= CUs) of the MFMA scan in the batch pipeline; 0 = all CUs
-                                 // (PIRGPU_SCAN_MFMA_WGS_BATCH)
+  // Fields that resolve_options / resolve_live_options fill from the options (options.h has what each one means and
+  // why its default is what it is; the defaults themselves stand at the reads).  Nothing reads them before
+  // ensure_workspace has run.
+  uint32_t upper_blocks = 0;     // target workgroup count of upper_fused_kernel (option UPPER_BLOCKS)
+  uint32_t upper_blocks_batch = 0;    // the same per query in batch mode (option UPPER_BLOCKS_BATCH)
+  // live options, resolved when the workspace is built and whenever pirgpu_set_option sets one: the paths that queue GPU
+  // work read these fields, never a name or the environment
+  uint32_t scan_wgs_batch = 0;   // persistent workgroups (= CUs) of the MFMA scan in the batch pipeline; 0 = all CUs
+                                 // (option SCAN_MFMA_WGS_BATCH)
+  int64_t slots_scan_wgs = -1;   // the same for the slot-sharded step; -1: follows scan_wgs_batch (option SLOTS_SCAN_WGS unset)
+  bool slots_gather_ntt = false, slots_blk_major = false;   // options SLOTS_GATHER_NTT, SLOTS_SCAN_BLK_MAJOR
+  bool tables_one_launch = false;                           // option TABLES_ONE_LAUNCH
+  int64_t ctm_rowsum_splits = 0;                            // option CT_ROWSUM_SPLITS
   bool in_batch = false;         // set while the batch pipeline enqueues work
   uint32_t scan_nsplit = 1, scan_cps = 0, scan_rows = 0, scan_cols = 0;
-  uint32_t scan_rpt = 4, scan_block = 256;  // rows per thread / workgroup size of the scan kernel
+  uint32_t scan_rpt = 0, scan_block = 0;    // rows per thread / workgroup size of the scan kernel
   bool scan_limb = false;                   // 28-bit limb accumulators (all data moduli < 2^50)
   uint32_t mq_nq = 4, mq_rows = 1;          // batch mode: queries per database pass / rows per wave
-  bool mq_single = true;                    // use the LDS-shared scan kernel for single queries too
+  bool mq_single = false;                   // use the LDS-shared scan kernel for single queries too
   uint32_t mq_single_rows = 4;              // rows per wave of that kernel for a single query (2 or 4)
   bool mq_single_limb = false;              // single query: 128-bit accumulators need fewer registers (3 WG/CU)
   uint64_t scan_npt = 0;
   // digit-sliced int8-MFMA scan (scan_mfma.hip): d >= 2, database additionally held in operand layout
   bool mfma_on = false;
   MfmaGeom mg{};
-  uint32_t mfma_nq = kMaxMfmaQueries;       // queries per database pass in batch mode
-  bool mfma_single = true;                  // single queries use it too (off for matrices wider than one chunk)
+  uint32_t mfma_nq = 0;                     // queries per database pass in batch mode
+  bool mfma_single = false;                 // single queries use it too (off for matrices wider than one chunk)
   bool scan_f64_fold = false;               // the scan folds its digit diagonals in exact fp64 arithmetic (option
                                             // SCAN_F64_FOLD; every data modulus below 2^50)
   bool scan_f64_fold_batch = false;         // ... in the launches that serve a group of queries (option SCAN_F64_FOLD_BATCH)
   bool split_upper = false;                 // upper level as transform-to-scratch + elementwise MAC (N >= 16384 in the fp64
-                                            // flavours, where the fused kernel spills; PIRGPU_SPLIT_UPPER=0/1 overrides)
-  uint64_t split_upper_words = (3ull << 30) / 8;  // scratch budget per lane / worker (PIRGPU_SPLIT_UPPER_MB)
+                                            // flavours, where the fused kernel spills; option SPLIT_UPPER overrides)
+  uint64_t split_upper_words = 0;           // scratch budget per lane / worker (option SPLIT_UPPER_MB)
   // the digit kernel of the wide expansion levels and the transform kernel of the split upper level run all transforms
   // of one source polynomial in ONE workgroup: one load and one permutation per source, stores drain under the next
   // transform (option LOOP_TRANSFORMS; fp64 flavours)
-  bool loop_transforms = true;
+  bool loop_transforms = false;
   uint32_t loop_min_sources = 1024;         // ... from this many (tree ciphertext, digit) sources per launch on
   uint32_t fuse_mac_nodes = 128;            // ... from this many tree ciphertexts per level on (narrower levels are latency-
                                             // bound: two dependent transform kernels cost more than mac + light combine)
-  bool fuse_mac_combine = true;             // levels below the last: combine step in the data residues' MAC + inverse-NTT
-                                            // kernel (PIRGPU_FUSE_MAC_COMBINE=0: separate ks_combine pass)
-  bool fuse_last_level = true;              // last expansion level fused with the selector NTT (PIRGPU_FUSE_LAST=0: off)
-  bool last_level_ntt = true;               // ... and carried out in the NTT domain (PIRGPU_LAST_NTT=0: coefficient form)
-  bool tree40 = true;                       // expansion tree between fused wide levels as 5-byte polynomials (PIRGPU_TREE40=0: doubles)
+  bool fuse_mac_combine = false;            // levels below the last: combine step in the data residues' MAC + inverse-NTT
+                                            // kernel (option FUSE_MAC_COMBINE = 0: separate ks_combine pass)
+  bool fuse_last_level = false;             // last expansion level fused with the selector NTT (option FUSE_LAST = 0: off)
+  bool last_level_ntt = false;              // ... and carried out in the NTT domain (option LAST_NTT = 0: coefficient form)
+  bool tree40 = false;                      // expansion tree between fused wide levels as 5-byte polynomials (option TREE40 = 0: doubles)
   bool c0_ntt = false;                      // the fused levels keep the tree's c0 polynomials in NTT form (option C0_NTT = 1 / 2; measured slower)
   bool c0_ntt_split = false;                // ... with component 0 of a level as a launch of its own (C0_NTT = 2)
-  bool want_sel_f64 = true;
+  bool want_sel_f64 = false;
   bool sel_f64 = false;                     // batch lanes keep their selectors as exact doubles between the last expansion
                                             // level and their two consumers (sel_pack, upper level): no u64 round trip
-                                            // (fp64 flavours, MFMA scan, NTT-domain last level; PIRGPU_SEL_F64=0: off)
-  bool pack40 = false;                      // key-switch digits stored packed (PIRGPU_PACK40) ...
-  int pack_bytes = 5;                       // ... in 5 (all moduli < 2^39), 6 (< 2^47) or 7 (< 2^55) bytes per residue (PIRGPU_PACK_BYTES)
+                                            // (fp64 flavours, MFMA scan, NTT-domain last level; option SEL_F64 = 0: off)
+  bool pack40 = false;                      // key-switch digits stored packed (option PACK40) ...
+  int pack_bytes = 5;                       // ... in 5 (all moduli < 2^39), 6 (< 2^47) or 7 (< 2^55) bytes per residue (option PACK_BYTES)
   uint8_t* d_dbp = nullptr;
   bool packed_valid = false;
   bool staging_released = false;            // pirgpu_db_finalize(release): only the operand-layout copy is left
@@ -363,8 +367,8 @@ struct pirgpu_ctx {
   std::vector<BatchLane> lanes;             // created on the first batch
   uint64_t groups_run = 0;
   hipStream_t head_stream = nullptr;        // the narrow first levels of every group's expansion (HeadSlot)
-  uint32_t head_levels = 5;                 // levels 0 .. head_levels - 1 run there (option HEAD_LEVELS; 0: all on the lane)
-  uint32_t head_mode = 1;                   // option HEAD_MODE: 0 never, 1 batches staged with pirgpu_batch_stage_async, 2 always
+  uint32_t head_levels = 0;                 // levels 0 .. head_levels - 1 run there (option HEAD_LEVELS; 0: all on the lane)
+  uint32_t head_mode = 0;                   // option HEAD_MODE: 0 never, 1 batches staged with pirgpu_batch_stage_async, 2 always
   hipEvent_t ev_head_tail = nullptr;        // the head stream's position (an upload into a batch set waits for it)
   hipStream_t copy_stream = nullptr;        // device-to-host downloads of finished groups (pirgpu_batch_set_host_replies):
                                             // a lane that downloaded its own replies sat idle for 8 MB of PCIe per group
@@ -381,7 +385,7 @@ struct pirgpu_ctx {
   DevParams hp_aux{};                       // the auxiliary base as the "data primes" of a second parameter block:
   DevParams* dp_aux = nullptr;              // ntt_batch transforms at B with the context's own kernels and flavour
   CtmParams* d_ctm = nullptr;               // constants of the exact base conversions (ctmult.h)
-  uint64_t ctm_scratch_words = (256ull << 20) / 8;   // product scratch per owner (option CT_SCRATCH_MB)
+  uint64_t ctm_scratch_words = 0;           // product scratch per owner (option CT_SCRATCH_MB)
   bool ctm_shared_sel = false;              // a level's selectors are lifted and transformed once (option CT_SHARED_SEL)
   std::map<hipStream_t, CtmScratch> ctm_ws; // per owner of a multiply, keyed by its stream
 
@@ -397,9 +401,9 @@ struct pirgpu_ctx {
   int prof_cur = -1;           // event set of the run being recorded (-1: not recording)
   float timings[6]{};
 
-  // options by name (pirgpu_set_option); a name not set here falls back to the environment variable PIRGPU_<NAME>
-  // (A/B scripts under tools/), then to the built-in default
-  std::map<std::string, int64_t> opts;
+  // what pirgpu_set_option was given by name, and the counters (options.h); a name not set here falls back to the
+  // environment variable PIRGPU_<NAME> (A/B scripts under tools/), then to the built-in default
+  OptionStore options;
   std::string err;
   uint64_t gen = 0;         // unique per context (thread-local error messages are keyed on it, not on the address)
   std::recursive_mutex mu;  // per ABI call; pirgpu_process_request holds it across its whole body
@@ -633,22 +637,15 @@ void build_ctm_tables(pirgpu_ctx* c) {
 
 uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
 
+std::string upper_case(const char* s) {
+  std::string up(s);
+  for (char& ch : up) ch = (char)toupper((unsigned char)ch);
+  return up;
+}
+
 // Streamed database: bytes of one encoded row band -- the 16 rows of the scanned matrix that make up one row tile of the
 // operand layout -- as u64 residues (valid once ensure_workspace has fixed the geometry)
 uint64_t stream_band_bytes(const pirgpu_ctx* c) { return 16ull * c->scan_cols * c->k * c->N * 8; }
-
-// Option `name` (upper case, without the PIRGPU_ prefix): pirgpu_set_option's value, else the environment variable
-// PIRGPU_<name>, else dflt.  *present reports whether either was given.
-int64_t option(const pirgpu_ctx* c, const char* name, int64_t dflt, bool* present = nullptr) {
-  if (present) *present = true;
-  auto it = c->opts.find(name);
-  if (it != c->opts.end()) return it->second;
-  const std::string env = std::string("PIRGPU_") + name;
-  const char* v = pirgpu_env(env.c_str());
-  if (v && *v) return strtoll(v, nullptr, 10);
-  if (present) *present = false;
-  return dflt;
-}
 
 // waits for everything the batch pipeline has enqueued: lane streams (grouped expansion + multiply) and worker streams
 void sync_batch_streams(pirgpu_ctx* c) {
@@ -724,18 +721,150 @@ TablePlan plan_table_runs(const uint32_t* tables, uint32_t count, uint32_t group
 void alloc_worker(pirgpu_ctx* c, Worker& w);
 void ensure_expansion_buffers(pirgpu_ctx* c, Worker& w);
 
+// An option as the unsigned number most fields are (a negative value wraps, and the clamps below then cap it).
+uint32_t opt_u32(const pirgpu_ctx* c, OptId id, uint32_t dflt) { return (uint32_t)c->options.value(id, dflt); }
+
+bool ctm_shared_sel_default(const pirgpu_ctx* c) { return c->ctm && c->planes > 1; }
+
+// What pirgpu_get_option answers for an option that was given nowhere: -1, "the built-in default applies" -- or the
+// default itself where it depends on the context
+int64_t unset_report(const pirgpu_ctx* c, OptId id) { return id == OPT_CT_SHARED_SEL ? ctm_shared_sel_default(c) : -1; }
+
+// Live options -> fields.  Runs when the workspace is built and whenever pirgpu_set_option sets one of them, so that the
+// paths that queue GPU work read fields only; the environment is read here and nowhere later.
+void resolve_live_options(pirgpu_ctx* c) {
+  c->scan_wgs_batch = (uint32_t)std::max<int64_t>(0, c->options.value(OPT_SCAN_MFMA_WGS_BATCH, 128));
+  bool given = false;   // unset: the slot-sharded pass follows scan_wgs_batch, whatever that is set to later
+  const int64_t slots_wgs = c->options.value(OPT_SLOTS_SCAN_WGS, 0, &given);
+  c->slots_scan_wgs = given ? std::max<int64_t>(0, slots_wgs) : -1;
+  c->slots_gather_ntt = c->options.value(OPT_SLOTS_GATHER_NTT, 1) != 0;
+  c->slots_blk_major = c->options.value(OPT_SLOTS_SCAN_BLK_MAJOR, 1) != 0;
+  c->tables_one_launch = c->options.value(OPT_TABLES_ONE_LAUNCH, 1) != 0;
+  c->ctm_rowsum_splits = c->options.value(OPT_CT_ROWSUM_SPLITS, 0);
+}
+
+// Options in, fields out: everything ensure_workspace and the launch paths need to know about the options, read once
+// per context (options.h says what each option means and why its default is what it is).  Needs the scan's matrix
+// (scan_rows, scan_cols, scan_npt).  The order matters: mfma_geometry takes SCAN_MFMA_WIDE and SCAN_MFMA_TOP4, and the
+// defaults of SCAN_MFMA_SINGLE and SCAN_F64_FOLD depend on the geometry it returns.
+void resolve_options(pirgpu_ctx* c) {
+  const uint32_t N = c->N, k = c->k, d = c->d;
+  resolve_live_options(c);
+  c->upper_blocks = (uint32_t)std::max<int64_t>(1, c->options.value(OPT_UPPER_BLOCKS, 512));
+  c->upper_blocks_batch = (uint32_t)std::max<int64_t>(1, c->options.value(OPT_UPPER_BLOCKS_BATCH, 64));
+  c->upper_blocks_batch = std::min(c->upper_blocks_batch, c->upper_blocks);  // the scratch is sized for upper_blocks
+  // launch geometry of the 64-bit scan kernels
+  c->scan_limb = true;
+  for (uint32_t j = 0; j < k; ++j) c->scan_limb = c->scan_limb && (c->hp.mod[j].q >> 50) == 0;
+  if (!opt_u32(c, OPT_SCAN_LIMB, 1)) c->scan_limb = false;
+  //   (settled in rounds 1 - 2, constants since round 5: 4 queries share one pass of the 64-bit kernels in batch mode,
+  //   one row per wave then; a single query takes four rows per wave with limb accumulators off -- HISTORY section 9)
+  c->mq_nq = 4;
+  c->mq_rows = 1;
+  c->mq_single = opt_u32(c, OPT_SCAN_MQ_SINGLE, 1) != 0;
+  c->mq_single_rows = 4;
+  c->mq_single_limb = false;
+  c->scan_rpt = opt_u32(c, OPT_SCAN_ROWS, 4);
+  c->scan_block = opt_u32(c, OPT_SCAN_BLOCK, 256);
+  const uint32_t xblocks = (k * N / 2 + c->scan_block - 1) / c->scan_block;
+  const uint32_t yblocks = (c->scan_rows + c->scan_rpt - 1) / c->scan_rpt;
+  uint64_t have = (uint64_t)xblocks * std::max<uint32_t>(yblocks, 1) * c->scan_block / 256;
+  // split the columns only when whole rows cannot fill the chip (d = 1 / few rows)
+  uint32_t want = have >= 512 ? 1 : (uint32_t)ceil_div(1024, std::max<uint64_t>(have, 1));
+  want = opt_u32(c, OPT_SCAN_NSPLIT, want);
+  want = std::max<uint32_t>(1, std::min<uint32_t>(want, std::max<uint32_t>(c->scan_cols, 1)));
+  c->scan_cps = (uint32_t)ceil_div(std::max<uint32_t>(c->scan_cols, 1), want);
+  c->scan_nsplit = (uint32_t)ceil_div(std::max<uint32_t>(c->scan_cols, 1), c->scan_cps);
+  // expansion
+  c->fuse_last_level = opt_u32(c, OPT_FUSE_LAST, 1) != 0;
+  c->fuse_mac_combine = opt_u32(c, OPT_FUSE_MAC_COMBINE, 1) != 0;
+  c->last_level_ntt = opt_u32(c, OPT_LAST_NTT, 1) != 0;
+  {
+    const uint32_t v = opt_u32(c, OPT_C0_NTT, 0);
+    c->c0_ntt = v != 0;
+    c->c0_ntt_split = v >= 2;
+  }
+  c->want_sel_f64 = opt_u32(c, OPT_SEL_F64, 1) != 0;
+  c->tree40 = opt_u32(c, OPT_TREE40, 1) != 0;
+  c->fuse_mac_nodes = 128;       // swept in round 2 (HISTORY section 4): a constant since round 5
+  c->head_levels = std::min<uint32_t>(opt_u32(c, OPT_HEAD_LEVELS, 5), 8);
+  c->head_mode = std::min<uint32_t>(opt_u32(c, OPT_HEAD_MODE, 1), 2);
+  c->split_upper = opt_u32(c, OPT_SPLIT_UPPER, c->logN >= 14 ? 1 : 0) != 0 && c->mode != kNttInt;
+  // N = 32768: always the split form, in its integer version (upper_ntt + launch_upper_mac_int) -- that degree's table
+  // has no upper_fused
+  if (c->logN >= 15) c->split_upper = true;
+  c->split_upper_words = (uint64_t)opt_u32(c, OPT_SPLIT_UPPER_MB, 3072) * (1ull << 20) / 8;
+  c->loop_transforms = opt_u32(c, OPT_LOOP_TRANSFORMS, 1) != 0 && c->mode != kNttInt;
+  // (loop_min_sources: swept 512 - 4096 in round 4, 1 024 stays: a constant since round 5)
+  c->pack40 = opt_u32(c, OPT_PACK40, 1) != 0;
+  {
+    // packed width of the key-switch intermediates: the fewest whole bytes the moduli allow, or the wider one asked for
+    uint32_t bits = 0;
+    for (uint32_t j = 0; j <= k; ++j) bits = std::max<uint32_t>(bits, 64 - (uint32_t)__builtin_clzll(c->hp.mod[j].q));
+    const int need = bits <= 39 ? 5 : (bits <= 47 ? 6 : (bits <= 55 ? 7 : 8));
+    int want = (int)opt_u32(c, OPT_PACK_BYTES, (uint32_t)need);
+    if (want < need) want = need;
+    if (c->mode == kNttInt && want != 5) want = 8;
+    if (c->logN >= 15) want = 8;   // N = 32768: the integer kernels there keep their intermediates as u64
+    if (want > 7) c->pack40 = false;
+    c->pack_bytes = c->pack40 ? want : 5;
+    if (c->pack40 && c->pack_bytes == 7 && c->logN >= 14 && !opt_u32(c, OPT_TREE40_WIDE, 0)) c->tree40 = false;
+    const NttOps* ops = ntt_ops_for(N, c->pack_bytes);
+    if (ops != c->ops) {
+      c->ops = ops;
+      HIP_TRY(c->ops->configure(c->mode));
+    }
+  }
+  // int8-MFMA scan
+  bool wide_given = false;
+  const int64_t wide = c->options.value(OPT_SCAN_MFMA_WIDE, 0, &wide_given);
+  c->mg = mfma_geometry(c->hp, c->scan_rows, c->scan_cols, wide_given ? (int)(wide != 0) : -1,
+                        opt_u32(c, OPT_SCAN_MFMA_TOP4, 1) != 0);
+  c->mfma_on = opt_u32(c, OPT_SCAN_MFMA, 1) != 0 && d >= 2 && c->mg.L != 0 && c->scan_rows >= 8 && c->scan_npt > 0;
+  if (c->slot_sharded && (!c->mfma_on || c->mg.nchunks != 1 || c->nslots % c->mg.NW))
+    throw Fail{PIRGPU_INVALID_ARGUMENT, "a slot shard needs the int8-MFMA scan in one column chunk (d = 2, >= 8 rows, "
+                                        "moduli below 2^55, at most 28 column groups)"};
+  c->mfma_nq = std::max<uint32_t>(1, std::min<uint32_t>(opt_u32(c, OPT_SCAN_MFMA_NQ, kMaxMfmaQueries), kMaxMfmaQueries));
+  c->mfma_single = opt_u32(c, OPT_SCAN_MFMA_SINGLE, c->mg.nchunks == 1 ? 1 : 0) != 0;
+  c->scan_f64_fold = opt_u32(c, OPT_SCAN_F64_FOLD, c->mg.L >= 6 ? 1 : 0) != 0;
+  c->scan_f64_fold_batch = opt_u32(c, OPT_SCAN_F64_FOLD_BATCH, 1) != 0;
+  for (uint32_t j = 0; j < k; ++j) {
+    c->scan_f64_fold = c->scan_f64_fold && (c->hp.mod[j].q >> 50) == 0;
+    c->scan_f64_fold_batch = c->scan_f64_fold_batch && (c->hp.mod[j].q >> 50) == 0;
+  }
+  // selectors as doubles inside a lane: every query ciphertext must go through ks_last_ntt_kernel (>= 2 items each)
+  const uint64_t rem = c->dim_sum % N;
+  c->sel_f64 = c->want_sel_f64 && c->mfma_on && c->mode != kNttInt && c->fuse_last_level && c->last_level_ntt &&
+               !c->split_upper && c->dim_sum >= 2 && rem != 1 && !c->ctm;   // (the products read u64 selectors)
+  // ciphertext-multiplication mode
+  if (c->ctm) c->ctm_scratch_words = (uint64_t)std::max<int64_t>(1, c->options.value(OPT_CT_SCRATCH_MB, 256)) * (1ull << 20) / 8;
+  c->ctm_shared_sel = c->ctm && c->options.value(OPT_CT_SHARED_SEL, ctm_shared_sel_default(c)) != 0;
+  // streamed database
+  if (c->streamed && c->mfma_on) {
+    const uint64_t mb = (uint64_t)std::max<int64_t>(0, c->options.value(OPT_DB_STREAM_MB, 256));
+    c->stream_bands = std::min<uint64_t>(std::max<uint64_t>(1, (mb << 20) / stream_band_bytes(c)), 65535);
+    c->mfma_single = true;   // the 64-bit kernels read the staging copy, which a streamed context never has
+  }
+}
+
 void ensure_workspace(pirgpu_ctx* c) {
   if (c->ws_ready) return;
   const uint32_t N = c->N, k = c->k, d = c->d;
 
   const uint64_t m_max = std::min<uint64_t>(N, hm::next_power_two(std::max<uint32_t>(c->dim_sum, 1)));
   c->m_max = m_max;
-  // per-level node counts inside this shard and result buffers
   const uint64_t shard_pts = matrix_pts(c);
-  c->upper_blocks = (uint32_t)std::max<int64_t>(1, option(c, "UPPER_BLOCKS", c->upper_blocks));
-  c->upper_blocks_batch = (uint32_t)std::max<int64_t>(1, option(c, "UPPER_BLOCKS_BATCH", c->upper_blocks_batch));
-  c->scan_wgs_batch = (uint32_t)std::max<int64_t>(0, option(c, "SCAN_MFMA_WGS_BATCH", c->scan_wgs_batch));
-  c->upper_blocks_batch = std::min(c->upper_blocks_batch, c->upper_blocks);  // the scratch is sized for upper_blocks
+  // base-level scan geometry
+  if (d == 1) {
+    c->scan_rows = c->planes;
+    c->scan_cols = (uint32_t)(shard_pts / c->planes);
+  } else {
+    c->scan_cols = c->dims[d - 1];
+    c->scan_rows = (uint32_t)ceil_div(shard_pts, c->scan_cols);
+  }
+  c->scan_npt = shard_pts;
+  resolve_options(c);
+  // per-level node counts inside this shard and result buffers
   c->lvl_rows.assign(d, 0);
   c->lvl_cts.assign(d, 0);
   uint64_t pt_words = 0;
@@ -753,145 +882,6 @@ void ensure_workspace(pirgpu_ctx* c) {
     }
   }
   c->pt_words = pt_words;
-  // base-level scan geometry
-  if (d == 1) {
-    c->scan_rows = c->planes;
-    c->scan_cols = (uint32_t)(shard_pts / c->planes);
-  } else {
-    c->scan_cols = c->dims[d - 1];
-    c->scan_rows = (uint32_t)ceil_div(shard_pts, c->scan_cols);
-  }
-  c->scan_npt = shard_pts;
-  {
-    // Scan launch geometry.  Tuning knobs (environment, read once per context):
-    //   PIRGPU_SCAN_ROWS   rows accumulated per thread (1,2,3,4,6,8)
-    //   PIRGPU_SCAN_BLOCK  workgroup size (64..256)
-    //   PIRGPU_SCAN_NSPLIT column splits (partial sums reduced by reduce_splits_kernel)
-    auto env_u32 = [c](const char* name, uint32_t dflt) {   // name = "PIRGPU_<OPTION>"
-      return (uint32_t)option(c, name + 7, dflt);
-    };
-    //   PIRGPU_SCAN_LIMB   0 forces the generic 128-bit accumulators
-    c->scan_limb = true;
-    for (uint32_t j = 0; j < k; ++j) c->scan_limb = c->scan_limb && (c->hp.mod[j].q >> 50) == 0;
-    if (!env_u32("PIRGPU_SCAN_LIMB", 1)) c->scan_limb = false;
-    //   (settled in rounds 1 - 2, constants since round 5: 4 queries share one pass of the 64-bit kernels in batch mode,
-    //   one row per wave then; a single query takes four rows per wave with limb accumulators off -- HISTORY section 9)
-    //   PIRGPU_SCAN_MQ_SINGLE=0 routes single queries through scan_kernel instead of the LDS-shared
-    //                      scan_mq_kernel
-    c->mq_nq = 4;
-    c->mq_rows = 1;
-    c->mq_single = env_u32("PIRGPU_SCAN_MQ_SINGLE", 1) != 0;
-    c->mq_single_rows = 4;
-    c->mq_single_limb = false;
-    c->scan_rpt = env_u32("PIRGPU_SCAN_ROWS", 4);
-    c->scan_block = env_u32("PIRGPU_SCAN_BLOCK", 256);
-    const uint32_t xblocks = (k * N / 2 + c->scan_block - 1) / c->scan_block;
-    const uint32_t yblocks = (c->scan_rows + c->scan_rpt - 1) / c->scan_rpt;
-    uint64_t have = (uint64_t)xblocks * std::max<uint32_t>(yblocks, 1) * c->scan_block / 256;
-    // split the columns only when whole rows cannot fill the chip (d = 1 / few rows)
-    uint32_t want = have >= 512 ? 1 : (uint32_t)ceil_div(1024, std::max<uint64_t>(have, 1));
-    want = env_u32("PIRGPU_SCAN_NSPLIT", want);
-    want = std::max<uint32_t>(1, std::min<uint32_t>(want, std::max<uint32_t>(c->scan_cols, 1)));
-    c->scan_cps = (uint32_t)ceil_div(std::max<uint32_t>(c->scan_cols, 1), want);
-    c->scan_nsplit = (uint32_t)ceil_div(std::max<uint32_t>(c->scan_cols, 1), c->scan_cps);
-    //   PIRGPU_SCAN_MFMA=0 keeps the 64-bit multiply-accumulate kernels for d >= 2 as well
-    //   PIRGPU_SCAN_MFMA_NQ queries per database pass of the MFMA scan in batch mode (1..8)
-    c->fuse_last_level = env_u32("PIRGPU_FUSE_LAST", 1) != 0;
-    c->fuse_mac_combine = env_u32("PIRGPU_FUSE_MAC_COMBINE", 1) != 0;
-    c->last_level_ntt = env_u32("PIRGPU_LAST_NTT", 1) != 0;
-    //   PIRGPU_C0_NTT      c0 of the expansion tree in NTT form from the first fused level on (needs the fused levels and
-    //                      the NTT-domain last level; fp64 flavours)
-    {
-      // 0: off (the default: measured -4 % as two launches, -7.6 % as one kernel, profiles/r06_ab_c0_ntt_*.txt), 1: both
-      // components of a level in one kernel, 2: component 0 as a launch of its own
-      const uint32_t v = env_u32("PIRGPU_C0_NTT", 0);
-      c->c0_ntt = v != 0;
-      c->c0_ntt_split = v >= 2;
-    }
-    c->want_sel_f64 = env_u32("PIRGPU_SEL_F64", 1) != 0;
-    c->tree40 = env_u32("PIRGPU_TREE40", 1) != 0;
-    c->fuse_mac_nodes = 128;       // swept in round 2 (HISTORY section 4): a constant since round 5
-    //   PIRGPU_HEAD_LEVELS  expansion levels of a batch group that run ahead on the head stream (0: none)
-    c->head_levels = std::min<uint32_t>(env_u32("PIRGPU_HEAD_LEVELS", c->head_levels), 8);
-    c->head_mode = std::min<uint32_t>(env_u32("PIRGPU_HEAD_MODE", c->head_mode), 2);
-    c->split_upper = env_u32("PIRGPU_SPLIT_UPPER", c->logN >= 14 ? 1 : 0) != 0 && c->mode != kNttInt;
-    // N = 32768: always the split form, in its integer version (upper_ntt + launch_upper_mac_int) -- that degree's table
-    // has no upper_fused
-    if (c->logN >= 15) c->split_upper = true;
-    c->split_upper_words = (uint64_t)env_u32("PIRGPU_SPLIT_UPPER_MB", 3072) * (1ull << 20) / 8;
-    c->loop_transforms = env_u32("PIRGPU_LOOP_TRANSFORMS", 1) != 0 && c->mode != kNttInt;
-    // (loop_min_sources: swept 512 - 4096 in round 4, 1 024 stays: a constant since round 5)
-    c->pack40 = env_u32("PIRGPU_PACK40", 1) != 0;
-    // packed storage of the key-switch intermediates: the fp64 flavours store x + q (|x| <= q) in the fewest whole bytes
-    // -- 5 for q < 2^39, 6 for q < 2^47 (cfg 4: 43 / 44 bits), 7 for q < 2^55 (cfg 5: 48 / 49 bits) -- instead of doubles;
-    // the integer flavour knows the 5-byte form only.  PIRGPU_PACK_BYTES=<5|6|7> forces a (sufficient) width, 8 = doubles.
-    {
-      uint32_t bits = 0;
-      for (uint32_t j = 0; j <= k; ++j) bits = std::max<uint32_t>(bits, 64 - (uint32_t)__builtin_clzll(c->hp.mod[j].q));
-      const int need = bits <= 39 ? 5 : (bits <= 47 ? 6 : (bits <= 55 ? 7 : 8));
-      int want = (int)env_u32("PIRGPU_PACK_BYTES", (uint32_t)need);
-      if (want < need) want = need;
-      if (c->mode == kNttInt && want != 5) want = 8;
-      if (c->logN >= 15) want = 8;   // N = 32768: the integer kernels there keep their intermediates as u64
-      if (want > 7) c->pack40 = false;
-      c->pack_bytes = c->pack40 ? want : 5;
-      // (N = 16384 with 7-byte residues: the combine kernel that also reads and writes the TREE packed needs 68 bytes of
-      // scratch under the 128-register cap of a 1024-thread workgroup -- the tree stays in doubles there, digits and
-      // products are packed)
-      if (c->pack40 && c->pack_bytes == 7 && c->logN >= 14 && !env_u32("PIRGPU_TREE40_WIDE", 0)) c->tree40 = false;
-      const NttOps* ops = ntt_ops_for(N, c->pack_bytes);
-      if (ops != c->ops) {
-        c->ops = ops;
-        HIP_TRY(c->ops->configure(c->mode));
-      }
-    }
-    //   PIRGPU_SCAN_MFMA_WIDE  0 / 1 forces the 8-wave / 4-wave (one wave per SIMD, up to 7 k-steps) scan kernel
-    bool wide_given = false;
-    const int64_t wide = option(c, "SCAN_MFMA_WIDE", 0, &wide_given);
-    //   PIRGPU_SCAN_MFMA_TOP4=0 keeps the top digit of database and selectors as a full byte (scan_mfma.hip TOP4)
-    c->mg = mfma_geometry(c->hp, c->scan_rows, c->scan_cols, wide_given ? (int)(wide != 0) : -1,
-                          env_u32("PIRGPU_SCAN_MFMA_TOP4", 1) != 0);
-    c->mfma_on = env_u32("PIRGPU_SCAN_MFMA", 1) != 0 && d >= 2 && c->mg.L != 0 && c->scan_rows >= 8 && shard_pts > 0;
-    if (c->slot_sharded && (!c->mfma_on || c->mg.nchunks != 1 || c->nslots % c->mg.NW))
-      throw Fail{PIRGPU_INVALID_ARGUMENT, "a slot shard needs the int8-MFMA scan in one column chunk (d = 2, >= 8 rows, "
-                                          "moduli below 2^55, at most 28 column groups)"};
-    c->mfma_nq = std::max<uint32_t>(1, std::min<uint32_t>(env_u32("PIRGPU_SCAN_MFMA_NQ", kMaxMfmaQueries),
-                                                          kMaxMfmaQueries));
-    //   PIRGPU_SCAN_MFMA_SINGLE: a single query on a matrix wider than one column chunk pays the partial-sum
-    //   round trip for one query only; there the 64-bit kernels on the u64 copy are faster (cfg 4: 5.6 vs 6.4 ms)
-    c->mfma_single = env_u32("PIRGPU_SCAN_MFMA_SINGLE", c->mg.nchunks == 1 ? 1 : 0) != 0;
-    //   PIRGPU_SCAN_F64_FOLD  fp64 fold of the digit diagonals (moduli below 2^50).  Default: on from 6 digits per
-    //   residue (cfg 4: scan 4.53 against 4.76 ms, cfg 5: 8.33 against 8.57, same box); at 5 digits (cfg 3) the
-    //   single-query pass measured 3 % slower with it (0.212 against 0.206 ms) and the batch step 0.5 % faster: off
-    c->scan_f64_fold = env_u32("PIRGPU_SCAN_F64_FOLD", c->mg.L >= 6 ? 1 : 0) != 0;
-    //   PIRGPU_SCAN_F64_FOLD_BATCH  the same choice for the launches that serve a GROUP of queries (batch pipeline on part
-    //   of the chip, slot-sharded step): on whenever the moduli allow -- with 16 result columns per tile instead of 2 the
-    //   fold is 8 x the work per database byte, and there the cheaper fold pays at 5 digits too (round 6, same box, three
-    //   alternating runs: 5 362 / 5 426 / 5 363 against 5 322 / 5 331 / 5 319 queries/s; profiles/r06_ab_scan_store_fold.txt)
-    c->scan_f64_fold_batch = env_u32("PIRGPU_SCAN_F64_FOLD_BATCH", 1) != 0;
-    for (uint32_t j = 0; j < k; ++j) {
-      c->scan_f64_fold = c->scan_f64_fold && (c->hp.mod[j].q >> 50) == 0;
-      c->scan_f64_fold_batch = c->scan_f64_fold_batch && (c->hp.mod[j].q >> 50) == 0;
-    }
-    // selectors as doubles inside a lane: every query ciphertext must go through ks_last_ntt_kernel (>= 2 items each)
-    const uint64_t rem = c->dim_sum % N;
-    c->sel_f64 = c->want_sel_f64 && c->mfma_on && c->mode != kNttInt && c->fuse_last_level && c->last_level_ntt &&
-                 !c->split_upper && c->dim_sum >= 2 && rem != 1 && !c->ctm;   // (the products read u64 selectors)
-    //   CT_SCRATCH_MB  ciphertext-multiplication mode: megabytes of product scratch per worker / lane; the children of a
-    //   level are multiplied in blocks that fit it (at least one child of every query of a group)
-    if (c->ctm) c->ctm_scratch_words = (uint64_t)std::max<int64_t>(1, option(c, "CT_SCRATCH_MB", 256)) * (1ull << 20) / 8;
-    //   CT_SHARED_SEL  ciphertext-multiplication mode: 1 = the selectors of a level, the same for every row and plane, are
-    //   lifted and transformed once per level and group and only the ciphertext half of a pair per block
-    //   (ctmult_shared.hip); 0 = all four polynomials of every pair.  Default: 1 on a context with wide items, 0 elsewhere
-    c->ctm_shared_sel = c->ctm && option(c, "CT_SHARED_SEL", c->planes > 1) != 0;
-    //   DB_STREAM_MB  streamed database: megabytes of encoded plaintexts per load chunk, rounded down to whole row bands
-    //   (at least one)
-    if (c->streamed && c->mfma_on) {
-      const uint64_t mb = (uint64_t)std::max<int64_t>(0, option(c, "DB_STREAM_MB", 256));
-      c->stream_bands = std::min<uint64_t>(std::max<uint64_t>(1, (mb << 20) / stream_band_bytes(c)), 65535);
-      c->mfma_single = true;   // the 64-bit kernels read the staging copy, which a streamed context never has
-    }
-  }
   c->ws_ready = true;
   if (c->workers.empty()) c->workers.emplace_back();
   c->workers[0].stream = c->stream;
@@ -1388,7 +1378,7 @@ void scan_group_mfma(pirgpu_ctx* c, hipStream_t st, uint8_t*& selp, const MfmaPt
   }
   HIP_TRY(launch_scan_mfma(st, c->dp, c->mg, table_dbp(c, table), packed, out, out_qstride, n, c->scan_rows, kN, words, wgs,
                            n > 1 ? (c->scan_f64_fold || c->scan_f64_fold_batch) : c->scan_f64_fold));
-  if (!profiled) ++c->scan_launches;
+  if (!profiled) ++c->options.counter(OPT_SCAN_LAUNCHES);
   if (timed) {
     HIP_TRY(hipEventRecord(c->bscan_ev[2 * c->bscan_n + 1], st));
     ++c->bscan_n;
@@ -1531,8 +1521,8 @@ uint32_t ctm_rowsum_block(pirgpu_ctx* c, hipStream_t st, const CtmRegions& r, ui
   const uint64_t wgs = (uint64_t)rows * nq * k * (N / 256);
   const uint64_t room = (uint64_t)cap / ((uint64_t)rows * nq);   // accumulators per row and query: its own + the partial sums
   uint32_t splits = (uint32_t)std::min<uint64_t>({ceil_div(kCtmRowsumWgs, wgs), (uint64_t)nj, room ? room - 1 : 0});
-  //   CT_ROWSUM_SPLITS  (A/B, tests) at most this many workgroups share a row's children; 1: never split; 0: as above
-  const int64_t most = option(c, "CT_ROWSUM_SPLITS", 0);
+  // option CT_ROWSUM_SPLITS (A/B, tests): at most this many workgroups share a row's children; 1: never split; 0: as above
+  const int64_t most = c->ctm_rowsum_splits;
   if (most > 0) splits = (uint32_t)std::min<int64_t>(splits, most);
   if (splits < 2) splits = 1;
   if ((uint64_t)(splits > 1 ? splits + 1 : 1) * rows * nq > cap) throw Fail{PIRGPU_INTERNAL, "row-sum accumulators exceed the product scratch"};
@@ -1576,7 +1566,7 @@ CtmSel ctm_hook_selectors(pirgpu_ctx* c, hipStream_t st, const uint64_t* b, uint
   HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp_aux, selb, n * 2 * kb, kb, 0, false));
   HIP_TRY(hipMemcpyAsync(selq, b, (size_t)n * c->ctw * 8, hipMemcpyDeviceToDevice, st));
   HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp, selq, n * 2 * k, k, 0, false));
-  c->ct_lifts += 2 * n;
+  c->options.counter(OPT_CT_LIFTS) += 2 * n;
   CtmSel sel{};
   sel.q.p[0] = selq;
   sel.b.p[0] = selb;
@@ -1635,7 +1625,7 @@ void post_scan_ctm_level(pirgpu_ctx* c, const Stage& sg, uint32_t l) {
       HIP_TRY(launch_ctm_lift_polys(st, c->d_ctm, k, N, ws.selc + (size_t)s0 * ctw, 0, 1, 0, std::min<uint32_t>(32767, nq * dim - s0),
                                     nullptr, ws.selb + (size_t)s0 * 2 * c->kb * N));
     HIP_TRY(c->ops->ntt_batch(st, c->mode, c->dp_aux, ws.selb, (uint64_t)nq * dim * 2 * c->kb, c->kb, 0, false));
-    c->ct_lifts += (uint64_t)2 * dim * nq;
+    c->options.counter(OPT_CT_LIFTS) += (uint64_t)2 * dim * nq;
     for (uint32_t q = 0; q < nq; ++q) {
       sel.q.p[q] = static_cast<const uint64_t*>(sg.sel.p[q]) + (size_t)c->sv_off[l] * ctw;
       sel.b.p[q] = ws.selb + (size_t)q * dim * 2 * c->kb * N;
@@ -1644,13 +1634,13 @@ void post_scan_ctm_level(pirgpu_ctx* c, const Stage& sg, uint32_t l) {
   const uint32_t bj = std::max<uint32_t>(1, cap / nq);   // children per block (of every query of the group)
   for (uint64_t j0 = 0; j0 < nch; j0 += bj) {
     const uint32_t nj = (uint32_t)std::min<uint64_t>(bj, nch - j0), n = nj * nq;
-    ++c->ct_blocks;
-    c->ct_lifts += (uint64_t)(shared ? 2 : 4) * n;
+    ++c->options.counter(OPT_CT_BLOCKS);
+    c->options.counter(OPT_CT_LIFTS) += (uint64_t)(shared ? 2 : 4) * n;
     if (c->ctm_deferred) {
       const uint32_t fin = ctm_rowsum_block(c, st, r, cap, sg.lvl[l + 1], c->lvl_cts[l + 1] * ctw, ws.selc, dim, nq, nch,
                                             (uint32_t)j0, nj, shared ? &sel : nullptr);
       if (!fin) continue;
-      c->ct_relins += (uint64_t)fin * nq;
+      c->options.counter(OPT_CT_RELINS) += (uint64_t)fin * nq;
       ctm_relinearize(c, st, r, fin * nq, key);
       // relin + (0, d1) into the finished rows: the accumulation with one child per row (pirgpu_relinearize's form)
       HIP_TRY(launch_ctm_accumulate(st, c->dp, k, N, r.yq, r.d, sg.lvl[l] + (size_t)(j0 / dim) * ctw, c->lvl_cts[l] * ctw, 1,
@@ -1658,7 +1648,7 @@ void post_scan_ctm_level(pirgpu_ctx* c, const Stage& sg, uint32_t l) {
       if ((j0 + nj) % dim != 0 && j0 + nj < nch) ctm_carry_row(c, st, r, nq, fin);
       continue;
     }
-    c->ct_relins += n;
+    c->options.counter(OPT_CT_RELINS) += n;
     if (shared)
       ctm_products_sel(c, st, r, sg.lvl[l + 1], c->lvl_cts[l + 1] * ctw, sel, dim, nq, (uint32_t)j0, n);
     else
@@ -1748,7 +1738,7 @@ void post_scan_stage(pirgpu_ctx* c, const Stage& sg, Worker* profiled) {
         *sg.up_scratch_words = unit * blk;
       }
       for (uint32_t b0 = 0; b0 < nd; b0 += blk) {
-        ++c->upper_parts;
+        ++c->options.counter(OPT_UPPER_PARTS);
         HIP_TRY(c->ops->upper_ntt(st, c->mode, c->dp, k, c->E, sg.lvl[l + 1], *sg.up_scratch, (uint32_t)rows, c->dims[l],
                                   (uint32_t)nch, (uint32_t)C, b0, blk, sg.n, c->lvl_cts[l + 1] * ctw, c->loop_transforms));
         if (c->mode == kNttInt)   // N = 32768
@@ -1762,7 +1752,7 @@ void post_scan_stage(pirgpu_ctx* c, const Stage& sg, Worker* profiled) {
       }
       if (l == 0 && profiled) record(c, *profiled, PH_FINAL);
     } else {
-      c->upper_parts += n_chunks;
+      c->options.counter(OPT_UPPER_PARTS) += n_chunks;
       HIP_TRY(c->ops->upper_fused(st, c->mode, c->dp, k, c->E, sg.lvl[l + 1], sg.sel, sg.pt_buf, (uint32_t)rows,
                                   c->dims[l], (uint32_t)nch, sv_first, (uint32_t)C, chunk_len, n_chunks, sg.n,
                                   c->lvl_cts[l + 1] * ctw, c->pt_words, sg.sel_f64));
@@ -2123,93 +2113,29 @@ int pirgpu_set_transparent_policy(pirgpu_ctx* c, int allow) {
   });
 }
 
-// Options the library understands (upper case in the environment: PIRGPU_<NAME>); `early` ones shape the workspace
-// and must be set before the context is first used.
-static const struct { const char* name; bool early; } kOptions[] = {
-    {"UPPER_BLOCKS", true}, {"UPPER_BLOCKS_BATCH", true}, {"SCAN_MFMA_WGS_BATCH", false}, {"SCAN_LIMB", true},
-    {"SCAN_MQ_SINGLE", true}, {"SCAN_ROWS", true}, {"SCAN_BLOCK", true}, {"SCAN_NSPLIT", true},
-    {"FUSE_LAST", true}, {"FUSE_MAC_COMBINE", true}, {"LAST_NTT", true}, {"C0_NTT", true}, {"SEL_F64", true}, {"TREE40", true},
-    {"SPLIT_UPPER", true}, {"SPLIT_UPPER_MB", true}, {"PACK40", true}, {"PACK_BYTES", true}, {"TREE40_WIDE", true},
-    {"SCAN_MFMA", true}, {"SCAN_MFMA_WIDE", true}, {"SCAN_MFMA_TOP4", true}, {"SCAN_MFMA_NQ", true}, {"SCAN_MFMA_SINGLE", true},
-    {"HEAD_LEVELS", true}, {"HEAD_MODE", true}, {"SCAN_F64_FOLD", true}, {"SCAN_F64_FOLD_BATCH", true}, {"LOOP_TRANSFORMS", true},
-    {"SLOTS_SCAN_WGS", false}, {"SLOTS_GATHER_NTT", false}, {"SLOTS_SCAN_BLK_MAJOR", false}, {"DB_STREAM_MB", true},
-    {"CT_SCRATCH_MB", true}, {"CT_SHARED_SEL", true},
-    // contexts with tables: 0 = one database-pass launch per run of equal tables instead of one per group (A/B);
-    // SCAN_LAUNCHES is a COUNTER, not a choice: get returns the database-pass launches the batch pipeline queued so far,
-    // set overwrites the count (0 to start over)
-    {"TABLES_ONE_LAUNCH", false}, {"SCAN_LAUNCHES", false},
-    // CT_BLOCKS is a counter of the same kind: the product blocks the upper levels of the ciphertext-multiplication mode
-    // queued so far (one per level and query or group when the level's children fit CT_SCRATCH_MB)
-    {"CT_BLOCKS", false},
-    // UPPER_PARTS, likewise: the parts the upper recursion levels cut a row's children into so far -- chunks of the fused
-    // kernel (their sums meet in reduce_splits_kernel) or blocks of the split form (carried in `acc`), counted once per
-    // level and query or group
-    {"UPPER_PARTS", false},
-    // CT_RELINS, likewise: the ciphertexts those levels have key-switched so far -- one per pair, or (deferred rounding)
-    // one per row and query
-    {"CT_RELINS", false}, {"CT_ROWSUM_SPLITS", false},
-    // CT_LIFTS, likewise: the polynomials those levels have lifted to the auxiliary base so far -- 4 per pair, or
-    // (CT_SHARED_SEL) 2 per pair and 2 dims[l] per query, level and group; the hooks pirgpu_ct_multiply and
-    // pirgpu_ct_multiply_sum count the same way, 2 per selector of the call
-    {"CT_LIFTS", false},
-};
-
+// Options by name: options.h declares them, resolve_options / resolve_live_options turn them into the context's fields.
 int pirgpu_set_option(pirgpu_ctx* c, const char* name, int64_t value) {
   return guarded(c, [&]() -> int {
     if (!name) return fail(c, PIRGPU_INVALID_ARGUMENT, "null option name");
-    std::string up(name);
-    for (char& ch : up) ch = (char)toupper((unsigned char)ch);
-    for (const auto& o : kOptions) {
-      if (up != o.name) continue;
-      if (o.early && c->ws_ready)
-        return fail(c, PIRGPU_FAILED_PRECONDITION, "option " + up + " shapes the workspace: set it before the context is first used");
-      if (up == "SCAN_LAUNCHES") {
-        c->scan_launches = (uint64_t)std::max<int64_t>(0, value);
-        return PIRGPU_OK;
-      }
-      if (up == "CT_BLOCKS") {
-        c->ct_blocks = (uint64_t)std::max<int64_t>(0, value);
-        return PIRGPU_OK;
-      }
-      if (up == "UPPER_PARTS") {
-        c->upper_parts = (uint64_t)std::max<int64_t>(0, value);
-        return PIRGPU_OK;
-      }
-      if (up == "CT_RELINS") {
-        c->ct_relins = (uint64_t)std::max<int64_t>(0, value);
-        return PIRGPU_OK;
-      }
-      if (up == "CT_LIFTS") {
-        c->ct_lifts = (uint64_t)std::max<int64_t>(0, value);
-        return PIRGPU_OK;
-      }
-      c->opts[up] = value;
-      if (up == "SCAN_MFMA_WGS_BATCH") c->scan_wgs_batch = (uint32_t)std::max<int64_t>(0, value);
-      return PIRGPU_OK;
-    }
-    return fail(c, PIRGPU_INVALID_ARGUMENT, "unknown option " + up);
+    const OptId id = find_option(name);
+    if (id == OPT_COUNT) return fail(c, PIRGPU_INVALID_ARGUMENT, "unknown option " + upper_case(name));
+    const OptRow& row = kOptRows[id];
+    if (row.kind == OptKind::Early && c->ws_ready)
+      return fail(c, PIRGPU_FAILED_PRECONDITION,
+                  std::string("option ") + row.name + " shapes the workspace: set it before the context is first used");
+    c->options.set(id, value);
+    if (row.kind == OptKind::Live) resolve_live_options(c);
+    return PIRGPU_OK;
   });
 }
 
 int pirgpu_get_option(pirgpu_ctx* c, const char* name, int64_t* value) {
   return guarded(c, [&]() -> int {
     if (!name || !value) return fail(c, PIRGPU_INVALID_ARGUMENT, "null argument");
-    std::string up(name);
-    for (char& ch : up) ch = (char)toupper((unsigned char)ch);
-    for (const auto& o : kOptions)
-      if (up == o.name) {
-        bool present = false;
-        *value = option(c, o.name, -1, &present);   // -1: not set anywhere, the built-in default applies
-        if (up == "SCAN_LAUNCHES") *value = (int64_t)c->scan_launches;
-        if (up == "CT_BLOCKS") *value = (int64_t)c->ct_blocks;
-        if (up == "UPPER_PARTS") *value = (int64_t)c->upper_parts;
-        if (up == "CT_RELINS") *value = (int64_t)c->ct_relins;
-        if (up == "CT_LIFTS") *value = (int64_t)c->ct_lifts;
-        // (the default depends on the context: report what applies, not -1)
-        if (up == "CT_SHARED_SEL" && !present) *value = c->ctm && c->planes > 1;
-        return PIRGPU_OK;
-      }
-    return fail(c, PIRGPU_INVALID_ARGUMENT, "unknown option " + up);
+    const OptId id = find_option(name);
+    if (id == OPT_COUNT) return fail(c, PIRGPU_INVALID_ARGUMENT, "unknown option " + upper_case(name));
+    *value = c->options.get(id, unset_report(c, id));
+    return PIRGPU_OK;
   });
 }
 
@@ -2304,7 +2230,7 @@ int pirgpu_ct_multiply(pirgpu_ctx* c, const uint64_t* a, const uint64_t* b, uint
       uint64_t* d_b = d_in + (size_t)m * ctw;
       HIP_TRY(hipMemcpyAsync(d_in, a + p0 * ctw, (size_t)m * ctw * 8, hipMemcpyHostToDevice, c->stream));
       HIP_TRY(hipMemcpyAsync(d_b, b + p0 * ctw, (size_t)m * ctw * 8, hipMemcpyHostToDevice, c->stream));
-      c->ct_lifts += (uint64_t)(shared ? 2 : 4) * m;
+      c->options.counter(OPT_CT_LIFTS) += (uint64_t)(shared ? 2 : 4) * m;
       if (shared) {
         uint64_t* d_selq = d_b + (size_t)m * ctw;
         const CtmSel sel = ctm_hook_selectors(c, c->stream, d_b, m, d_selq, d_selq + (size_t)m * ctw);
@@ -2357,7 +2283,7 @@ int pirgpu_ct_multiply_sum(pirgpu_ctx* c, const uint64_t* a, const uint64_t* b, 
     uint32_t fin = 0;
     for (uint64_t j0 = 0; j0 < n; j0 += cap) {
       const uint32_t nj = (uint32_t)std::min<uint64_t>(cap, n - j0);
-      c->ct_lifts += (uint64_t)(shared ? 2 : 4) * nj;
+      c->options.counter(OPT_CT_LIFTS) += (uint64_t)(shared ? 2 : 4) * nj;
       fin += ctm_rowsum_block(c, c->stream, r, cap, d_a, 0, d_b, (uint32_t)n, 1, n, (uint32_t)j0, nj,
                               shared ? &sel : nullptr);   // (nothing to carry forward)
     }
@@ -3915,7 +3841,7 @@ static void scan_group_runs(pirgpu_ctx* c, BatchLane& ln, const MfmaPtrs& col, u
   const uint32_t nch = c->mg.nchunks;
   ensure_packed(c);
   uint64_t* const out_base = ln.lvl[c->d - 1];
-  if (!option(c, "TABLES_ONE_LAUNCH", 1) || !scan_mfma_runs_supported(c->mg)) {
+  if (!c->tables_one_launch || !scan_mfma_runs_supported(c->mg)) {
     for (uint32_t r = 0; r < nr; ++r) {
       MfmaPtrs cr{};
       for (uint32_t q = rb[r]; q < rb[r + 1]; ++q) cr.p[q - rb[r]] = col.p[q];
@@ -3953,7 +3879,7 @@ static void scan_group_runs(pirgpu_ctx* c, BatchLane& ln, const MfmaPtrs& col, u
   }
   HIP_TRY(launch_scan_mfma_runs(ln.stream, c->dp, c->mg, grp, c->scan_rows, kN, words, wgs,
                                 c->scan_f64_fold || c->scan_f64_fold_batch, out_qstride));
-  ++c->scan_launches;
+  ++c->options.counter(OPT_SCAN_LAUNCHES);
   if (timed) {
     HIP_TRY(hipEventRecord(c->bscan_ev[2 * c->bscan_n + 1], ln.stream));
     ++c->bscan_n;
@@ -4534,16 +4460,14 @@ int pirgpu_slots_scan_async(pirgpu_ctx* c, const uint8_t* device_packed, uint32_
     const uint64_t piece = (uint64_t)c->nslots * c->mg.KG * c->mg.tile_bytes;      // my slots of one packed group
     const uint64_t qwords = (uint64_t)c->scan_rows * 2 * c->nslots;                // row sums of one query on my slots
     // workgroups: the pass shares the chip with the other lane's expansion like the single-GPU batch pass (option
-    // SLOTS_SCAN_WGS; 0 = one per CU).  Units in (slot block, group) order (option SLOTS_SCAN_BLK_MAJOR, default on):
-    // the workgroups running side by side then read the same database tiles for different groups -- the launch was
-    // 6 % (cfg 3) / 11 % (cfg 4) shorter than with one sweep of the slots per group, the step 1.2 - 1.5 %
-    const uint32_t wgs = (uint32_t)std::max<int64_t>(0, option(c, "SLOTS_SCAN_WGS", c->scan_wgs_batch));
+    // SLOTS_SCAN_WGS; unset: as many as that pass).  Units in (slot block, group) order: option SLOTS_SCAN_BLK_MAJOR
+    const uint32_t wgs = c->slots_scan_wgs < 0 ? c->scan_wgs_batch : (uint32_t)c->slots_scan_wgs;
     ScanGroups grp{};
     auto flush = [&]() {
       if (!grp.n) return;
       HIP_TRY(launch_scan_mfma_groups(ln.stream, c->dp, c->mg, c->d_dbp, grp, c->scan_rows, 0, wgs,
                                       c->scan_f64_fold || c->scan_f64_fold_batch, c->slot0,
-                                      c->nslots, qwords, c->nslots, option(c, "SLOTS_SCAN_BLK_MAJOR", 1) != 0));
+                                      c->nslots, qwords, c->nslots, c->slots_blk_major));
       grp = ScanGroups{};
     };
     for (uint32_t r = 0; r < n_ranks; ++r)
@@ -4587,7 +4511,7 @@ int pirgpu_slots_finish_async(pirgpu_ctx* c, const uint64_t* device_rowsums, uin
       // rank h's block of the receive buffer holds [count][RC][slots of h]: the group's queries are rows j0 .. j0 + B of
       // it; the inverse transform of the row sums (database.cpp:250-254) gathers them from there (option
       // SLOTS_GATHER_NTT = 0: a separate assembly pass, then the plain in-place transform)
-      bool gather = option(c, "SLOTS_GATHER_NTT", 1) != 0;
+      bool gather = c->slots_gather_ntt;
       const uint32_t nt = c->N >> ntt_log_ept((int)c->logN);    // threads of a transform workgroup
       for (uint32_t r = 0; r <= n_ranks; ++r) gather = gather && map.cut[r] % nt == 0;
       if (gather)

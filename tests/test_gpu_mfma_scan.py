@@ -179,6 +179,60 @@ def test_options_by_name_replace_the_environment():
     db.close()
 
 
+# every option of the ABI with its kind, written out (pir_amd/csrc/options.h declares them; tests/cpp/options_test.cpp
+# holds the same three lists against the registry itself)
+EARLY_OPTIONS = ["UPPER_BLOCKS", "UPPER_BLOCKS_BATCH", "SCAN_LIMB", "SCAN_MQ_SINGLE", "SCAN_ROWS", "SCAN_BLOCK", "SCAN_NSPLIT",
+                 "FUSE_LAST", "FUSE_MAC_COMBINE", "LAST_NTT", "C0_NTT", "SEL_F64", "TREE40", "SPLIT_UPPER", "SPLIT_UPPER_MB",
+                 "PACK40", "PACK_BYTES", "TREE40_WIDE", "SCAN_MFMA", "SCAN_MFMA_WIDE", "SCAN_MFMA_TOP4", "SCAN_MFMA_NQ",
+                 "SCAN_MFMA_SINGLE", "HEAD_LEVELS", "HEAD_MODE", "SCAN_F64_FOLD", "SCAN_F64_FOLD_BATCH", "LOOP_TRANSFORMS",
+                 "DB_STREAM_MB", "CT_SCRATCH_MB", "CT_SHARED_SEL"]
+LIVE_OPTIONS = {"SCAN_MFMA_WGS_BATCH": 96, "SLOTS_SCAN_WGS": 64, "SLOTS_GATHER_NTT": 0, "SLOTS_SCAN_BLK_MAJOR": 0,
+                "TABLES_ONE_LAUNCH": 0, "CT_ROWSUM_SPLITS": 1}          # name -> the value the test sets
+COUNTER_OPTIONS = ["SCAN_LAUNCHES", "CT_BLOCKS", "UPPER_PARTS", "CT_RELINS", "CT_LIFTS"]
+
+
+def test_every_option_by_kind(monkeypatch):
+    """All 42 options on one small context (no ciphertext multiplication: its counters exist and read 0): what get
+    answers before the first use, and after it that early options are refused by name, live ones are taken and reported
+    back, counters are overwritten (negative: 0) -- and that none of it changes a reply."""
+    assert len(EARLY_OPTIONS) == 31 and len(LIVE_OPTIONS) == 6 and len(COUNTER_OPTIONS) == 5
+    assert len(set(EARLY_OPTIONS) | set(LIVE_OPTIONS) | set(COUNTER_OPTIONS)) == 42
+    for name in EARLY_OPTIONS + list(LIVE_OPTIONS) + COUNTER_OPTIONS:
+        monkeypatch.delenv("PIRGPU_" + name, raising=False)
+    s = setup_with_dims(0, 2048, [17, 17], N=4096, plain_bits=24)
+    db, srv = make(s)
+    for name in EARLY_OPTIONS + list(LIVE_OPTIONS):
+        assert db.get_option(name) == (0 if name == "CT_SHARED_SEL" else -1), name      # given nowhere
+    for name in COUNTER_OPTIONS:
+        assert db.get_option(name) == 0, name
+    n = s.params.num_items
+    check_queries(s, srv, [n // 2 + 1])
+    for name in EARLY_OPTIONS:
+        with pytest.raises(pir_amd.PirGpuError) as e:
+            db.set_option(name.lower(), 1)
+        assert e.value.code == pir_amd.StatusCode.FAILED_PRECONDITION and name in e.value.message, name
+    assert db.get_option("CT_SHARED_SEL") == 0                     # the same report after the first use
+    for name, value in LIVE_OPTIONS.items():
+        db.set_option(name, value)
+        assert db.get_option(name.lower()) == value, name
+    for name in COUNTER_OPTIONS:
+        db.set_option(name, 7)
+        assert db.get_option(name) == 7, name
+        db.set_option(name, -3)
+        assert db.get_option(name) == 0, name
+    # the replies are what they were: a single query, and a group through the batch pipeline (whose database pass now
+    # runs on 96 workgroups)
+    check_queries(s, srv, [3, n - 1])
+    idx = [1, n // 3, n - 2]
+    queries = np.stack([s.client.create_query_for(s.params, i) for i in idx])
+    got = srv.process_batch(queries, n_workers=4)
+    for i in range(len(idx)):
+        rc, exp = s.orc.process_query(s.db_ntt, s.params.dimensions, queries[i], s.galois_keys)
+        assert rc == 0 and np.array_equal(got[i], exp), idx[i]
+    assert db.get_option("SCAN_LAUNCHES") >= 1                     # counting went on from the 0 set above
+    db.close()
+
+
 def test_small_row_counts_use_the_valu_scan():
     s = PirSetup(300, 2048, 2, N=4096, plain_bits=24)        # 60 plaintexts -> dims [8, 8]: rows = 8 -> MFMA
     db, srv = make(s)
