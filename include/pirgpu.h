@@ -631,7 +631,15 @@ int pirgpu_scan_info(pirgpu_ctx* ctx, uint32_t info[8]);
  * "built-in default".  Options that shape the workspace must be set before the context is first used
  * (FailedPrecondition afterwards).  The arithmetic flavour (PIRGPU_NTT_MODE) is fixed at pirgpu_create.
  * Environment variables are honoured only when PIRGPU_ALLOW_ENV=1 is set too (tests, A/B scripts): by default a
- * context's behaviour depends on its parameters and pirgpu_set_option alone. */
+ * context's behaviour depends on its parameters and pirgpu_set_option alone.
+ * One switch of the batch pipeline is environment only and NOT an option: PIRGPU_SCAN_MFMA_PAIR (0 | 1 | 2, default 1;
+ * read when the context builds its workspace): two groups of 8 queries share one database read (5-digit moduli, d >= 2,
+ * one column chunk, plain contexts).  With the default, the first call that queues at least four groups (32 queries
+ * with 16 workers) allocates the second group's working buffers on both lanes -- per lane 8 x dim_sum ciphertexts of
+ * selection vectors, one packed-selector buffer and one set of row sums: 340 + 104 + 170 MB per lane, about 1.2 GB in
+ * all, at N = 4096, 2^20 x 288 B, d = 2 -- and keeps them for the context's life; they are not part of pirgpu_db_memory's
+ * count.  Because the environment is honoured only behind PIRGPU_ALLOW_ENV=1, a caller cannot turn pairing off through
+ * pirgpu_set_option; a deployment that must not spend that memory sets PIRGPU_ALLOW_ENV=1 PIRGPU_SCAN_MFMA_PAIR=0. */
 int pirgpu_set_option(pirgpu_ctx* ctx, const char* name, int64_t value);
 int pirgpu_get_option(pirgpu_ctx* ctx, const char* name, int64_t* value);
 /* Arithmetic flavour of the transform kernels of this context: 0 = 64-bit integer Shoup/Harvey butterflies (any

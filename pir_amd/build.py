@@ -8,7 +8,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpirgpu.so")
-SOURCES = ["kernels.hip", "scan_mfma.hip", "ctx.hip", "wire.cpp", "wire_codec.cpp",
+SOURCES = ["kernels.hip", "scan_mfma.hip", "scan_mfma_pair.hip", "ctx.hip", "wire.cpp", "wire_codec.cpp",
            "ntt_ring32k.hip",        # N = 32768: two-pass transforms, integer flavour only (built once)
            "ctmult.hip",             # ciphertext-multiplication mode: lift, tensor, scale, accumulate
            "ctmult_rowsum.hip",      # ... its deferred rounding: the tensor summed over the children of a row

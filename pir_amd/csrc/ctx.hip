@@ -136,6 +136,11 @@ struct BatchLane {
   uint32_t head_next = 0;
   uint64_t *res_a = nullptr, *res_b = nullptr, *prod = nullptr, *dig = nullptr;
   uint8_t* selp = nullptr;
+  // paired database pass (PIRGPU_SCAN_MFMA_PAIR): the SECOND group of a pair keeps its selection vectors
+  // ([query][dim_sum] ciphertexts: the lane's workers hold the first group's), its packed selectors and its row sums here
+  uint64_t* sv2 = nullptr;
+  uint8_t* selp2 = nullptr;
+  uint64_t* rows2 = nullptr;
   uint8_t* selp_runs = nullptr;      // contexts with tables: packed selectors of up to 8 runs of one group (one launch for all)
   hipEvent_t ev_scanned = nullptr;
   hipEvent_t ev_join = nullptr;      // pirgpu_join: everything queued on this lane so far
@@ -331,6 +336,8 @@ struct pirgpu_ctx {
   bool scan_f64_fold = false;               // the scan folds its digit diagonals in exact fp64 arithmetic (option
                                             // SCAN_F64_FOLD; every data modulus below 2^50)
   bool scan_f64_fold_batch = false;         // ... in the launches that serve a group of queries (option SCAN_F64_FOLD_BATCH)
+  uint32_t scan_pair = 1;                   // two groups per database read (scan_mfma_pair.hip): 0 off, 1 in calls that queue at
+                                            // least four groups, 2 whenever a call has two left (PIRGPU_SCAN_MFMA_PAIR)
   bool split_upper = false;                 // upper level as transform-to-scratch + elementwise MAC (N >= 16384 in the fp64
                                             // flavours, where the fused kernel spills; option SPLIT_UPPER overrides)
   uint64_t split_upper_words = 0;           // scratch budget per lane / worker (option SPLIT_UPPER_MB)
@@ -828,6 +835,16 @@ void resolve_options(pirgpu_ctx* c) {
   c->mfma_single = opt_u32(c, OPT_SCAN_MFMA_SINGLE, c->mg.nchunks == 1 ? 1 : 0) != 0;
   c->scan_f64_fold = opt_u32(c, OPT_SCAN_F64_FOLD, c->mg.L >= 6 ? 1 : 0) != 0;
   c->scan_f64_fold_batch = opt_u32(c, OPT_SCAN_F64_FOLD_BATCH, 1) != 0;
+  // Two groups per database read in the batch pipeline (scan_mfma_pair.hip).  Environment only, like PIRGPU_SCAN_MFMA_WGS
+  // (tests, A/B; read here, when the workspace is built): 0 off, 1 (the default) in calls that queue at least four groups,
+  // so that both lanes get a pair and shorter calls keep the finer pipeline, 2 whenever a call has two groups left.
+  // Kernel alone at cfg 3, one paired launch against two single ones: 0.72 of the time on 128 workgroups, 0.63 on 256.
+  // Headline, same library, 0 against 1, alternating runs after two of the same setting (spread 0.3 %): 5 530 / 5 548 /
+  // 5 577 / 5 574 / 5 575 / 5 574 against 5 797 / 5 822 / 5 814 / 5 830 queries/s (+4.4 %), replies unchanged; one
+  // synchronous wire caller 4 790 against 4 936 (profiles/scan_pair_ab.txt): on.
+  c->scan_pair = 1;
+  if (const char* v = pirgpu_env("PIRGPU_SCAN_MFMA_PAIR"))
+    if (*v) c->scan_pair = (uint32_t)std::min<long>(2, std::max<long>(0, strtol(v, nullptr, 10)));
   for (uint32_t j = 0; j < k; ++j) {
     c->scan_f64_fold = c->scan_f64_fold && (c->hp.mod[j].q >> 50) == 0;
     c->scan_f64_fold_batch = c->scan_f64_fold_batch && (c->hp.mod[j].q >> 50) == 0;
@@ -1387,6 +1404,45 @@ void scan_group_mfma(pirgpu_ctx* c, hipStream_t st, uint8_t*& selp, const MfmaPt
   }
   if (c->mg.nchunks > 1)
     HIP_TRY(launch_reduce_splits(st, c->dp, part, c->mg.nchunks, words, out_base, n, (uint64_t)c->mg.nchunks * words, words));
+}
+
+// The same pass for TWO groups on one lane (scan_mfma_pair.hip): both groups' column selectors are packed, then ONE launch
+// multiplies every database tile it reads with both.  Group h's row sums go to out[h], query-major.  One column chunk.
+static void scan_pair_mfma(pirgpu_ctx* c, BatchLane& ln, const MfmaPtrs (&col)[2], const uint32_t (&n)[2],
+                           uint64_t* const (&out)[2], bool sel_f64, bool share_chip) {
+  const uint32_t kN = c->k * c->N;
+  const uint64_t words = (uint64_t)c->scan_rows * c->ctw;
+  hipStream_t st = ln.stream;
+  ensure_packed(c);
+  if (!ln.selp) ln.selp = c->dalloc<uint8_t>(c->mg.sel_bytes);
+  uint8_t* const selp[2] = {ln.selp, ln.selp2};
+  ScanGroups grp{};
+  grp.n = 2;
+  for (uint32_t h = 0; h < 2; ++h) {
+    HIP_TRY(launch_sel_pack(st, c->dp, c->mg, col[h], n[h], selp[h], c->scan_cols, kN, sel_f64));
+    grp.sel[h] = selp[h];
+    grp.out[h] = out[h];
+    grp.nq[h] = (uint8_t)n[h];
+  }
+  const uint32_t wgs = share_chip && c->scan_wgs_batch ? c->scan_wgs_batch : 0;
+  const bool timed = c->prof && c->bscan_n < 64;
+  if (timed) {
+    while (c->bscan_ev.size() < 2 * (size_t)(c->bscan_n + 1)) {
+      hipEvent_t e;
+      HIP_TRY(hipEventCreate(&e));
+      c->bscan_ev.push_back(e);
+    }
+    HIP_TRY(hipEventRecord(c->bscan_ev[2 * c->bscan_n], st));
+  }
+  HIP_TRY(launch_scan_mfma_pair(st, c->dp, c->mg, c->d_dbp, grp, c->scan_rows, words, wgs,
+                                c->scan_f64_fold || c->scan_f64_fold_batch, 0, kN, words, kN));
+  ++c->options.counter(OPT_SCAN_LAUNCHES);
+  if (timed) {
+    HIP_TRY(hipEventRecord(c->bscan_ev[2 * c->bscan_n + 1], st));
+    ++c->bscan_n;
+    c->bscan_wgs = wgs;
+    c->bscan_nq = n[0] + n[1];
+  }
 }
 
 // Base case of PIRDatabase::multiply (reference database.cpp:185-194,238-247): one fused
@@ -3730,6 +3786,15 @@ static void ensure_lanes(pirgpu_ctx* c, bool with_expansion_buffers) {
   }
 }
 
+// The second group of a paired database pass: its selection vectors, packed column selectors and row sums, lane-owned
+// (the lane's workers hold the first group's; stream order on the lane covers the reuse from pair to pair and call to call)
+static void ensure_pair_buffers(pirgpu_ctx* c, BatchLane& ln, bool expands) {
+  if (expands && !ln.sv2) ln.sv2 = c->dalloc<uint64_t>((size_t)kMaxMfmaQueries * c->dim_sum * c->ctw);
+  if (ln.selp2) return;
+  ln.selp2 = c->dalloc<uint8_t>(c->mg.sel_bytes);
+  ln.rows2 = c->dalloc<uint64_t>((size_t)kMaxMfmaQueries * c->lvl_cts[c->d - 1] * c->ctw);
+}
+
 // Batched oblivious expansion of the staged queries first .. first+B-1 on lane `ln`, B queries interleaved
 // (ciphertext index = node * B + query), into the members' own selection vectors (NTT form).
 static void ensure_head_slot(pirgpu_ctx* c, HeadSlot& hs) {
@@ -3929,11 +3994,84 @@ static void batch_run_mfma(pirgpu_ctx* c, uint32_t count, const uint64_t* ext_sv
   c->bs().host_reply_done = host_dl;
   c->bs().dl_end.clear();
   c->bs().dl_next = 0;
+  // the per-group download of finished replies (pirgpu_batch_set_host_replies), consecutive queries
+  auto queue_download = [&](BatchLane& ln, uint32_t first, uint32_t B) {
+    BatchSet& b = c->bs();
+    const size_t gi = b.dl_end.size();
+    while (gi >= b.dl_events.size()) {
+      hipEvent_t e;
+      HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      b.dl_events.push_back(e);
+      HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      b.rd_events.push_back(e);
+    }
+    if (!c->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+    HIP_TRY(hipEventRecord(b.rd_events[gi], ln.stream));
+    HIP_TRY(hipStreamWaitEvent(c->copy_stream, b.rd_events[gi], 0));
+    HIP_TRY(hipMemcpyAsync(b.host_reply + (size_t)first * rwords, reply_base(c) + (size_t)first * rwords,
+                           (size_t)B * rwords * 8, hipMemcpyDeviceToHost, c->copy_stream));
+    HIP_TRY(hipEventRecord(b.dl_events[gi], c->copy_stream));
+    b.dl_end.push_back(first + B);
+  };
+  // Two groups per database read (PIRGPU_SCAN_MFMA_PAIR, scan_mfma_pair.hip): a lane expands group a (into its workers'
+  // selection vectors) and group b (into its own second buffer), packs both, scans the database ONCE for both, then
+  // finishes a and b one after the other.  The plain case only: the context's own expansion of one database in one
+  // column chunk (or caller-owned selection vectors), re-encoding upper levels at every prime, replies written in place.
+  // Everything else -- an odd last group, short calls under value 1, tables, packed / slot-sharded input, result_primes,
+  // wide items, ciphertext-multiplication mode -- keeps one pass per group.
+  const bool may_pair = c->scan_pair && !pk && !qtab && c->d >= 2 && !c->ctm && !c->rp && c->planes <= 1 &&
+                        G == (uint32_t)kMaxMfmaQueries && scan_mfma_pair_supported(c->mg) &&
+                        (c->scan_pair >= 2 || (n_groups >= 4 && nl >= 2));
+  auto run_pair = [&](uint32_t first_a, uint32_t Ba, uint32_t first_b, uint32_t Bb) {
+    const uint32_t li = (uint32_t)(c->groups_run++ % nl);
+    BatchLane& ln = c->lanes[li];
+    ensure_pair_buffers(c, ln, !ext_sv);
+    const bool sel_f64 = !ext_sv && c->sel_f64;   // a lane's own selectors: exact doubles instead of u64
+    Worker* members[kMaxMfmaQueries];
+    for (uint32_t q = 0; q < Ba; ++q) {
+      members[q] = &c->workers[(li * G + q) % W];
+      HIP_TRY(hipStreamWaitEvent(ln.stream, members[q]->ev_done, 0));  // whoever used its buffers last is done
+    }
+    if (!ext_sv) {
+      expand_group_on_lane(c, ln, members, Ba, first_a, sel_f64);
+      expand_group_on_lane(c, ln, members, Bb, first_b, sel_f64, ln.sv2);
+    }
+    const uint32_t firsts[2] = {first_a, first_b}, n[2] = {Ba, Bb};
+    uint64_t* const rows_out[2] = {ln.lvl[c->d - 1], ln.rows2};
+    MfmaPtrs sel[2] = {}, col[2] = {};
+    for (uint32_t h = 0; h < 2; ++h)
+      for (uint32_t q = 0; q < n[h]; ++q) {
+        sel[h].p[q] = ext_sv ? ext_sv + (size_t)(firsts[h] + q) * svwords : (h ? ln.sv2 + (size_t)q * svwords : members[q]->sv_ntt);
+        col[h].p[q] = (const uint64_t*)sel[h].p[q] + (size_t)c->sv_off[c->d - 1] * c->ctw;
+      }
+    scan_pair_mfma(c, ln, col, n, rows_out, sel_f64, share_chip);
+    for (uint32_t h = 0; h < 2; ++h) {
+      uint64_t* lvl_ptrs[PIRGPU_MAX_DIMS];
+      for (uint32_t l = 0; l < c->d; ++l) lvl_ptrs[l] = ln.lvl[l];
+      lvl_ptrs[c->d - 1] = rows_out[h];
+      lvl_ptrs[0] = reply_base(c) + (size_t)firsts[h] * rwords;   // d >= 2: level 0 is the replies, written in place
+      Stage sg{ln.stream, lvl_ptrs, ln.pt_buf, n[h], sel[h], false, &ln.up_scratch, &ln.up_scratch_words};
+      sg.sel_f64 = sel_f64;
+      for (uint32_t q = 0; q < n[h]; ++q)
+        sg.ksets[q] = firsts[h] + q < c->bs().batch_keysets.size() ? c->bs().batch_keysets[firsts[h] + q] : 0;
+      post_scan_stage(c, sg, nullptr);
+      if (host_dl) queue_download(ln, firsts[h], n[h]);
+    }
+    for (uint32_t q = 0; q < Ba; ++q) {
+      HIP_TRY(hipEventRecord(members[q]->ev_done, ln.stream));
+      members[q]->reply_valid = false;
+    }
+  };
   for (uint32_t rank0 = 0; rank0 < count; rank0 += span) {
     const uint32_t step = pk ? (uint32_t)kMaxMfmaQueries : G;
     const uint32_t in_span = std::min<uint32_t>(span, count - rank0);
     for (uint32_t j0 = 0; j0 < in_span; j0 += step) {
       const uint32_t B = std::min<uint32_t>(step, in_span - j0);
+      if (may_pair && j0 + step < in_span) {   // a full group and whatever follows it
+        run_pair(rank0 + j0, B, rank0 + j0 + step, std::min<uint32_t>(step, in_span - j0 - step));
+        j0 += step;
+        continue;
+      }
       if (B > W) throw Fail{PIRGPU_FAILED_PRECONDITION, "packed groups need min(queries per rank, 8) workers (pirgpu_set_concurrency)"};
       const uint32_t li = (uint32_t)(c->groups_run++ % nl);
       BatchLane& ln = c->lanes[li];
@@ -3996,19 +4134,21 @@ static void batch_run_mfma(pirgpu_ctx* c, uint32_t count, const uint64_t* ext_sv
         // the group's replies start their way to the host while the next groups are computed -- on the context's COPY
         // stream, behind an event of the lane: the lane itself goes straight on to its next group (round 3 queued the
         // copy on the lane, which then idled for 8 MB of PCIe per group: 5-6 % of a lane's time at cfg 3)
-        BatchSet& b = c->bs();
-        const size_t gi = b.dl_end.size();
-        while (gi >= b.dl_events.size()) {
-          hipEvent_t e;
-          HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-          b.dl_events.push_back(e);
-          HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-          b.rd_events.push_back(e);
-        }
-        if (!c->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-        HIP_TRY(hipEventRecord(b.rd_events[gi], ln.stream));
-        HIP_TRY(hipStreamWaitEvent(c->copy_stream, b.rd_events[gi], 0));
-        if (order) {
+        if (!order) {
+          queue_download(ln, first, B);
+        } else {
+          BatchSet& b = c->bs();
+          const size_t gi = b.dl_end.size();
+          while (gi >= b.dl_events.size()) {
+            hipEvent_t e;
+            HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            b.dl_events.push_back(e);
+            HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            b.rd_events.push_back(e);
+          }
+          if (!c->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+          HIP_TRY(hipEventRecord(b.rd_events[gi], ln.stream));
+          HIP_TRY(hipStreamWaitEvent(c->copy_stream, b.rd_events[gi], 0));
           // a permuted group's replies are scattered over the buffer: one copy each, and the group reports how many
           // LEADING queries of the batch are complete with it (the copy stream runs the groups' copies in order)
           for (uint32_t q = 0; q < B; ++q) {
@@ -4017,12 +4157,9 @@ static void batch_run_mfma(pirgpu_ctx* c, uint32_t count, const uint64_t* ext_sv
             done[oq(first + q)] = 1;
           }
           while (lead < count && done[lead]) ++lead;
-        } else {
-          HIP_TRY(hipMemcpyAsync(b.host_reply + (size_t)first * rwords, reply_base(c) + (size_t)first * rwords,
-                                 (size_t)B * rwords * 8, hipMemcpyDeviceToHost, c->copy_stream));
+          HIP_TRY(hipEventRecord(b.dl_events[gi], c->copy_stream));
+          b.dl_end.push_back(lead);
         }
-        HIP_TRY(hipEventRecord(b.dl_events[gi], c->copy_stream));
-        b.dl_end.push_back(order ? lead : first + B);
       }
       for (uint32_t q = 0; q < B; ++q) {
         HIP_TRY(hipEventRecord(members[q]->ev_done, ln.stream));

@@ -240,6 +240,15 @@ hipError_t launch_scan_mfma_groups(hipStream_t st, const DevParams* P, const Mfm
                                    const ScanGroups& grp, uint32_t rows, uint64_t chunk_stride, uint32_t wgs, bool f64_fold,
                                    uint32_t slot0, uint32_t nslots, uint64_t out_qstride, uint32_t out_rstride,
                                    bool blk_major = false);   // blk_major: units ordered (slot block, group) instead of (group, slot block)
+// TWO groups per database read (scan_mfma_pair.hip): grp holds exactly two groups, which share every tile a unit loads,
+// the second one's selectors in LDS.  Same arguments; scan_mfma_pair_supported: the geometries it is built for (L = 5,
+// 8 waves, one chunk) -- and only the whole ring, group-major (slot0 = 0, out_rstride = nslots, blk_major = false),
+// grp.n = 2.  Anything else is hipErrorInvalidValue: the caller launches single passes.
+bool scan_mfma_pair_supported(const MfmaGeom& gm);
+hipError_t launch_scan_mfma_pair(hipStream_t st, const DevParams* P, const MfmaGeom& gm, const uint8_t* dbp,
+                                 const ScanGroups& grp, uint32_t rows, uint64_t chunk_stride, uint32_t wgs, bool f64_fold,
+                                 uint32_t slot0, uint32_t nslots, uint64_t out_qstride, uint32_t out_rstride,
+                                 bool blk_major = false);
 // several groups over the whole ring, each over ITS OWN database grp.db[g] (the runs of equal tables inside one batch
 // group); scan_mfma_runs_supported: the geometries the launch is built for (the 8-wave kernels) -- others launch per run
 bool scan_mfma_runs_supported(const MfmaGeom& gm);

@@ -3,6 +3,8 @@
 // compiler sees are the ones it saw before this file existed), or grp.db[g] (scan_mfma_runs_kernel: a table per group,
 // read from the by-value kernel argument with a workgroup-uniform index -- scalar loads, never a divergent one; past the
 // last unit the next unit names no group, so the current one is named and nothing is loaded from it).
+// scan_mfma_pair.hip holds a hand copy of the loaders, the fold and the result staging below (its kernel serves two groups
+// per unit and must not change what the kernels here compile to): a fix to any of them belongs in both places.
   constexpr uint32_t TB = tile_bytes(L, TOP4);
   constexpr int LF = TOP4 ? L - 1 : L;   // digits stored as full bytes
   constexpr int NS = 2 * L - 1;        // digit diagonals
