@@ -199,6 +199,7 @@ def test_every_option_by_kind(monkeypatch):
     assert len(set(EARLY_OPTIONS) | set(LIVE_OPTIONS) | set(COUNTER_OPTIONS)) == 42
     for name in EARLY_OPTIONS + list(LIVE_OPTIONS) + COUNTER_OPTIONS:
         monkeypatch.delenv("PIRGPU_" + name, raising=False)
+    monkeypatch.delenv("PIRGPU_SCAN_MFMA_PAIR", raising=False)   # (environment only: its default pairs long calls alone)
     s = setup_with_dims(0, 2048, [17, 17], N=4096, plain_bits=24)
     db, srv = make(s)
     for name in EARLY_OPTIONS + list(LIVE_OPTIONS):
@@ -220,16 +221,27 @@ def test_every_option_by_kind(monkeypatch):
         assert db.get_option(name) == 7, name
         db.set_option(name, -3)
         assert db.get_option(name) == 0, name
-    # the replies are what they were: a single query, and a group through the batch pipeline (whose database pass now
-    # runs on 96 workgroups)
+    # the replies are what they were: a single query, and a group through the batch pipeline (one group: it has the whole
+    # chip, whatever SCAN_MFMA_WGS_BATCH says)
     check_queries(s, srv, [3, n - 1])
     idx = [1, n // 3, n - 2]
     queries = np.stack([s.client.create_query_for(s.params, i) for i in idx])
     got = srv.process_batch(queries, n_workers=4)
+    expected = []
     for i in range(len(idx)):
         rc, exp = s.orc.process_query(s.db_ntt, s.params.dimensions, queries[i], s.galois_keys)
         assert rc == 0 and np.array_equal(got[i], exp), idx[i]
+        expected.append(exp)
     assert db.get_option("SCAN_LAUNCHES") >= 1                     # counting went on from the 0 set above
+    # ... and a batch that shares the chip -- two groups on two lanes (too short a call to pair them): its database passes
+    # run on the 96 workgroups set above
+    srv.set_profiling(True)
+    before = db.get_option("SCAN_LAUNCHES")
+    got = srv.process_batch(np.stack([queries[i % 3] for i in range(9)]), n_workers=16)
+    t = srv.batch_scan_timings()
+    assert db.get_option("SCAN_LAUNCHES") - before == 2 and t["launches"] == 2 and t["workgroups"] == 96, t
+    for i in range(9):
+        assert np.array_equal(got[i], expected[i % 3]), i
     db.close()
 
 

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import pir_amd
+import scan_fold_model as M
 from gpu_helpers import device_to_seal_order, to_product_params
 from oracle.client import Client
 from test_gpu_mfma_scan import setup_with_dims
@@ -133,9 +134,10 @@ def test_two_clients_mixed_inside_each_group(monkeypatch):
 # ---- structured extremes (the operands of tests/test_gpu_scan_worst_case.py): group 0's column selectors all at the
 # residue whose digits are all +127 / top +7, group 1's all at the -128 / -8 end -- a B tile or an accumulator that leaks
 # from one group into the other cannot cancel
-@functools.lru_cache(maxsize=1)
-def extremes():
-    case = case_of(36, 5, True, True, 192)                      # 9 rows x 192 columns: 3 k-steps, one chunk
+@functools.lru_cache(maxsize=None)
+def extremes_of(bits, low_end, top4):
+    """The operands below for two data primes of `bits` bits at either end of the size, either top-digit form."""
+    case = case_of(bits, 5, low_end, top4, 192)                 # 9 rows x 192 columns: 3 k-steps, one chunk
     k = 2
     rng = np.random.default_rng(2024)
     members = {0: 3, 1: 0}                                      # group -> member: (+127, top max), (-128, top min)
@@ -155,19 +157,23 @@ def extremes():
     return case, sv, expected, order
 
 
+def extremes():
+    return extremes_of(36, True, True)
+
+
 def run_selectors(srv, sv_dev, count):
     srv.stage_batch(np.zeros((count, 1, 2, 2, N), dtype=np.uint64))     # sizes the reply buffers
     srv.batch_run_selectors(sv_dev.data_ptr(), count)
 
 
-@pytest.mark.parametrize("fold", [1, 0], ids=["fp64 fold", "integer fold"])
-def test_groups_at_opposite_extremes(fold, monkeypatch):
+def opposite_extremes(operands, top4, fold):
+    """One pair per orientation, group 0 at one end of the digits and group 1 at the other."""
     import torch
-    monkeypatch.setenv(PAIR, "2")
-    case, sv, expected, order = extremes()
-    db, srv = context(case, scan_mfma_top4=1, scan_f64_fold_batch=fold)
-    info = srv.scan_info()
-    assert info["mfma"] and info["chunks"] == 1 and info["ksteps"] == 3 and info["top_digit_nibble"], info
+    case, sv, expected, order = operands
+    db, srv = context(case, scan_mfma_top4=1 if top4 else 0, scan_f64_fold_batch=fold)
+    info, arith = srv.scan_info(), srv.arith_info()
+    assert info["mfma"] and info["digits"] == 5 and info["chunks"] == 1 and info["ksteps"] == 3, info
+    assert info["top_digit_nibble"] == top4 and arith["scan_f64_fold_batch"] == bool(fold), (info, arith)
     srv.set_concurrency(16)
     for flip in (False, True):                                  # either group at either end
         o = order[8:] + order[:8] if flip else order
@@ -179,6 +185,26 @@ def test_groups_at_opposite_extremes(fold, monkeypatch):
         for i, v in enumerate(o):
             assert np.array_equal(got[i], expected[v]), (flip, i)
     db.close()
+
+
+@pytest.mark.parametrize("fold", [1, 0], ids=["fp64 fold", "integer fold"])
+def test_groups_at_opposite_extremes(fold, monkeypatch):
+    monkeypatch.setenv(PAIR, "2")
+    opposite_extremes(extremes(), True, fold)
+
+
+@pytest.mark.parametrize("fold", [1, 0], ids=["fp64 fold", "integer fold"])
+@pytest.mark.parametrize("low_end", [True, False], ids=["smallest primes", "largest primes"])
+def test_groups_at_opposite_extremes_of_the_byte_form(low_end, fold, monkeypatch):
+    """39-bit primes: the top digit is a full byte because it has to be (it reaches -64 / +63 where the 36-bit primes'
+    stays inside a nibble), so the TOP4 = false loaders, the LDS round trip of group 1's top-digit tile and both folds
+    meet top digits at both ends of the centring -- one group at each end, either way round."""
+    monkeypatch.setenv(PAIR, "2")
+    operands = extremes_of(39, low_end, False)
+    case = operands[0]
+    tops = [M.to_digits(case.members[m] % q, q, 5, False)[0][4] for m in (3, 0) for q in case.qs]
+    assert min(tops) <= -31 and max(tops) >= 31, tops          # four times what a nibble holds
+    opposite_extremes(operands, False, fold)
 
 
 def assert_one_lane(srv):
