@@ -305,6 +305,16 @@ int pirgpu_keyset_release(pirgpu_ctx* ctx, uint32_t slot);
 int pirgpu_keyset_set_key(pirgpu_ctx* ctx, uint32_t slot, uint32_t galois_elt, const uint64_t* key);
 /* n keys of one set in one call (one wait for all uploads instead of one per key). */
 int pirgpu_keyset_set_keys(pirgpu_ctx* ctx, uint32_t slot, uint32_t n, const uint32_t* galois_elts, const uint64_t* const* keys);
+/* pirgpu_keyset_set_keys for seed-compressed keys: key i is given as its c0 halves c0[i] = [k][k+1][N] words
+ * (any alignment -- they may point straight into request bytes) and seeds[i] = k x 64 bytes; the installed key is
+ * exactly the one pirgpu_keyset_set_keys installs for key[j][0] = c0[i][j], key[j][1] = sample_poly_uniform(seed j)
+ * (SEAL's BlakePRNG, re-sampled by a kernel on the device: DESIGN.md section 6.7). */
+int pirgpu_keyset_set_keys_seeded(pirgpu_ctx* ctx, uint32_t slot, uint32_t n, const uint32_t* galois_elts,
+                                  const void* const* c0, const uint8_t* const* seeds);
+/* Test hook: n seeds -> out[n][k+1][N] over the context's key-level moduli (the kernel of the call above). */
+int pirgpu_expand_seeds(pirgpu_ctx* ctx, const uint8_t* seeds, uint32_t n, uint64_t* out);
+/* [0] objects expanded on the device so far, [1] draws those expansions rejected. */
+int pirgpu_keyset_seed_stats(pirgpu_ctx* ctx, uint64_t stats[2]);
 int pirgpu_query_use_keyset(pirgpu_ctx* ctx, uint32_t slot);
 int pirgpu_batch_set_keysets(pirgpu_ctx* ctx, const uint32_t* slots, uint32_t count);
 int pirgpu_keyset_stats(pirgpu_ctx* ctx, uint64_t stats[4]);

@@ -150,6 +150,10 @@ SIGNATURES = {
     "pirgpu_keyset_release": (C.c_int, [C.c_void_p, C.c_uint32]),
     "pirgpu_keyset_set_key": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, u64p]),
     "pirgpu_keyset_set_keys": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_void_p)]),
+    "pirgpu_keyset_set_keys_seeded": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
+                                                C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "pirgpu_expand_seeds": (C.c_int, [C.c_void_p, u8p, C.c_uint32, u64p]),
+    "pirgpu_keyset_seed_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "pirgpu_query_use_keyset": (C.c_int, [C.c_void_p, C.c_uint32]),
     "pirgpu_batch_set_keysets": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32]),
     "pirgpu_batch_stage_async": (C.c_int, [C.c_void_p, u64p, C.c_uint32, C.c_uint32]),

@@ -291,6 +291,19 @@ struct pirgpu_ctx {
   uint64_t keyset_clock = 0, key_uploads = 0, keyset_evictions = 0;
   std::vector<uint64_t*> key_pool;          // device key buffers of emptied sets, reused by the next upload (no hipMalloc)
   uint64_t* d_key_stage = nullptr;          // one key in SEAL order on its way to device order (allocated once)
+  // seed-compressed keys (pirgpu_keyset_set_keys_seeded): the stage of a GROUP of keys (the
+  // expansion kernel fills the c1 halves of a whole group in one launch), the seeds and the kernel's counters on the
+  // device; two keys' worth of c0 halves plus the seeds and a copy of the counters in pinned host memory
+  uint64_t* d_seed_stage = nullptr;
+  size_t seed_stage_keys = 0;
+  uint8_t* d_seeds = nullptr;
+  size_t d_seeds_cap = 0;
+  uint64_t* d_seed_stats = nullptr;         // [0] draws rejected, [1] an object overran its refill bound
+  uint64_t* h_seed_pin = nullptr;           // [2][k][k+1][N] words, then kSeedStatWords words of counters
+  uint8_t* h_seeds = nullptr;               // pinned, h_seeds_cap bytes
+  size_t h_seeds_cap = 0;
+  hipEvent_t ev_seed_pin[2] = {nullptr, nullptr};   // "the copy out of this half of h_seed_pin is done"
+  uint64_t seed_objects = 0;                // objects expanded on the device so far
   std::map<uint32_t, uint64_t*> xpow;       // shift -> NTT_j(x^(-shift)), [k][N] doubles (NTT-domain last expansion level)
   std::map<uint32_t, uint16_t*> gperm;      // Galois element g -> [2][N] u16: sigma_g / sigma_(g^-1) on NTT positions (galois_perm_table)
 
@@ -2100,6 +2113,11 @@ void pirgpu_destroy(pirgpu_ctx* c) {
   for (KeySet& ks : c->keysets)
     for (auto& kv : ks.keys) (void)hipFree(kv.second);
   for (uint64_t* p : c->key_pool) (void)hipFree(p);
+  if (c->d_seeds) (void)hipFree(c->d_seeds);
+  if (c->h_seed_pin) (void)hipHostFree(c->h_seed_pin);
+  if (c->h_seeds) (void)hipHostFree(c->h_seeds);
+  for (hipEvent_t e : c->ev_seed_pin)
+    if (e) (void)hipEventDestroy(e);
   for (void* p : c->allocs) (void)hipFree(p);
   for (BatchSet& b : c->sets) {
     if (b.h_query) (void)hipHostFree(b.h_query);
@@ -2921,12 +2939,8 @@ int pirgpu_db_update_plaintexts(pirgpu_ctx* c, uint64_t n, const uint64_t* pt_in
 // ======================================================================================================================
 // [6] C ABI: Galois keys and per-client key sets
 // ======================================================================================================================
-// Uploads one Galois key into a key set slot (SEAL's NTT order at the boundary, device order in HBM).  A new client's
-// first request pays for 12 of these (N = 4096): the staging buffer is allocated once per context and the key buffers
-// of emptied sets are recycled, so the steady state of a server whose clients come and go allocates nothing.
-static void upload_key(pirgpu_ctx* c, uint32_t slot, uint32_t g, const uint64_t* key, bool wait = true) {
-  if (slot >= c->keysets.size()) throw Fail{PIRGPU_INVALID_ARGUMENT, "key set slot out of range"};
-  if (!key || !(g & 1) || g >= 2 * c->N) throw Fail{PIRGPU_INVALID_ARGUMENT, "invalid Galois element"};
+// The device buffer of key g in a slot: the one it has, a recycled one or a new one.
+static uint64_t* key_buffer(pirgpu_ctx* c, uint32_t slot, uint32_t g) {
   const size_t words = (size_t)c->k * 2 * (c->k + 1) * c->N;
   auto& keys = c->keysets[slot].keys;
   uint64_t* dev = nullptr;
@@ -2946,6 +2960,17 @@ static void upload_key(pirgpu_ctx* c, uint32_t slot, uint32_t g, const uint64_t*
     }
     keys[g] = dev;
   }
+  return dev;
+}
+
+// Uploads one Galois key into a key set slot (SEAL's NTT order at the boundary, device order in HBM).  A new client's
+// first request pays for 12 of these (N = 4096): the staging buffer is allocated once per context and the key buffers
+// of emptied sets are recycled, so the steady state of a server whose clients come and go allocates nothing.
+static void upload_key(pirgpu_ctx* c, uint32_t slot, uint32_t g, const uint64_t* key, bool wait = true) {
+  if (slot >= c->keysets.size()) throw Fail{PIRGPU_INVALID_ARGUMENT, "key set slot out of range"};
+  if (!key || !(g & 1) || g >= 2 * c->N) throw Fail{PIRGPU_INVALID_ARGUMENT, "invalid Galois element"};
+  const size_t words = (size_t)c->k * 2 * (c->k + 1) * c->N;
+  uint64_t* dev = key_buffer(c, slot, g);
   if (!c->d_key_stage) c->d_key_stage = c->dalloc<uint64_t>(words);
   // stream order on the main stream covers the reuse of the staging buffer by the next key
   HIP_TRY(hipMemcpyAsync(c->d_key_stage, key, words * 8, hipMemcpyHostToDevice, c->stream));
@@ -3122,6 +3147,145 @@ int pirgpu_keyset_set_keys(pirgpu_ctx* c, uint32_t slot, uint32_t n, const uint3
     // first request); the staging buffer's reuse from key to key is covered by stream order
     for (uint32_t i = 0; i < n; ++i) upload_key(c, index, galois_elts[i], keys[i], false);
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return PIRGPU_OK;
+  });
+}
+
+// ---- seed-compressed keys
+constexpr size_t kSeedBytes = 64;
+constexpr size_t kSeedStatWords = 2;
+constexpr size_t kSeedStageBytes = 128u << 20;   // the stage holds as many keys as fit in this, at least 1, at most 16
+
+static SeedExpandArgs seed_expand_args(const pirgpu_ctx* c) {
+  SeedExpandArgs a{};
+  a.n_mod = c->k + 1;
+  a.N = c->N;
+  const uint64_t max_random = 0x7FFFFFFFFFFFFFFFull;
+  for (uint32_t j = 0; j < a.n_mod; ++j) {
+    a.mod[j] = c->hp.mod[j];
+    a.max_multiple[j] = max_random - max_random % a.mod[j].q - 1;
+  }
+  // a prime below 2^61 accepts more than 7 draws of 8: four times the stream without rejections is never reached
+  a.max_refills = 4 * ((uint64_t)a.n_mod * c->N / 512 + 1) + kSeedThreads / 64;
+  return a;
+}
+
+static void ensure_seed_buffers(pirgpu_ctx* c, size_t n_seeds) {
+  const size_t km = c->k + 1, key_words = (size_t)c->k * 2 * km * c->N;
+  if (!c->d_seed_stats) {
+    c->d_seed_stats = c->dalloc<uint64_t>(kSeedStatWords);
+    HIP_TRY(hipMemsetAsync(c->d_seed_stats, 0, kSeedStatWords * 8, c->stream));
+  }
+  if (!c->d_seed_stage) {
+    c->seed_stage_keys = std::min<size_t>(16, std::max<size_t>(1, kSeedStageBytes / (key_words * 8)));
+    c->d_seed_stage = c->dalloc<uint64_t>(c->seed_stage_keys * key_words);
+  }
+  if (!c->h_seed_pin)
+    HIP_TRY(hipHostMalloc((void**)&c->h_seed_pin, (key_words + kSeedStatWords) * 8, hipHostMallocDefault));   // 2 c0 halves = 1 key
+  for (hipEvent_t& e : c->ev_seed_pin)
+    if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  const size_t bytes = std::max<size_t>(n_seeds, 64) * kSeedBytes;
+  if (bytes > c->d_seeds_cap) {     // nothing of an earlier call is in flight: every call ends with a wait
+    if (c->d_seeds) HIP_TRY(hipFree(c->d_seeds));
+    c->d_seeds = nullptr;
+    c->d_seeds_cap = 0;
+    HIP_TRY(hipMalloc((void**)&c->d_seeds, bytes));
+    c->d_seeds_cap = bytes;
+  }
+  if (bytes > c->h_seeds_cap) {
+    if (c->h_seeds) HIP_TRY(hipHostFree(c->h_seeds));
+    c->h_seeds = nullptr;
+    c->h_seeds_cap = 0;
+    HIP_TRY(hipHostMalloc((void**)&c->h_seeds, bytes, hipHostMallocDefault));
+    c->h_seeds_cap = bytes;
+  }
+}
+
+// the kernel's counters after the stream has been waited for: an overrun is an error (and is cleared)
+static void check_seed_overrun(pirgpu_ctx* c) {
+  const uint64_t* st = c->h_seed_pin + (size_t)c->k * 2 * (c->k + 1) * c->N;
+  if (st[1]) {
+    HIP_TRY(hipMemsetAsync(c->d_seed_stats + 1, 0, 8, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    throw Fail{PIRGPU_INTERNAL, "seed expansion ran past its stream bound"};
+  }
+}
+
+int pirgpu_keyset_set_keys_seeded(pirgpu_ctx* c, uint32_t slot, uint32_t n, const uint32_t* galois_elts,
+                                  const void* const* c0, const uint8_t* const* seeds) {
+  return guarded(c, [&]() -> int {
+    if (n && (!galois_elts || !c0 || !seeds)) return fail(c, PIRGPU_INVALID_ARGUMENT, "null buffer");
+    const uint32_t index = resolve_slot(c, slot);
+    for (uint32_t i = 0; i < n; ++i)
+      if (!c0[i] || !seeds[i] || !(galois_elts[i] & 1) || galois_elts[i] >= 2 * c->N)
+        return fail(c, PIRGPU_INVALID_ARGUMENT, "invalid Galois element");
+    if (!n) return PIRGPU_OK;
+    const uint32_t k = c->k, km = k + 1;
+    const size_t poly_words = (size_t)km * c->N, half_words = (size_t)k * poly_words, key_words = 2 * half_words;
+    ensure_seed_buffers(c, (size_t)n * k);
+    const SeedExpandArgs args = seed_expand_args(c);
+    for (uint32_t i = 0; i < n; ++i) memcpy(c->h_seeds + (size_t)i * k * kSeedBytes, seeds[i], k * kSeedBytes);
+    HIP_TRY(hipMemcpyAsync(c->d_seeds, c->h_seeds, (size_t)n * k * kSeedBytes, hipMemcpyHostToDevice, c->stream));
+    bool pin_used[2] = {false, false};
+    for (uint32_t g0 = 0; g0 < n; g0 += (uint32_t)c->seed_stage_keys) {
+      const uint32_t ng = std::min<uint32_t>((uint32_t)c->seed_stage_keys, n - g0);
+      // component 1 of every object of the group: object (key i, digit j) -> stage[i][j][1]; the stage's reuse from
+      // group to group is covered by stream order
+      HIP_TRY(launch_seed_expand(c->stream, args, c->d_seeds + (size_t)g0 * k * kSeedBytes, ng * k,
+                                 c->d_seed_stage + poly_words, 2 * poly_words, c->d_seed_stats));
+      for (uint32_t i = g0; i < g0 + ng; ++i) {
+        const uint32_t h = i & 1;
+        uint64_t* pin = c->h_seed_pin + h * half_words;
+        if (pin_used[h]) HIP_TRY(hipEventSynchronize(c->ev_seed_pin[h]));   // the copy of key i - 2 has left this half
+        memcpy(pin, c0[i], half_words * 8);
+        uint64_t* stage = c->d_seed_stage + (size_t)(i - g0) * key_words;
+        // c0 [k][km][N] -> component 0 of [k][2][km][N]
+        HIP_TRY(hipMemcpy2DAsync(stage, 2 * poly_words * 8, pin, poly_words * 8, poly_words * 8, k, hipMemcpyHostToDevice,
+                                 c->stream));
+        HIP_TRY(hipEventRecord(c->ev_seed_pin[h], c->stream));
+        pin_used[h] = true;
+        uint64_t* dev = key_buffer(c, index, galois_elts[i]);
+        HIP_TRY(launch_ntt_reorder(c->stream, c->N, stage, dev, (uint64_t)k * 2 * km, true, c->mode != kNttInt));
+        ++c->key_uploads;
+      }
+    }
+    c->seed_objects += (uint64_t)n * k;
+    HIP_TRY(hipMemcpyAsync(c->h_seed_pin + key_words, c->d_seed_stats, kSeedStatWords * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));   // the one wait of the call
+    check_seed_overrun(c);
+    return PIRGPU_OK;
+  });
+}
+
+int pirgpu_expand_seeds(pirgpu_ctx* c, const uint8_t* seeds, uint32_t n, uint64_t* out) {
+  return guarded(c, [&]() -> int {
+    if (n && (!seeds || !out)) return fail(c, PIRGPU_INVALID_ARGUMENT, "null buffer");
+    if (!n) return PIRGPU_OK;
+    const size_t poly_words = (size_t)(c->k + 1) * c->N;
+    ensure_seed_buffers(c, n);
+    DevScratch buf;
+    uint64_t* d_out = buf.get<uint64_t>((size_t)n * poly_words * 8);
+    HIP_TRY(hipMemcpyAsync(c->d_seeds, seeds, (size_t)n * kSeedBytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(launch_seed_expand(c->stream, seed_expand_args(c), c->d_seeds, n, d_out, poly_words, c->d_seed_stats));
+    c->seed_objects += n;
+    HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)n * poly_words * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_seed_pin + (size_t)c->k * 2 * poly_words, c->d_seed_stats, kSeedStatWords * 8,
+                           hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    check_seed_overrun(c);
+    return PIRGPU_OK;
+  });
+}
+
+int pirgpu_keyset_seed_stats(pirgpu_ctx* c, uint64_t stats[2]) {
+  return guarded(c, [&]() -> int {
+    if (!stats) return fail(c, PIRGPU_INVALID_ARGUMENT, "null buffer");
+    stats[0] = c->seed_objects;
+    stats[1] = 0;
+    if (c->d_seed_stats) {
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      HIP_TRY(hipMemcpy(&stats[1], c->d_seed_stats, 8, hipMemcpyDeviceToHost));
+    }
     return PIRGPU_OK;
   });
 }

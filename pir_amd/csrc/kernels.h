@@ -260,4 +260,17 @@ hipError_t launch_scan_mfma_runs(hipStream_t st, const DevParams* P, const MfmaG
 hipError_t launch_slots_assemble(hipStream_t st, const uint64_t* src, uint64_t* dst, const SliceMap& map, uint32_t RC,
                                  uint32_t kN, uint32_t nq, uint64_t dst_qstride, uint32_t nq_total, uint32_t q0);
 
+// Seed expansion (seed_expand.hip): object o of n_obj re-samples SEAL's sample_poly_uniform from
+// seeds[o][64] over mod[0 .. n_mod) into out + o * obj_stride, [n_mod][N] canonical residues; one workgroup of
+// kSeedThreads per object.  stats[0] += draws rejected, stats[1] = 1 if an object needed more than max_refills refills.
+constexpr uint32_t kSeedThreads = 512;
+struct SeedExpandArgs {                // by-value kernel argument
+  ModConst mod[kMaxMod];
+  uint64_t max_multiple[kMaxMod];      // (2^63 - 1) - ((2^63 - 1) mod q) - 1: candidates below it are accepted
+  uint64_t max_refills;                // bound on the stream an object may consume (a workgroup never spins)
+  uint32_t n_mod, N;
+};
+hipError_t launch_seed_expand(hipStream_t st, const SeedExpandArgs& args, const uint8_t* seeds, uint32_t n_obj, uint64_t* out,
+                              uint64_t obj_stride, uint64_t* stats);
+
 }  // namespace pirgpu

@@ -12,6 +12,7 @@
 // Every method is a thin call into libpirgpu (include/pirgpu.h); nothing is computed here.
 #pragma once
 #include <algorithm>
+#include <array>
 #include <cstdint>
 #include <map>
 #include <memory>
@@ -382,6 +383,16 @@ class PIRServer {
     for (auto it = keys.begin(); rc == 0 && it != keys.end(); ++it)
       rc = pirgpu_set_galois_key(db_->handle(), it->first, it->second.data());
     return detail::FromRc(db_->handle(), rc);
+  }
+
+  // Seed-compressed key objects (what ProcessRequest receives from the reference client, client.cpp:47-54) have their
+  // c1 halves re-sampled on the device (pirgpu_keyset_set_keys_seeded): {objects expanded there
+  // so far, draws those expansions rejected}.
+  StatusOr<std::array<uint64_t, 2>> SeedExpansionStats() const {
+    std::array<uint64_t, 2> st{};
+    int rc = pirgpu_keyset_seed_stats(db_->handle(), st.data());
+    if (rc) return detail::FromRc(db_->handle(), rc);
+    return st;
   }
 
   // server.cpp:67-76

@@ -41,6 +41,9 @@
 #pragma weak pirgpu_current_table
 #pragma weak pirgpu_query_use_table
 #pragma weak pirgpu_batch_set_tables
+// The same for the device's seed expansion: where a back end lacks it, seed-compressed keys are
+// expanded on the host as before.
+#pragma weak pirgpu_keyset_set_keys_seeded
 
 namespace pirgpu {
 namespace wire {
@@ -124,6 +127,59 @@ int pirgpu_wire_load_kswitch_key(const pirgpu_params* params, const uint8_t* blo
   } catch (const Err& e) {
     return e.code;
   } catch (const std::exception&) {
+    return PIRGPU_INTERNAL;
+  }
+}
+
+// The splitting loader (split_kswitch_keys) without a device.  *all_seeded = every object of the set is seed-compressed;
+// then, if the set holds a key at `index`, its c0 halves [k][k+1][N] go to c0_out, its k seeds to seeds_out and *found
+// is 1 (either buffer may be null).  0, or the status the loader fails with, its message in err (err_cap bytes).
+int pirgpu_wire_split_kswitch_key(const pirgpu_params* params, const uint8_t* blob, size_t len, uint64_t index,
+                                  int* all_seeded, int* found, uint64_t* c0_out, uint8_t* seeds_out, char* err,
+                                  size_t err_cap) {
+  if (!params || !blob || !all_seeded || !found) return PIRGPU_INVALID_ARGUMENT;
+  auto report = [&](const std::string& msg) {
+    if (err && err_cap) snprintf(err, err_cap, "%s", msg.c_str());
+  };
+  report("");
+  *all_seeded = *found = 0;
+  try {
+    const Shape sh = make_shape(*params);
+    SplitKeys split;
+    split_kswitch_keys(sh, blob, len, nullptr, split);
+    *all_seeded = split.all_seeded ? 1 : 0;
+    const size_t half = (size_t)(sh.k + 1) * sh.N * 8;
+    for (const auto& e : split.entries) {
+      if (e.index != index) continue;
+      *found = 1;
+      for (uint32_t j = 0; j < sh.k; ++j) {
+        if (c0_out) memcpy(reinterpret_cast<uint8_t*>(c0_out) + j * half, e.c0[j], half);
+        if (seeds_out) memcpy(seeds_out + j * kSeedBytes, e.seed[j], kSeedBytes);
+      }
+    }
+    return PIRGPU_OK;
+  } catch (const Err& e) {
+    report(e.msg);
+    return e.code;
+  } catch (const std::exception& e) {
+    report(e.what());
+    return PIRGPU_INTERNAL;
+  }
+}
+
+// KSwitchKeys::load (load_kswitch_keys, every key expanded) for its status and message alone: what the splitting
+// loader's are compared with.
+int pirgpu_wire_load_kswitch_error(const pirgpu_params* params, const uint8_t* blob, size_t len, char* err, size_t err_cap) {
+  if (!params || !blob) return PIRGPU_INVALID_ARGUMENT;
+  if (err && err_cap) err[0] = 0;
+  try {
+    load_kswitch_keys(make_shape(*params), blob, len, [](uint64_t, const uint64_t*) {});
+    return PIRGPU_OK;
+  } catch (const Err& e) {
+    if (err && err_cap) snprintf(err, err_cap, "%s", e.msg.c_str());
+    return e.code;
+  } catch (const std::exception& e) {
+    if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
     return PIRGPU_INTERNAL;
   }
 }
@@ -498,6 +554,15 @@ struct CtxLock {
   CtxLock& operator=(const CtxLock&) = delete;
 };
 
+// Whether an all-seeded key set is expanded on the device: the back end has the entry point, and
+// PIRGPU_WIRE_SEED_EXPAND=0 (behind PIRGPU_ALLOW_ENV=1; read per new client, for A/B runs and tests) does not force the
+// host path.
+bool seed_expand_on_device() {
+  if (!pirgpu_keyset_set_keys_seeded) return false;
+  const char* v = pirgpu_env("PIRGPU_WIRE_SEED_EXPAND");
+  return !(v && v[0] == '0');
+}
+
 // SEALDeserialize<GaloisKeys> (server.cpp:46-48) with the device-resident key cache: a client that
 // repeats its (multi-MB) key object byte for byte finds its keys resident; a new client's keys are parsed -- the
 // objects of a seed-compressed Serializable<GaloisKeys>, what the reference client sends (client.cpp:47-54), are
@@ -533,11 +598,68 @@ void resolve_keys(const Server& sv, Job& job, bool speculative, bool* unverified
     job.pins = 1;
     return;
   }
+  const ParallelFor on_pool = [](size_t n, const std::function<void(size_t)>& fn) { Pool::get().parallel_for(n, 16, fn); };
+  if (seed_expand_on_device()) {
+    // A set whose every object is seed-compressed (what the reference client sends) goes to the device as c0 halves
+    // and seeds: no host thread hashes anything.  Expanded and mixed sets fall through.
+    SplitKeys galois, relin;
+    split_kswitch_keys(sv.sh, job.pr.galois_keys, job.pr.galois_keys_len, on_pool, galois);
+    bool device = galois.all_seeded;
+    if (device && sv.ctm) {
+      split_kswitch_keys(sv.sh, job.pr.relin_keys, job.pr.relin_keys_len, on_pool, relin);
+      device = relin.all_seeded;
+    }
+    if (device) {
+      const SplitKeys::Entry* relin_entry = nullptr;
+      if (sv.ctm) {
+        for (const auto& e : relin.entries)
+          if (e.index == 0) relin_entry = &e;
+        if (!relin_entry) throw Err{PIRGPU_INVALID_ARGUMENT, "RelinKeys holds no key"};
+        job.relin_checked = true;
+      }
+      // the digits of a key lie apart in the request: gathered per key (the ABI takes one [k][k+1][N] block per key)
+      const uint32_t k = sv.sh.k;
+      const size_t half = (size_t)(k + 1) * sv.sh.N * 8;
+      std::vector<const SplitKeys::Entry*> ents;
+      std::vector<uint32_t> elts;
+      for (const auto& e : galois.entries) {
+        ents.push_back(&e);
+        elts.push_back((uint32_t)(2 * e.index + 1));
+      }
+      if (relin_entry) {   // the relinearisation key rides as the key of element 1, which expansion never uses
+        ents.push_back(relin_entry);
+        elts.push_back(1);
+      }
+      const size_t n = ents.size();
+      std::vector<uint8_t> c0(n * k * half), seeds(n * k * kSeedBytes);
+      on_pool(n * k, [&](size_t i) {
+        memcpy(c0.data() + i * half, ents[i / k]->c0[i % k], half);
+        memcpy(seeds.data() + i * kSeedBytes, ents[i / k]->seed[i % k], kSeedBytes);
+      });
+      std::vector<const void*> c0p(n);
+      std::vector<const uint8_t*> sdp(n);
+      for (size_t i = 0; i < n; ++i) {
+        c0p[i] = c0.data() + i * k * half;
+        sdp[i] = seeds.data() + i * k * kSeedBytes;
+      }
+      rc = pirgpu_keyset_claim(sv.ctx, id, id_len, &slot);
+      if (rc) throw Err{rc, pirgpu_last_error(sv.ctx)};
+      rc = pirgpu_keyset_set_keys_seeded(sv.ctx, slot, (uint32_t)n, elts.data(), c0p.data(), sdp.data());   // one wait for the set
+      if (rc) {
+        const std::string msg = pirgpu_last_error(sv.ctx);
+        (void)pirgpu_keyset_release(sv.ctx, slot);
+        throw Err{rc, msg};
+      }
+      rc = pirgpu_keyset_pin(sv.ctx, slot);
+      if (rc) throw Err{rc, pirgpu_last_error(sv.ctx)};
+      job.slot = slot;
+      job.pins = 1;
+      return;
+    }
+  }
   // empty bytes -> load throws -> InvalidArgument, like the reference
   std::vector<std::pair<uint64_t, std::vector<uint64_t>>> parsed;
-  load_kswitch_keys_parallel(sv.sh, job.pr.galois_keys, job.pr.galois_keys_len,
-                             [](size_t n, const std::function<void(size_t)>& fn) { Pool::get().parallel_for(n, 16, fn); },
-                             parsed);
+  load_kswitch_keys_parallel(sv.sh, job.pr.galois_keys, job.pr.galois_keys_len, on_pool, parsed);
   std::vector<uint64_t> relin_key;   // ciphertext-multiplication contexts: RelinKeys index 0, validated like the rest
   if (sv.ctm) {
     load_kswitch_keys(sv.sh, job.pr.relin_keys, job.pr.relin_keys_len, [&](uint64_t i, const uint64_t* key) {

@@ -16,6 +16,14 @@ void pirgpu_wire_sample_poly_uniform(const uint8_t* seed, const uint64_t* moduli
 struct pirgpu_params;
 int pirgpu_wire_load_kswitch_key(const struct pirgpu_params* params, const uint8_t* blob, size_t len, uint64_t index,
                                  uint64_t* out);
+// The splitting loader for seed-compressed key sets without a device: *all_seeded = every object of the set is
+// seed-compressed; then the c0 halves [k][k+1][N] and the k seeds of the key at `index` (if *found).  Status and message
+// (err, err_cap bytes) as the server would fail with.  pirgpu_wire_load_kswitch_error: those of the expanding loader.
+int pirgpu_wire_split_kswitch_key(const struct pirgpu_params* params, const uint8_t* blob, size_t len, uint64_t index,
+                                  int* all_seeded, int* found, uint64_t* c0_out, uint8_t* seeds_out, char* err,
+                                  size_t err_cap);
+int pirgpu_wire_load_kswitch_error(const struct pirgpu_params* params, const uint8_t* blob, size_t len, char* err,
+                                   size_t err_cap);
 // Device-free validation of a serialized pir.Request (same checks as pirgpu_process_request).
 struct pirgpu_params;
 int pirgpu_wire_validate_request(const struct pirgpu_params* params, const uint8_t* request, size_t request_len,

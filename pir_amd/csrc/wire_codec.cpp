@@ -240,7 +240,21 @@ void load_ciphertext(Cursor& c, const Shape& sh, bool key_level, std::vector<uin
   load_ciphertext_into(c, sh, key_level, out.data());
 }
 
-void load_ciphertext_into(Cursor& c, const Shape& sh, bool key_level, uint64_t* out) {
+// The structure of one saved Ciphertext, every check of Ciphertext::load short of the coefficient ranges made: where
+// its coefficient words lie inside the bytes (any alignment), how many there are -- 2 nres N, or nres N for the
+// seed-compressed form, whose 64-byte seed then follows the array -- and where the object ends.
+namespace {
+struct CtView {
+  const uint8_t* words = nullptr;
+  uint64_t count = 0;
+  const uint8_t* seed = nullptr;   // null: fully expanded
+  const uint8_t* obj_end = nullptr;
+  uint32_t nres = 0;
+};
+}  // namespace
+
+static CtView view_ciphertext(Cursor& c, const Shape& sh, bool key_level) {
+  CtView v;
   const uint8_t* obj_end = c.header();
   Cursor o{c.p, obj_end};
   uint64_t id[4];
@@ -262,28 +276,65 @@ void load_ciphertext_into(Cursor& c, const Shape& sh, bool key_level, uint64_t* 
   if (count != full && count != full / 2)
     throw Err{PIRGPU_INVALID_ARGUMENT, "ciphertext data is invalid (coefficient count)"};
   a.need(count * 8);
-  memcpy(out, a.p, count * 8);
+  v.words = a.p;
+  v.count = count;
+  v.nres = nres;
+  v.obj_end = obj_end;
   if (count == full / 2) {
     // Seed-compressed object (Serializable<>, what PIRClient::initialize sends for its keys, client.cpp:47-54):
     // only c0 was saved; the 64-byte seed follows the IntArray and c1 is re-sampled from it
     // (Ciphertext::load_members -> expand_seed -> sample_poly_uniform over this object's moduli).
     Cursor sc{arr_end, o.end};
     sc.need(kSeedBytes);
-    SealPrng rng(sc.p);
+    v.seed = sc.p;
+  }
+  return v;
+}
+
+// is_data_valid_for on the words of an object where they lie in the request: every coefficient below its modulus.
+// `words` = polys x [nres][N] little-endian words at any alignment.
+static void check_coefficient_range(const Shape& sh, const uint8_t* words, uint32_t polys, uint32_t nres) {
+  for (uint32_t poly = 0; poly < polys; ++poly)
+    for (uint32_t j = 0; j < nres; ++j) {
+      const uint64_t q = sh.q[j];   // (key level: residue k is the special prime, sh.q[k])
+      const uint8_t* v = words + ((size_t)poly * nres + j) * sh.N * 8;
+      uint64_t bad = 0;   // branch-free scan (vectorises): any coefficient >= q
+      for (uint32_t i = 0; i < sh.N; ++i) {
+        uint64_t w;
+        memcpy(&w, v + (size_t)i * 8, 8);
+        bad |= (uint64_t)(w >= q);
+      }
+      if (bad) throw Err{PIRGPU_INVALID_ARGUMENT, "ciphertext data is invalid (coefficient out of range)"};
+    }
+}
+
+void load_ciphertext_into(Cursor& c, const Shape& sh, bool key_level, uint64_t* out) {
+  const CtView v = view_ciphertext(c, sh, key_level);
+  memcpy(out, v.words, v.count * 8);
+  if (v.seed) {
+    SealPrng rng(v.seed);
     uint64_t mods[PIRGPU_MAX_PRIMES + 1];
-    for (uint32_t j = 0; j < nres; ++j) mods[j] = sh.q[j];
-    sample_poly_uniform(rng, mods, nres, sh.N, out + full / 2);
+    for (uint32_t j = 0; j < v.nres; ++j) mods[j] = sh.q[j];
+    sample_poly_uniform(rng, mods, v.nres, sh.N, out + v.count);
   }
   // is_data_valid_for: every coefficient below its modulus
   for (uint32_t poly = 0; poly < 2; ++poly)
-    for (uint32_t j = 0; j < nres; ++j) {
-      const uint64_t q = (key_level && j == sh.k) ? sh.q[sh.k] : sh.q[j];
-      const uint64_t* v = out + ((size_t)poly * nres + j) * sh.N;
+    for (uint32_t j = 0; j < v.nres; ++j) {
+      const uint64_t q = sh.q[j];
+      const uint64_t* w = out + ((size_t)poly * v.nres + j) * sh.N;
       uint64_t bad = 0;   // branch-free scan (vectorises): any coefficient >= q
-      for (uint32_t i = 0; i < sh.N; ++i) bad |= (uint64_t)(v[i] >= q);
+      for (uint32_t i = 0; i < sh.N; ++i) bad |= (uint64_t)(w[i] >= q);
       if (bad) throw Err{PIRGPU_INVALID_ARGUMENT, "ciphertext data is invalid (coefficient out of range)"};
     }
-  c.p = obj_end;
+  c.p = v.obj_end;
+}
+
+// Ciphertext::load for its verdict alone: nothing is copied, and the c1 half of a seed-compressed object is not
+// sampled -- sample_poly_uniform yields residues below their moduli by construction.
+static void validate_ciphertext(Cursor& c, const Shape& sh, bool key_level) {
+  const CtView v = view_ciphertext(c, sh, key_level);
+  check_coefficient_range(sh, v.words, v.seed ? 1 : 2, v.nres);
+  c.p = v.obj_end;
 }
 
 // seed != nullptr: the Serializable<> form -- only c0 is written, followed by the 64-byte seed c1 was sampled from.
@@ -359,7 +410,7 @@ void load_kswitch_keys(const Shape& sh, const uint8_t* data, size_t len,
   uint64_t dim1 = o.u64();
   if (dim1 > sh.N) throw Err{PIRGPU_INVALID_ARGUMENT, "GaloisKeys data is invalid"};
   const uint32_t km = sh.k + 1;
-  std::vector<uint64_t> key((size_t)sh.k * 2 * km * sh.N), tmp;
+  std::vector<uint64_t> key(sink ? (size_t)sh.k * 2 * km * sh.N : 0), tmp;
   for (uint64_t index = 0; index < dim1; ++index) {
     uint64_t dim2 = o.u64();
     if (dim2 == 0) continue;
@@ -367,8 +418,12 @@ void load_kswitch_keys(const Shape& sh, const uint8_t* data, size_t len,
     for (uint64_t j = 0; j < dim2; ++j) {
       const uint8_t* pk_end = o.header();  // PublicKey wrapper
       Cursor pk{o.p, pk_end};
-      load_ciphertext(pk, sh, true, tmp);  // [2][k+1][N]
-      memcpy(key.data() + (size_t)j * 2 * km * sh.N, tmp.data(), tmp.size() * 8);
+      if (sink) {
+        load_ciphertext(pk, sh, true, tmp);  // [2][k+1][N]
+        memcpy(key.data() + (size_t)j * 2 * km * sh.N, tmp.data(), tmp.size() * 8);
+      } else {
+        validate_ciphertext(pk, sh, true);   // a validation-only load expands no seed
+      }
       o.p = pk_end;
     }
     if (sink) sink(index, key.data());
@@ -424,6 +479,78 @@ void load_kswitch_keys_parallel(const Shape& sh, const uint8_t* data, size_t len
   else for (size_t i = 0; i < pieces.size(); ++i) one(i);
   for (const Err& e : errs)
     if (e.code) throw e;   // the first failing object in object order, like the sequential loader
+}
+
+// The splitting loader: the same walk and the same checks, but nothing is copied and no seed is expanded.  When every
+// object of the set is seed-compressed, split.entries holds for every present entry its index and, per decomposition
+// digit, where the c0 half [k+1][N] lies inside `data` and where its seed does; the c0 halves have been range-checked
+// through `pf` and the first failing object in object order has thrown, like the loaders above (the c1 halves are
+// sampled below their moduli by whoever expands them).  When any object is fully expanded, all_seeded is false,
+// nothing has been range-checked and nothing has thrown for the objects: the caller runs a loader above, which
+// reports what there is to report.
+void split_kswitch_keys(const Shape& sh, const uint8_t* data, size_t len, const ParallelFor& pf, SplitKeys& split) {
+  Cursor c{data, data + len};
+  const uint8_t* obj_end = c.header();
+  Cursor o{c.p, obj_end};
+  uint64_t id[4];
+  for (int i = 0; i < 4; ++i) id[i] = o.u64();
+  if (memcmp(id, sh.key_id, 32) != 0) throw Err{PIRGPU_INVALID_ARGUMENT, "GaloisKeys data is invalid (parms_id mismatch)"};
+  uint64_t dim1 = o.u64();
+  if (dim1 > sh.N) throw Err{PIRGPU_INVALID_ARGUMENT, "GaloisKeys data is invalid"};
+  struct Piece {
+    size_t entry;
+    uint32_t j;
+    const uint8_t *p, *end;
+  };
+  std::vector<Piece> pieces;
+  split.entries.clear();
+  split.all_seeded = true;
+  for (uint64_t index = 0; index < dim1; ++index) {
+    uint64_t dim2 = o.u64();
+    if (dim2 == 0) continue;
+    if (dim2 != sh.k) throw Err{PIRGPU_INVALID_ARGUMENT, "GaloisKeys data is invalid (decomposition count)"};
+    split.entries.emplace_back();
+    split.entries.back().index = index;
+    split.entries.back().c0.assign(sh.k, nullptr);
+    split.entries.back().seed.assign(sh.k, nullptr);
+    for (uint64_t j = 0; j < dim2; ++j) {
+      const uint8_t* pk_end = o.header();  // PublicKey wrapper
+      pieces.push_back(Piece{split.entries.size() - 1, (uint32_t)j, o.p, pk_end});
+      o.p = pk_end;
+    }
+  }
+  // the structure of every object first (headers only): one expanded object sends the whole set down the other path
+  std::vector<Err> errs(pieces.size(), Err{0, ""});
+  std::vector<CtView> views(pieces.size());
+  for (size_t i = 0; i < pieces.size(); ++i) {
+    try {
+      Cursor pk{pieces[i].p, pieces[i].end};
+      views[i] = view_ciphertext(pk, sh, true);
+      if (!views[i].seed) split.all_seeded = false;
+    } catch (const Err& e) {
+      errs[i] = e;
+    }
+  }
+  if (!split.all_seeded) {
+    split.entries.clear();
+    return;
+  }
+  auto one = [&](size_t i) {
+    if (errs[i].code) return;
+    try {
+      check_coefficient_range(sh, views[i].words, 1, views[i].nres);
+      split.entries[pieces[i].entry].c0[pieces[i].j] = views[i].words;
+      split.entries[pieces[i].entry].seed[pieces[i].j] = views[i].seed;
+    } catch (const Err& e) {
+      errs[i] = e;
+    } catch (const std::exception& e) {
+      errs[i] = Err{PIRGPU_INTERNAL, e.what()};
+    }
+  };
+  if (pf) pf(pieces.size(), one);
+  else for (size_t i = 0; i < pieces.size(); ++i) one(i);
+  for (const Err& e : errs)
+    if (e.code) throw e;   // the first failing object in object order
 }
 
 std::string save_kswitch_keys(const Shape& sh, const std::vector<const uint64_t*>& entries,

@@ -155,6 +155,19 @@ void load_kswitch_keys(const Shape& sh, const uint8_t* data, size_t len,
 using ParallelFor = std::function<void(size_t, const std::function<void(size_t)>&)>;
 void load_kswitch_keys_parallel(const Shape& sh, const uint8_t* data, size_t len, const ParallelFor& pf,
                                 std::vector<std::pair<uint64_t, std::vector<uint64_t>>>& keys);
+// The splitting loader for seed-compressed sets: the same walk and checks, nothing copied, no seed expanded.  With
+// all_seeded, entries[e] names entry `index` by pointers INTO `data`: c0[j] = the c0 half [k+1][N] of digit j (range
+// checked through pf; any alignment), seed[j] = its kSeedBytes.  Without (one object or more fully expanded), entries
+// is empty and nothing was range-checked: the set belongs to a loader above.
+struct SplitKeys {
+  struct Entry {
+    uint64_t index;
+    std::vector<const uint8_t*> c0, seed;   // [k]
+  };
+  std::vector<Entry> entries;
+  bool all_seeded = false;
+};
+void split_kswitch_keys(const Shape& sh, const uint8_t* data, size_t len, const ParallelFor& pf, SplitKeys& split);
 // KSwitchKeys::save: entries[i] = key [k][2][k+1][N] or nullptr (absent), i < dim1.
 // seeds (optional): per entry k * kSeedBytes bytes -> the seed-compressed Serializable<> form (c1 halves omitted).
 std::string save_kswitch_keys(const Shape& sh, const std::vector<const uint64_t*>& entries,

@@ -406,6 +406,53 @@ class PIRServer:
             self._check(self.lib.pirgpu_keyset_set_key(self.db.handle, slot.value, int(g), _ptr(key)))
         return int(slot.value)
 
+    def install_keyset_seeded(self, client_id: bytes, seeded_keys: Dict[int, tuple]) -> int:
+        """install_keyset for seed-compressed keys: {Galois element: (c0 [k, k+1, N], seeds)} with seeds = k x 64 bytes
+        (bytes or a uint8 array), one seed per decomposition digit.  The c1 halves are re-sampled from the seeds on the
+        device (SEAL's BlakePRNG + sample_poly_uniform); the installed set equals the one install_keyset installs for the
+        expanded keys.  Element 1 carries the relinearisation key of ciphertext-multiplication mode."""
+        ident = np.frombuffer(client_id, dtype=np.uint8)
+        slot = C.c_uint32(0)
+        self._check(self.lib.pirgpu_keyset_lookup(self.db.handle, ident.ctypes.data_as(capi.u8p), len(client_id), 1,
+                                                  C.byref(slot)))
+        if slot.value:
+            return int(slot.value)
+        halves, seeds = [], []
+        for g, (c0, sd) in seeded_keys.items():
+            c0 = _u64(c0)
+            sd = np.ascontiguousarray(np.frombuffer(bytes(sd), dtype=np.uint8))
+            if c0.shape != (self.k, self.k + 1, self.N) or sd.size != 64 * self.k:
+                raise PirGpuError(3, "seeded Galois key must be c0 [%d, %d, %d] and %d seed bytes, got %s and %d"
+                                  % (self.k, self.k + 1, self.N, 64 * self.k, list(c0.shape), sd.size))
+            halves.append(c0)
+            seeds.append(sd)
+        n = len(halves)
+        self._check(self.lib.pirgpu_keyset_claim(self.db.handle, ident.ctypes.data_as(capi.u8p), len(client_id),
+                                                 C.byref(slot)))
+        elts = (C.c_uint32 * max(n, 1))(*[int(g) for g in seeded_keys])
+        p0 = (C.c_void_p * max(n, 1))(*[h.ctypes.data for h in halves])
+        ps = (C.c_void_p * max(n, 1))(*[s.ctypes.data for s in seeds])
+        rc = self.lib.pirgpu_keyset_set_keys_seeded(self.db.handle, slot.value, n, elts, p0, ps)
+        if rc:
+            msg = self.lib.pirgpu_last_error(self.db.handle).decode()
+            self.lib.pirgpu_keyset_release(self.db.handle, slot.value)
+            raise PirGpuError(rc, msg)
+        return int(slot.value)
+
+    def expand_seeds(self, seeds: Sequence[bytes]) -> np.ndarray:
+        """Test hook: the device's re-sampling of n 64-byte seeds over the key-level moduli -> [n, k+1, N]."""
+        flat = np.frombuffer(b"".join(bytes(s) for s in seeds), dtype=np.uint8).copy()
+        if flat.size != 64 * len(seeds):
+            raise PirGpuError(3, "every seed must be 64 bytes")
+        out = np.empty((len(seeds), self.k + 1, self.N), dtype=np.uint64)
+        self._check(self.lib.pirgpu_expand_seeds(self.db.handle, flat.ctypes.data_as(capi.u8p), len(seeds), _ptr(out)))
+        return out
+
+    def keyset_seed_stats(self) -> Dict[str, int]:
+        st = (C.c_uint64 * 2)()
+        self._check(self.lib.pirgpu_keyset_seed_stats(self.db.handle, st))
+        return {"objects": int(st[0]), "rejected": int(st[1])}
+
     def release_keyset(self, slot: int) -> None:
         self._check(self.lib.pirgpu_keyset_release(self.db.handle, slot))
 
