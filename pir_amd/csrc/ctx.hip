@@ -11,12 +11,13 @@
 //        options.h) into the context's fields
 //   [3]  oblivious expansion: expand_core (levels: ks_digit -> ks_mac_intt -> ks_mac_combine / ks_combine; last level
 //        in the NTT domain), expand_query_to_sv
-//   [4]  multiply: scan_group_mfma / scan_on_device, post_scan_stage (inverse NTT, upper levels, fold)
+//   [4]  multiply: scan_group_mfma / scan_pair_mfma / scan_on_device, post_scan_stage (inverse NTT, upper levels, fold)
 //   [5]  C ABI: create / destroy, options, database loading (db_encode, db_pack), finalize
 //   [6]  C ABI: Galois keys, per-client key sets (handles with generations, pins, LRU)
 //   [7]  C ABI: single query, join / fork, test hooks
-//   [8]  batch pipeline: staging, lanes, expand_group_on_lane, batch_run_mfma (groups of 8 on two lanes); contexts with
-//        tables: plan_table_runs (order by table, runs inside a group), scan_group_runs (one launch for all runs)
+//   [8]  batch pipeline: staging, lanes and what every walk over groups shares (claim_lane, LaneStage, queue_download),
+//        expand_group_on_lane, scan_group_runs (tables: one launch for all runs of a group), batch_run_mfma (one body per
+//        step of the plan: a group of 8 or a pair).  The plan itself is host arithmetic in batch_plan.h
 //   [9]  multi-GPU entry points: u64 exchange, packed row shards, slot shards (pirgpu_slots_*), fix-up, pack40
 //   [10] measurement
 // The kernels are in kernels.hip, scan_mfma.hip, ntt_kernels.hip (+ ntt_core.h, arith.h); the wire level in wire.cpp.
@@ -36,6 +37,7 @@
 #include <vector>
 
 #include "../../include/pirgpu.h"
+#include "batch_plan.h"
 #include "ctmult.h"
 #include "device_params.h"
 #include "host_math.h"
@@ -115,8 +117,9 @@ struct Worker {
 
 // Batch mode with the MFMA scan: a group of up to 8 queries is expanded TOGETHER on one lane (the
 // expansion kernels run over nodes x queries, ciphertext index = node * B + query), scanned in one
-// database pass, and finished per query on the workers' own streams.  Two lanes alternate so that the
-// bandwidth-bound scan of one group overlaps the compute-bound expansion of the next.
+// database pass, and finished together on the same lane, in the lane's query-major buffers (the workers lend their
+// selection vectors only).  Two lanes alternate so that the bandwidth-bound scan of one group overlaps the
+// compute-bound expansion of the next.
 // The first few levels of a group's expansion tree are a chain of small, latency-bound launches (8-128 tree ciphertexts:
 // three dependent launches per level, 5-7 us each on their own, ~20 us each while the other lane's big kernels own the
 // chip).  On the lane they cost 0.2-0.35 ms of a group's ~3 ms although they need almost no CU time.  Round 4: they run
@@ -170,6 +173,15 @@ struct Stage {
   bool rows_inverted = false;   // the row sums in lvl[d - 1] are in coefficient form already (slot-sharded step: the
                                 // inverse transform gathered them out of the exchange buffer)
   uint32_t ksets[kMaxMfmaQueries] = {};   // ciphertext-multiplication mode: key set of every query (its relinearisation key)
+};
+
+// One group of a step of batch_run_mfma's walk: a step is one group, or two halves that share a database pass (half 0 in
+// the members' and the lane's usual buffers, half 1 in the lane's second set).  They differ in nothing else.
+struct GroupHalf {
+  uint32_t first, n;    // its queries, by position in the served order
+  uint64_t* sv;         // selection vectors of the lane's own expansion, [query][dim_sum]; null: the members' sv_ntt
+  uint64_t* rows;       // its row sums (level d - 1), query-major
+  MfmaPtrs sel, col;    // per query: the selection vector, and the column selectors inside it that the pass reads
 };
 
 // Ciphertext-multiplication mode: the scratch one owner of a multiply (a worker, a lane) runs its products in, allocated
@@ -716,28 +728,6 @@ void check_transparent(pirgpu_ctx* c, uint32_t table = 0) {
   if (zeros && !c->allow_transparent) throw Fail{PIRGPU_INTERNAL, "result ciphertext is transparent"};
 }
 
-// Contexts with tables: the order a batch is served in.  The queries are sorted by table (stable: equal tables keep their
-// submission order) so that equal tables meet in the same group of `group` queries; order[i] = the staged query served at
-// position i.  A RUN is a maximal stretch of positions with one table inside one group: run r covers the positions
-// [run_begin[r], run_begin[r + 1]) and is scanned against its table's operand layout.  Host only, no device state.
-struct TablePlan {
-  std::vector<uint32_t> order, run_begin;
-  bool identity = true;   // order[i] == i: the batch is served exactly as a batch without tables
-};
-TablePlan plan_table_runs(const uint32_t* tables, uint32_t count, uint32_t group) {
-  TablePlan tp;
-  tp.order.resize(count);
-  for (uint32_t i = 0; i < count; ++i) tp.order[i] = i;
-  std::stable_sort(tp.order.begin(), tp.order.end(), [&](uint32_t a, uint32_t b) { return tables[a] < tables[b]; });
-  group = std::max<uint32_t>(group, 1);
-  for (uint32_t i = 0; i < count; ++i) {
-    tp.identity = tp.identity && tp.order[i] == i;
-    if (i == 0 || i % group == 0 || tables[tp.order[i]] != tables[tp.order[i - 1]]) tp.run_begin.push_back(i);
-  }
-  tp.run_begin.push_back(count);
-  return tp;
-}
-
 void alloc_worker(pirgpu_ctx* c, Worker& w);
 void ensure_expansion_buffers(pirgpu_ctx* c, Worker& w);
 
@@ -992,6 +982,11 @@ void check_staged_keysets(pirgpu_ctx* c) {
       throw Fail{PIRGPU_FAILED_PRECONDITION,
                  "stale key set handle: a key set of the staged batch was evicted or released (pirgpu_batch_set_keysets again)"};
   }
+}
+// key set of query `query` (submission index) of the current batch; 0 where none was assigned (caller-owned selectors)
+uint32_t keyset_of(pirgpu_ctx* c, uint32_t query) {
+  const std::vector<uint32_t>& ks = c->bs().batch_keysets;
+  return query < ks.size() ? ks[query] : 0;
 }
 
 const uint64_t* find_key(pirgpu_ctx* c, uint32_t slot, uint32_t g) {
@@ -1372,6 +1367,30 @@ void pack_range(pirgpu_ctx* c, const uint64_t* d_enc, uint64_t l0, uint64_t n, D
   HIP_TRY(hipStreamSynchronize(c->stream));   // the unit lists above are read by the copies queued here
 }
 
+// A database pass of the batch pipeline on stream `st`: counted (SCAN_LAUNCHES) and, while profiling is on, timed between
+// two events for pirgpu_batch_scan_timings -- the first kMaxBscan launches, with the workgroups and queries of the last.
+template <typename Launch>
+void timed_scan_launch(pirgpu_ctx* c, hipStream_t st, uint32_t wgs, uint32_t nq, Launch&& launch) {
+  constexpr uint32_t kMaxBscan = 64;
+  const bool timed = c->prof && c->bscan_n < kMaxBscan;
+  if (timed) {
+    while (c->bscan_ev.size() < 2 * (size_t)(c->bscan_n + 1)) {
+      hipEvent_t e;
+      HIP_TRY(hipEventCreate(&e));
+      c->bscan_ev.push_back(e);
+    }
+    HIP_TRY(hipEventRecord(c->bscan_ev[2 * c->bscan_n], st));
+  }
+  launch();
+  ++c->options.counter(OPT_SCAN_LAUNCHES);
+  if (timed) {
+    HIP_TRY(hipEventRecord(c->bscan_ev[2 * c->bscan_n + 1], st));
+    ++c->bscan_n;
+    c->bscan_wgs = wgs;
+    c->bscan_nq = nq;
+  }
+}
+
 // One pass of the MFMA scan for up to 8 queries (the caller has ordered stream `st` after their expansions): pack
 // the column selectors (unless they arrive packed), scan, fold column chunks.  Row sums of query q go to
 // out + q * scan_rows ciphertexts; `part` (query-major as well) holds the per-chunk sums of matrices wider than one chunk.
@@ -1396,33 +1415,20 @@ void scan_group_mfma(pirgpu_ctx* c, hipStream_t st, uint8_t*& selp, const MfmaPt
   // the streams' state at enqueue time); a lone group gets the whole chip
   const bool share = share_chip && !profiled && c->scan_wgs_batch;
   const uint32_t wgs = share ? c->scan_wgs_batch : 0;
-  constexpr uint32_t kMaxBscan = 64;
-  const bool timed = c->prof && !profiled && c->bscan_n < kMaxBscan;
-  if (timed) {
-    while (c->bscan_ev.size() < 2 * (size_t)(c->bscan_n + 1)) {
-      hipEvent_t e;
-      HIP_TRY(hipEventCreate(&e));
-      c->bscan_ev.push_back(e);
-    }
-    HIP_TRY(hipEventRecord(c->bscan_ev[2 * c->bscan_n], st));
-  }
-  HIP_TRY(launch_scan_mfma(st, c->dp, c->mg, table_dbp(c, table), packed, out, out_qstride, n, c->scan_rows, kN, words, wgs,
-                           n > 1 ? (c->scan_f64_fold || c->scan_f64_fold_batch) : c->scan_f64_fold));
-  if (!profiled) ++c->options.counter(OPT_SCAN_LAUNCHES);
-  if (timed) {
-    HIP_TRY(hipEventRecord(c->bscan_ev[2 * c->bscan_n + 1], st));
-    ++c->bscan_n;
-    c->bscan_wgs = wgs;
-    c->bscan_nq = n;
-  }
+  auto launch = [&] {
+    HIP_TRY(launch_scan_mfma(st, c->dp, c->mg, table_dbp(c, table), packed, out, out_qstride, n, c->scan_rows, kN, words, wgs,
+                             n > 1 ? (c->scan_f64_fold || c->scan_f64_fold_batch) : c->scan_f64_fold));
+  };
+  // (a profiled single query has its own phase timings and is no batch pass: not counted, not timed here)
+  if (profiled) launch();
+  else timed_scan_launch(c, st, wgs, n, launch);
   if (c->mg.nchunks > 1)
     HIP_TRY(launch_reduce_splits(st, c->dp, part, c->mg.nchunks, words, out_base, n, (uint64_t)c->mg.nchunks * words, words));
 }
 
 // The same pass for TWO groups on one lane (scan_mfma_pair.hip): both groups' column selectors are packed, then ONE launch
-// multiplies every database tile it reads with both.  Group h's row sums go to out[h], query-major.  One column chunk.
-static void scan_pair_mfma(pirgpu_ctx* c, BatchLane& ln, const MfmaPtrs (&col)[2], const uint32_t (&n)[2],
-                           uint64_t* const (&out)[2], bool sel_f64, bool share_chip) {
+// multiplies every database tile it reads with both.  Half h's row sums go to hv[h].rows, query-major.  One column chunk.
+static void scan_pair_mfma(pirgpu_ctx* c, BatchLane& ln, const GroupHalf (&hv)[2], bool sel_f64, bool share_chip) {
   const uint32_t kN = c->k * c->N;
   const uint64_t words = (uint64_t)c->scan_rows * c->ctw;
   hipStream_t st = ln.stream;
@@ -1432,30 +1438,16 @@ static void scan_pair_mfma(pirgpu_ctx* c, BatchLane& ln, const MfmaPtrs (&col)[2
   ScanGroups grp{};
   grp.n = 2;
   for (uint32_t h = 0; h < 2; ++h) {
-    HIP_TRY(launch_sel_pack(st, c->dp, c->mg, col[h], n[h], selp[h], c->scan_cols, kN, sel_f64));
+    HIP_TRY(launch_sel_pack(st, c->dp, c->mg, hv[h].col, hv[h].n, selp[h], c->scan_cols, kN, sel_f64));
     grp.sel[h] = selp[h];
-    grp.out[h] = out[h];
-    grp.nq[h] = (uint8_t)n[h];
+    grp.out[h] = hv[h].rows;
+    grp.nq[h] = (uint8_t)hv[h].n;
   }
   const uint32_t wgs = share_chip && c->scan_wgs_batch ? c->scan_wgs_batch : 0;
-  const bool timed = c->prof && c->bscan_n < 64;
-  if (timed) {
-    while (c->bscan_ev.size() < 2 * (size_t)(c->bscan_n + 1)) {
-      hipEvent_t e;
-      HIP_TRY(hipEventCreate(&e));
-      c->bscan_ev.push_back(e);
-    }
-    HIP_TRY(hipEventRecord(c->bscan_ev[2 * c->bscan_n], st));
-  }
-  HIP_TRY(launch_scan_mfma_pair(st, c->dp, c->mg, c->d_dbp, grp, c->scan_rows, words, wgs,
-                                c->scan_f64_fold || c->scan_f64_fold_batch, 0, kN, words, kN));
-  ++c->options.counter(OPT_SCAN_LAUNCHES);
-  if (timed) {
-    HIP_TRY(hipEventRecord(c->bscan_ev[2 * c->bscan_n + 1], st));
-    ++c->bscan_n;
-    c->bscan_wgs = wgs;
-    c->bscan_nq = n[0] + n[1];
-  }
+  timed_scan_launch(c, st, wgs, hv[0].n + hv[1].n, [&] {
+    HIP_TRY(launch_scan_mfma_pair(st, c->dp, c->mg, c->d_dbp, grp, c->scan_rows, words, wgs,
+                                  c->scan_f64_fold || c->scan_f64_fold_batch, 0, kN, words, kN));
+  });
 }
 
 // Base case of PIRDatabase::multiply (reference database.cpp:185-194,238-247): one fused
@@ -3959,8 +3951,6 @@ static void ensure_pair_buffers(pirgpu_ctx* c, BatchLane& ln, bool expands) {
   ln.rows2 = c->dalloc<uint64_t>((size_t)kMaxMfmaQueries * c->lvl_cts[c->d - 1] * c->ctw);
 }
 
-// Batched oblivious expansion of the staged queries first .. first+B-1 on lane `ln`, B queries interleaved
-// (ciphertext index = node * B + query), into the members' own selection vectors (NTT form).
 static void ensure_head_slot(pirgpu_ctx* c, HeadSlot& hs) {
   if (hs.res_a) return;
   const uint32_t N = c->N, k = c->k;
@@ -3977,6 +3967,104 @@ static void ensure_head_slot(pirgpu_ctx* c, HeadSlot& hs) {
   }
 }
 
+// ---- what every walk over groups shares (batch_run_mfma, the 64-bit rounds, the packed and the slot-sharded steps) ----
+
+static uint32_t active_workers(const pirgpu_ctx* c) { return active_workers(c->n_active, (uint32_t)c->workers.size()); }
+static uint32_t lanes_in_use(const pirgpu_ctx* c, uint32_t G) { return lanes_in_use(active_workers(c), G, (uint32_t)c->lanes.size()); }
+
+// `after` / `then` (a stream of the caller's, may be null): the lane waits for what is queued on `after` so far, `then`
+// for what is queued on the lane so far.
+static void lane_after(pirgpu_ctx* c, hipStream_t lane, void* after) {
+  if (!after) return;
+  if (!c->ev_after) HIP_TRY(hipEventCreateWithFlags(&c->ev_after, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(c->ev_after, (hipStream_t)after));
+  HIP_TRY(hipStreamWaitEvent(lane, c->ev_after, 0));
+}
+static void lane_then(BatchLane& ln, void* then) {
+  if (!then) return;
+  if (!ln.ev_join) HIP_TRY(hipEventCreateWithFlags(&ln.ev_join, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(ln.ev_join, ln.stream));
+  HIP_TRY(hipStreamWaitEvent((hipStream_t)then, ln.ev_join, 0));
+}
+
+// The next lane of `nl` in turn, with n workers bound to it as the members of its group (they lend their selection-vector
+// buffers): member q is worker (lane * per_lane + base + q) mod W -- lane-bound with per_lane = G, so that stream order
+// on the lane covers their reuse -- and the lane waits until whoever used a member's buffers last is done.
+struct LaneClaim {
+  BatchLane& ln;
+  uint32_t n;
+  Worker* members[kMaxMfmaQueries];
+};
+static LaneClaim claim_lane(pirgpu_ctx* c, uint32_t nl, uint32_t n, uint32_t per_lane, uint32_t base = 0, void* after = nullptr) {
+  const uint32_t li = (uint32_t)(c->groups_run++ % nl), W = active_workers(c);
+  LaneClaim cl{c->lanes[li], n, {}};
+  lane_after(c, cl.ln.stream, after);
+  for (uint32_t q = 0; q < n; ++q) {
+    cl.members[q] = &c->workers[(li * per_lane + base + q) % W];
+    HIP_TRY(hipStreamWaitEvent(cl.ln.stream, cl.members[q]->ev_done, 0));
+  }
+  return cl;
+}
+// The members' buffers are free once the lane got here (replies_elsewhere: in the lane / batch buffers, not the workers').
+static void release_lane(const LaneClaim& cl, bool replies_elsewhere) {
+  for (uint32_t q = 0; q < cl.n; ++q) {
+    HIP_TRY(hipEventRecord(cl.members[q]->ev_done, cl.ln.stream));
+    if (replies_elsewhere) cl.members[q]->reply_valid = false;
+  }
+}
+
+// The multiply of a group of n queries in a lane's query-major buffers -- except the row sums (level d - 1) at `rows` and
+// level 0 at `lvl0` where given: the replies' own place, so that the last fold and the final inverse transform write them
+// where they are read (no device-to-device copy per group).
+struct LaneStage {
+  uint64_t* lvl[PIRGPU_MAX_DIMS];
+  Stage sg;
+  LaneStage(const pirgpu_ctx* c, BatchLane& ln, uint32_t n, uint64_t* lvl0, uint64_t* rows)
+      : sg{ln.stream, lvl, ln.pt_buf, n, MfmaPtrs{}, false, &ln.up_scratch, &ln.up_scratch_words} {
+    for (uint32_t l = 0; l < c->d; ++l) lvl[l] = ln.lvl[l];
+    if (rows) lvl[c->d - 1] = rows;
+    if (lvl0) lvl[0] = lvl0;
+    sg.last = ln.last;   // result_primes: level 0 lands there, the compact switch writes the replies to lvl[0]
+  }
+  LaneStage(const LaneStage&) = delete;
+};
+
+// Set while the batch pipeline enqueues work (pirgpu_ctx::in_batch), on every way out.
+struct InBatch {
+  bool& f;
+  explicit InBatch(pirgpu_ctx* c) : f(c->in_batch) { f = true; }
+  ~InBatch() { f = false; }
+};
+
+// pirgpu_batch_set_host_replies: a group's replies start their way to the host while the next groups are computed -- on
+// the context's COPY stream, behind an event of the lane: the lane itself goes straight on to its next group (round 3
+// queued the copy on the lane, which then idled for 8 MB of PCIe per group: 5-6 % of a lane's time at cfg 3).  The n
+// replies from `first` on in one copy, or -- a permuted group -- those at scattered[q], one copy each; `report` = how many
+// LEADING queries of the batch are complete with this group (the copy stream runs the groups' copies in order).
+static void queue_download(pirgpu_ctx* c, BatchLane& ln, uint32_t first, uint32_t n, const uint32_t* scattered, uint32_t report) {
+  BatchSet& b = c->bs();
+  const size_t rwords = (size_t)c->reply_cts * c->rctw, gi = b.dl_end.size();
+  while (gi >= b.dl_events.size()) {
+    hipEvent_t e;
+    HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    b.dl_events.push_back(e);
+    HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    b.rd_events.push_back(e);
+  }
+  if (!c->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+  HIP_TRY(hipEventRecord(b.rd_events[gi], ln.stream));
+  HIP_TRY(hipStreamWaitEvent(c->copy_stream, b.rd_events[gi], 0));
+  for (uint32_t q = 0; q < (scattered ? n : 1); ++q) {
+    const size_t at = (size_t)(scattered ? scattered[q] : first) * rwords;
+    HIP_TRY(hipMemcpyAsync(b.host_reply + at, reply_base(c) + at, (scattered ? 1 : n) * rwords * 8, hipMemcpyDeviceToHost,
+                           c->copy_stream));
+  }
+  HIP_TRY(hipEventRecord(b.dl_events[gi], c->copy_stream));
+  b.dl_end.push_back(report);
+}
+
+// Batched oblivious expansion of the staged queries first .. first+B-1 on lane `ln`, B queries interleaved
+// (ciphertext index = node * B + query), into the members' own selection vectors (NTT form).
 // sv_dst (optional): the selection vector of query q goes to sv_dst + q * dim_sum ciphertexts (caller-owned memory that
 // outlives the members' buffers: the slot-sharded step keeps its row selectors there for two steps) instead of the
 // members' own buffers.
@@ -4016,8 +4104,7 @@ static void expand_group_on_lane(pirgpu_ctx* c, BatchLane& ln, Worker* const* me
     uint32_t ksets[kMaxMfmaQueries];   // every query of the group is switched with its own client's keys
     for (uint32_t q = 0; q < B; ++q) {
       dst.p[q] = (sv_dst ? sv_dst + (size_t)q * c->dim_sum * ctw : members[q]->sv_ntt) + produced * ctw;
-      const uint32_t oq = qidx ? qidx[q] : first + q;
-      ksets[q] = oq < c->bs().batch_keysets.size() ? c->bs().batch_keysets[oq] : 0;
+      ksets[q] = keyset_of(c, qidx ? qidx[q] : first + q);
     }
     uint64_t* res;
     if (use_head) {
@@ -4097,33 +4184,12 @@ static void scan_group_runs(pirgpu_ctx* c, BatchLane& ln, const MfmaPtrs& col, u
     grp.db[r] = table_dbp(c, tabs[r]);
   }
   const uint32_t wgs = share_chip && c->scan_wgs_batch ? c->scan_wgs_batch : 0;
-  const bool timed = c->prof && c->bscan_n < 64;
-  if (timed) {
-    while (c->bscan_ev.size() < 2 * (size_t)(c->bscan_n + 1)) {
-      hipEvent_t e;
-      HIP_TRY(hipEventCreate(&e));
-      c->bscan_ev.push_back(e);
-    }
-    HIP_TRY(hipEventRecord(c->bscan_ev[2 * c->bscan_n], ln.stream));
-  }
-  HIP_TRY(launch_scan_mfma_runs(ln.stream, c->dp, c->mg, grp, c->scan_rows, kN, words, wgs,
-                                c->scan_f64_fold || c->scan_f64_fold_batch, out_qstride));
-  ++c->options.counter(OPT_SCAN_LAUNCHES);
-  if (timed) {
-    HIP_TRY(hipEventRecord(c->bscan_ev[2 * c->bscan_n + 1], ln.stream));
-    ++c->bscan_n;
-    c->bscan_wgs = wgs;
-    c->bscan_nq = B;
-  }
+  timed_scan_launch(c, ln.stream, wgs, B, [&] {
+    HIP_TRY(launch_scan_mfma_runs(ln.stream, c->dp, c->mg, grp, c->scan_rows, kN, words, wgs,
+                                  c->scan_f64_fold || c->scan_f64_fold_batch, out_qstride));
+  });
   if (nch > 1)
     HIP_TRY(launch_reduce_splits(ln.stream, c->dp, ln.scan_part, nch, words, out_base, B, (uint64_t)nch * words, words));
-}
-
-// Members (selection-vector buffers) of the group that runs on lane `li`: lane-bound, so that stream order on the
-// lane covers their reuse; with fewer than 2 x G workers every group uses lane 0.
-static uint32_t lanes_in_use(pirgpu_ctx* c, uint32_t G) {
-  const uint32_t W = std::max<uint32_t>(1, std::min<uint32_t>(c->n_active, (uint32_t)c->workers.size()));
-  return std::max<uint32_t>(1, std::min<uint32_t>((uint32_t)c->lanes.size(), W / std::max<uint32_t>(G, 1)));
 }
 
 // qtab (contexts with tables): the table of every query of the batch, by submission index.  The groups are then formed
@@ -4131,148 +4197,65 @@ static uint32_t lanes_in_use(pirgpu_ctx* c, uint32_t G) {
 static void batch_run_mfma(pirgpu_ctx* c, uint32_t count, const uint64_t* ext_sv, const PackedInput* pk = nullptr,
                            const uint32_t* qtab = nullptr) {
   const size_t rwords = (size_t)c->reply_cts * c->rctw, svwords = (size_t)c->dim_sum * c->ctw;
-  const uint32_t W = std::max<uint32_t>(1, std::min<uint32_t>(c->n_active, (uint32_t)c->workers.size()));
+  const uint32_t W = active_workers(c);
   const uint32_t G = std::min<uint32_t>(c->mfma_nq, W);
   TablePlan tp;
   if (qtab) tp = plan_table_runs(qtab, count, G);
   const uint32_t* order = qtab && !tp.identity ? tp.order.data() : nullptr;   // position in the served order -> staged query
   auto oq = [&](uint32_t pos) { return order ? order[pos] : pos; };
   auto tab = [&](uint32_t pos) { return qtab ? qtab[oq(pos)] : 0u; };
-  std::vector<uint8_t> done(order ? count : 0, 0);   // permuted batch: submission indices whose replies are queued
-  uint32_t lead = 0;                                 // ... and how many leading ones are
+  LeadingReplies lead(order ? count : 0);   // permuted batch: what its groups report as downloaded
   const uint32_t my_rows = c->se - c->sb;
   ensure_lanes(c, !ext_sv && !pk);
   const uint32_t nl = lanes_in_use(c, G);
   // groups: runs of up to G consecutive queries; with packed input a group is what ONE source rank packed together
   // (its queries in runs of kMaxMfmaQueries), so the walk restarts at every source-rank boundary
-  const uint32_t span = pk ? pk->per_rank : count;
+  const uint32_t span = pk ? pk->per_rank : count, step = pk ? (uint32_t)kMaxMfmaQueries : G;
   // groups this call queues: with two or more (and two lanes) every pass runs on half the chip
-  uint32_t n_groups = 0;
-  for (uint32_t rank0 = 0; rank0 < count; rank0 += span) {
-    const uint32_t in_span = std::min<uint32_t>(span, count - rank0);
-    n_groups += (in_span + (pk ? (uint32_t)kMaxMfmaQueries : G) - 1) / (pk ? (uint32_t)kMaxMfmaQueries : G);
-  }
+  const uint32_t n_groups = count_groups(count, span, step);
   const bool share_chip = n_groups >= 2 && nl >= 2;
-  // pirgpu_batch_set_host_replies: every group downloads its replies as soon as they exist (on its lane's stream)
+  // pirgpu_batch_set_host_replies: every group downloads its replies as soon as they exist (queue_download)
   const bool host_dl = c->bs().host_reply && (uint64_t)count * c->reply_cts <= c->bs().host_reply_cts;
   c->bs().host_reply_done = host_dl;
   c->bs().dl_end.clear();
   c->bs().dl_next = 0;
-  // the per-group download of finished replies (pirgpu_batch_set_host_replies), consecutive queries
-  auto queue_download = [&](BatchLane& ln, uint32_t first, uint32_t B) {
-    BatchSet& b = c->bs();
-    const size_t gi = b.dl_end.size();
-    while (gi >= b.dl_events.size()) {
-      hipEvent_t e;
-      HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      b.dl_events.push_back(e);
-      HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      b.rd_events.push_back(e);
-    }
-    if (!c->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    HIP_TRY(hipEventRecord(b.rd_events[gi], ln.stream));
-    HIP_TRY(hipStreamWaitEvent(c->copy_stream, b.rd_events[gi], 0));
-    HIP_TRY(hipMemcpyAsync(b.host_reply + (size_t)first * rwords, reply_base(c) + (size_t)first * rwords,
-                           (size_t)B * rwords * 8, hipMemcpyDeviceToHost, c->copy_stream));
-    HIP_TRY(hipEventRecord(b.dl_events[gi], c->copy_stream));
-    b.dl_end.push_back(first + B);
-  };
   // Two groups per database read (PIRGPU_SCAN_MFMA_PAIR, scan_mfma_pair.hip): a lane expands group a (into its workers'
   // selection vectors) and group b (into its own second buffer), packs both, scans the database ONCE for both, then
   // finishes a and b one after the other.  The plain case only: the context's own expansion of one database in one
   // column chunk (or caller-owned selection vectors), re-encoding upper levels at every prime, replies written in place.
   // Everything else -- an odd last group, short calls under value 1, tables, packed / slot-sharded input, result_primes,
   // wide items, ciphertext-multiplication mode -- keeps one pass per group.
-  const bool may_pair = c->scan_pair && !pk && !qtab && c->d >= 2 && !c->ctm && !c->rp && c->planes <= 1 &&
+  const bool may_pair = !pk && !qtab && c->d >= 2 && !c->ctm && !c->rp && c->planes <= 1 &&
                         G == (uint32_t)kMaxMfmaQueries && scan_mfma_pair_supported(c->mg) &&
-                        (c->scan_pair >= 2 || (n_groups >= 4 && nl >= 2));
-  auto run_pair = [&](uint32_t first_a, uint32_t Ba, uint32_t first_b, uint32_t Bb) {
-    const uint32_t li = (uint32_t)(c->groups_run++ % nl);
-    BatchLane& ln = c->lanes[li];
-    ensure_pair_buffers(c, ln, !ext_sv);
-    const bool sel_f64 = !ext_sv && c->sel_f64;   // a lane's own selectors: exact doubles instead of u64
-    Worker* members[kMaxMfmaQueries];
-    for (uint32_t q = 0; q < Ba; ++q) {
-      members[q] = &c->workers[(li * G + q) % W];
-      HIP_TRY(hipStreamWaitEvent(ln.stream, members[q]->ev_done, 0));  // whoever used its buffers last is done
-    }
-    if (!ext_sv) {
-      expand_group_on_lane(c, ln, members, Ba, first_a, sel_f64);
-      expand_group_on_lane(c, ln, members, Bb, first_b, sel_f64, ln.sv2);
-    }
-    const uint32_t firsts[2] = {first_a, first_b}, n[2] = {Ba, Bb};
-    uint64_t* const rows_out[2] = {ln.lvl[c->d - 1], ln.rows2};
-    MfmaPtrs sel[2] = {}, col[2] = {};
-    for (uint32_t h = 0; h < 2; ++h)
-      for (uint32_t q = 0; q < n[h]; ++q) {
-        sel[h].p[q] = ext_sv ? ext_sv + (size_t)(firsts[h] + q) * svwords : (h ? ln.sv2 + (size_t)q * svwords : members[q]->sv_ntt);
-        col[h].p[q] = (const uint64_t*)sel[h].p[q] + (size_t)c->sv_off[c->d - 1] * c->ctw;
+                        pair_by_count(c->scan_pair, n_groups, nl);
+  const bool sel_f64 = !pk && !ext_sv && c->sel_f64;   // a lane's own selectors, read on that lane only: exact doubles
+  // (d = 1 would make the scan itself write to the replies, a permuted group's replies are not neighbours: the lane buffer)
+  const bool direct_reply = c->d >= 2 && !order;
+  for (const GroupStep& st : plan_group_walk(count, span, step, may_pair).steps) {
+    const uint32_t nh = st.n[1] ? 2 : 1;
+    if (st.n[0] > W) throw Fail{PIRGPU_FAILED_PRECONDITION, "packed groups need min(queries per rank, 8) workers (pirgpu_set_concurrency)"};
+    const LaneClaim cl = claim_lane(c, nl, st.n[0], G);
+    BatchLane& ln = cl.ln;
+    if (nh == 2) ensure_pair_buffers(c, ln, !ext_sv);
+    GroupHalf hv[2] = {{st.first[0], st.n[0], nullptr, ln.lvl[c->d - 1], {}, {}}, {st.first[1], st.n[1], ln.sv2, ln.rows2, {}, {}}};
+    if (!pk && !ext_sv)
+      for (uint32_t h = 0; h < nh; ++h)
+        expand_group_on_lane(c, ln, cl.members, hv[h].n, hv[h].first, sel_f64, hv[h].sv, order ? order + hv[h].first : nullptr);
+    for (uint32_t h = 0; h < nh; ++h)
+      for (uint32_t q = 0; q < hv[h].n; ++q) {
+        const uint64_t* own = hv[h].sv ? hv[h].sv + (size_t)q * svwords : cl.members[q]->sv_ntt;
+        const uint64_t* sv = ext_sv ? ext_sv + (size_t)oq(hv[h].first + q) * svwords : own;
+        // (packed input: the column selectors arrive packed, the row selectors are this shard's alone)
+        hv[h].sel.p[q] = pk ? pk->rows + (size_t)(hv[h].first + q) * my_rows * c->ctw : sv;
+        if (!pk) hv[h].col.p[q] = sv + (size_t)c->sv_off[c->d - 1] * c->ctw;
       }
-    scan_pair_mfma(c, ln, col, n, rows_out, sel_f64, share_chip);
-    for (uint32_t h = 0; h < 2; ++h) {
-      uint64_t* lvl_ptrs[PIRGPU_MAX_DIMS];
-      for (uint32_t l = 0; l < c->d; ++l) lvl_ptrs[l] = ln.lvl[l];
-      lvl_ptrs[c->d - 1] = rows_out[h];
-      lvl_ptrs[0] = reply_base(c) + (size_t)firsts[h] * rwords;   // d >= 2: level 0 is the replies, written in place
-      Stage sg{ln.stream, lvl_ptrs, ln.pt_buf, n[h], sel[h], false, &ln.up_scratch, &ln.up_scratch_words};
-      sg.sel_f64 = sel_f64;
-      for (uint32_t q = 0; q < n[h]; ++q)
-        sg.ksets[q] = firsts[h] + q < c->bs().batch_keysets.size() ? c->bs().batch_keysets[firsts[h] + q] : 0;
-      post_scan_stage(c, sg, nullptr);
-      if (host_dl) queue_download(ln, firsts[h], n[h]);
-    }
-    for (uint32_t q = 0; q < Ba; ++q) {
-      HIP_TRY(hipEventRecord(members[q]->ev_done, ln.stream));
-      members[q]->reply_valid = false;
-    }
-  };
-  for (uint32_t rank0 = 0; rank0 < count; rank0 += span) {
-    const uint32_t step = pk ? (uint32_t)kMaxMfmaQueries : G;
-    const uint32_t in_span = std::min<uint32_t>(span, count - rank0);
-    for (uint32_t j0 = 0; j0 < in_span; j0 += step) {
-      const uint32_t B = std::min<uint32_t>(step, in_span - j0);
-      if (may_pair && j0 + step < in_span) {   // a full group and whatever follows it
-        run_pair(rank0 + j0, B, rank0 + j0 + step, std::min<uint32_t>(step, in_span - j0 - step));
-        j0 += step;
-        continue;
-      }
-      if (B > W) throw Fail{PIRGPU_FAILED_PRECONDITION, "packed groups need min(queries per rank, 8) workers (pirgpu_set_concurrency)"};
-      const uint32_t li = (uint32_t)(c->groups_run++ % nl);
-      BatchLane& ln = c->lanes[li];
-      Worker* members[kMaxMfmaQueries];
-      for (uint32_t q = 0; q < B; ++q) {
-        members[q] = &c->workers[(li * G + q) % W];
-        HIP_TRY(hipStreamWaitEvent(ln.stream, members[q]->ev_done, 0));  // whoever used its buffers last is done
-      }
-      const uint32_t first = rank0 + j0;  // global index of the group's first query
-      const uint8_t* packed = nullptr;
-      // level 0 of the group = its replies, query-major with the reply buffer's own stride: the last fold and the final
-      // inverse transform write them where pirgpu_batch_fetch reads them (no device-to-device copy per group)
-      uint64_t* lvl_ptrs[PIRGPU_MAX_DIMS];
-      for (uint32_t l = 0; l < c->d; ++l) lvl_ptrs[l] = ln.lvl[l];
-      // (d = 1 would make the scan itself write there, a permuted group's replies are not neighbours: the lane buffer)
-      const bool direct_reply = c->d >= 2 && !order;
-      if (direct_reply) lvl_ptrs[0] = reply_base(c) + (size_t)first * rwords;
-      Stage sg{ln.stream, lvl_ptrs, ln.pt_buf, B, MfmaPtrs{}, pk != nullptr, &ln.up_scratch, &ln.up_scratch_words};
-      sg.last = ln.last;   // result_primes: level 0 lands there, the compact switch writes the replies to lvl_ptrs[0]
-      for (uint32_t q = 0; q < B; ++q)
-        sg.ksets[q] = oq(first + q) < c->bs().batch_keysets.size() ? c->bs().batch_keysets[oq(first + q)] : 0;
-      MfmaPtrs col{};
-      if (pk) {
-        const uint32_t groups_per_rank = (pk->per_rank + kMaxMfmaQueries - 1) / kMaxMfmaQueries;
-        packed = pk->packed + ((size_t)(rank0 / pk->per_rank) * groups_per_rank + j0 / kMaxMfmaQueries) * c->mg.sel_bytes;
-        for (uint32_t q = 0; q < B; ++q) sg.sel.p[q] = pk->rows + (size_t)(first + q) * my_rows * c->ctw;
-      } else {
-        if (!ext_sv) {
-          expand_group_on_lane(c, ln, members, B, first, c->sel_f64, nullptr, order ? order + first : nullptr);
-          sg.sel_f64 = c->sel_f64;   // written and read on this lane only: exact doubles instead of u64
-        }
-        for (uint32_t q = 0; q < B; ++q) {
-          const uint64_t* sv = ext_sv ? ext_sv + (size_t)oq(first + q) * svwords : members[q]->sv_ntt;
-          sg.sel.p[q] = sv;
-          col.p[q] = sv + (size_t)c->sv_off[c->d - 1] * c->ctw;
-        }
-      }
+    if (nh == 2) {
+      scan_pair_mfma(c, ln, hv, sel_f64, share_chip);
+    } else {
+      const uint32_t first = hv[0].first, B = hv[0].n;
+      const uint32_t groups_per_rank = pk ? (pk->per_rank + kMaxMfmaQueries - 1) / kMaxMfmaQueries : 0;
+      const uint8_t* packed = !pk ? nullptr : pk->packed + ((size_t)(first / pk->per_rank) * groups_per_rank +
+                                                             first % pk->per_rank / kMaxMfmaQueries) * c->mg.sel_bytes;
       // runs of equal tables among the members (one run without tables)
       uint32_t rb[kMaxMfmaQueries + 1], tabs[kMaxMfmaQueries], nr = 0;
       for (uint32_t q = 0; q < B; ++q)
@@ -4282,11 +4265,18 @@ static void batch_run_mfma(pirgpu_ctx* c, uint32_t count, const uint64_t* ext_sv
         }
       rb[nr] = B;
       if (nr == 1)
-        scan_group_mfma(c, ln.stream, ln.selp, col, B, ln.lvl[c->d - 1], ln.scan_part, nullptr, packed, sg.sel_f64,
-                        share_chip, tabs[0]);
+        scan_group_mfma(c, ln.stream, ln.selp, hv[0].col, B, hv[0].rows, ln.scan_part, nullptr, packed, sel_f64, share_chip, tabs[0]);
       else
-        scan_group_runs(c, ln, col, B, rb, nr, tabs, sg.sel_f64, share_chip);
-      post_scan_stage(c, sg, nullptr);
+        scan_group_runs(c, ln, hv[0].col, B, rb, nr, tabs, sel_f64, share_chip);
+    }
+    for (uint32_t h = 0; h < nh; ++h) {
+      const uint32_t first = hv[h].first, B = hv[h].n;
+      LaneStage ls(c, ln, B, direct_reply ? reply_base(c) + (size_t)first * rwords : nullptr, hv[h].rows);
+      ls.sg.sel = hv[h].sel;
+      ls.sg.local_rows = pk != nullptr;
+      ls.sg.sel_f64 = sel_f64;
+      for (uint32_t q = 0; q < B; ++q) ls.sg.ksets[q] = keyset_of(c, oq(first + q));
+      post_scan_stage(c, ls.sg, nullptr);
       if (order) {   // every reply to its query's own place
         for (uint32_t q = 0; q < B; ++q)
           HIP_TRY(hipMemcpyAsync(reply_base(c) + (size_t)oq(first + q) * rwords, ln.lvl[0] + (size_t)q * rwords, rwords * 8,
@@ -4294,42 +4284,9 @@ static void batch_run_mfma(pirgpu_ctx* c, uint32_t count, const uint64_t* ext_sv
       } else if (!direct_reply)
         HIP_TRY(hipMemcpyAsync(reply_base(c) + (size_t)first * rwords, ln.lvl[0], (size_t)B * rwords * 8,
                                hipMemcpyDeviceToDevice, ln.stream));
-      if (host_dl) {
-        // the group's replies start their way to the host while the next groups are computed -- on the context's COPY
-        // stream, behind an event of the lane: the lane itself goes straight on to its next group (round 3 queued the
-        // copy on the lane, which then idled for 8 MB of PCIe per group: 5-6 % of a lane's time at cfg 3)
-        if (!order) {
-          queue_download(ln, first, B);
-        } else {
-          BatchSet& b = c->bs();
-          const size_t gi = b.dl_end.size();
-          while (gi >= b.dl_events.size()) {
-            hipEvent_t e;
-            HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            b.dl_events.push_back(e);
-            HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            b.rd_events.push_back(e);
-          }
-          if (!c->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-          HIP_TRY(hipEventRecord(b.rd_events[gi], ln.stream));
-          HIP_TRY(hipStreamWaitEvent(c->copy_stream, b.rd_events[gi], 0));
-          // a permuted group's replies are scattered over the buffer: one copy each, and the group reports how many
-          // LEADING queries of the batch are complete with it (the copy stream runs the groups' copies in order)
-          for (uint32_t q = 0; q < B; ++q) {
-            const size_t at = (size_t)oq(first + q) * rwords;
-            HIP_TRY(hipMemcpyAsync(b.host_reply + at, reply_base(c) + at, rwords * 8, hipMemcpyDeviceToHost, c->copy_stream));
-            done[oq(first + q)] = 1;
-          }
-          while (lead < count && done[lead]) ++lead;
-          HIP_TRY(hipEventRecord(b.dl_events[gi], c->copy_stream));
-          b.dl_end.push_back(lead);
-        }
-      }
-      for (uint32_t q = 0; q < B; ++q) {
-        HIP_TRY(hipEventRecord(members[q]->ev_done, ln.stream));
-        members[q]->reply_valid = false;  // the group's replies live in the lane / batch buffers, not in the worker
-      }
+      if (host_dl) queue_download(c, ln, first, B, order ? order + first : nullptr, order ? lead.mark(order + first, B) : first + B);
     }
+    release_lane(cl, true);
   }
 }
 
@@ -4338,21 +4295,13 @@ static void batch_run_mfma(pirgpu_ctx* c, uint32_t count, const uint64_t* ext_sv
 // also shares the database pass (batch_run_mfma), otherwise groups of up to 4 workers share one pass of
 // scan_mq_kernel (d = 1 / few rows), hand-offs between streams through events.  With ext_sv the expansion
 // is skipped and query i reads its NTT-form selection vector at ext_sv + i*dim_sum.
-static void batch_run_impl_body(pirgpu_ctx* c, uint32_t count, const uint64_t* ext_sv);
 static void batch_run_impl(pirgpu_ctx* c, uint32_t count, const uint64_t* ext_sv) {
-  struct Flag {
-    bool& f;
-    explicit Flag(bool& x) : f(x) { f = true; }
-    ~Flag() { f = false; }
-  } flag(c->in_batch);
-  batch_run_impl_body(c, count, ext_sv);
-}
-static void batch_run_impl_body(pirgpu_ctx* c, uint32_t count, const uint64_t* ext_sv) {
+  InBatch in_batch(c);
   refuse_slot_shard(c);
   c->bs().host_reply_done = false;   // set again by the path that queues per-group downloads (batch_run_mfma)
   const size_t rwords = (size_t)c->reply_cts * c->rctw;
   const size_t svwords = (size_t)c->dim_sum * c->ctw;
-  const uint32_t W = std::max<uint32_t>(1, std::min<uint32_t>(c->n_active, (uint32_t)c->workers.size()));
+  const uint32_t W = active_workers(c);
   const uint32_t G = mq_usable(c) && c->pt_end > c->pt_begin ? std::min<uint32_t>(c->mq_nq, kMaxScanQueries) : 1;
   // contexts with tables: the table of every query -- what pirgpu_batch_set_tables left for this many queries, else the
   // table selected with pirgpu_query_use_table for all of them.  Every named table must be complete and free of zero
@@ -4374,7 +4323,7 @@ static void batch_run_impl_body(pirgpu_ctx* c, uint32_t count, const uint64_t* e
   if (!ext_sv) check_staged_keysets(c);
   if (c->ctm && c->d >= 2)   // every query's relinearisation key, before anything is queued
     for (uint32_t i = 0; i < count; ++i) {
-      const uint32_t slot = i < c->bs().batch_keysets.size() ? c->bs().batch_keysets[i] : 0;
+      const uint32_t slot = keyset_of(c, i);
       (void)relin_keys_for(c, &slot, 1);
     }
   ensure_packed(c);
@@ -4402,16 +4351,12 @@ static void batch_run_impl_body(pirgpu_ctx* c, uint32_t count, const uint64_t* e
     } else {
       for (uint32_t j0 = 0; j0 < n; j0 += kMaxMfmaQueries) {
         const uint32_t B = std::min<uint32_t>(kMaxMfmaQueries, n - j0);
-        BatchLane& ln = c->lanes[c->groups_run++ % c->lanes.size()];
-        Worker* members[kMaxMfmaQueries];
+        // every lane, and worker j0 + q itself as member q: it goes on with its own query on its own stream
+        const LaneClaim cl = claim_lane(c, (uint32_t)c->lanes.size(), B, 0, j0);
+        expand_group_on_lane(c, cl.ln, cl.members, B, base + j0, false, nullptr, order ? order + base + j0 : nullptr);
         for (uint32_t q = 0; q < B; ++q) {
-          members[q] = &c->workers[j0 + q];
-          HIP_TRY(hipStreamWaitEvent(ln.stream, members[q]->ev_done, 0));  // its selection vector is free again
-        }
-        expand_group_on_lane(c, ln, members, B, base + j0, false, nullptr, order ? order + base + j0 : nullptr);
-        for (uint32_t q = 0; q < B; ++q) {
-          HIP_TRY(hipEventRecord(members[q]->ev_expanded, ln.stream));
-          HIP_TRY(hipStreamWaitEvent(members[q]->stream, members[q]->ev_expanded, 0));
+          HIP_TRY(hipEventRecord(cl.members[q]->ev_expanded, cl.ln.stream));
+          HIP_TRY(hipStreamWaitEvent(cl.members[q]->stream, cl.members[q]->ev_expanded, 0));
         }
       }
     }
@@ -4450,7 +4395,7 @@ static void batch_run_impl_body(pirgpu_ctx* c, uint32_t count, const uint64_t* e
     }
     for (uint32_t j = 0; j < n; ++j) {
       Worker& w = c->workers[j];
-      w.keyset = oq(base + j) < c->bs().batch_keysets.size() ? c->bs().batch_keysets[oq(base + j)] : 0;
+      w.keyset = keyset_of(c, oq(base + j));
       post_scan_on_device(c, w);
       HIP_TRY(hipMemcpyAsync(reply_base(c) + (size_t)oq(base + j) * rwords, w.lvl[0], rwords * 8, hipMemcpyDeviceToDevice,
                              w.stream));
@@ -4482,7 +4427,7 @@ int pirgpu_batch_expand(pirgpu_ctx* c, uint32_t first, uint32_t count, uint64_t*
     if (!device_dst && count) return fail(c, PIRGPU_INVALID_ARGUMENT, "null buffer");
     const uint32_t nq = c->dim_sum / c->N + 1;
     const size_t qwords = (size_t)nq * c->ctw, svwords = (size_t)c->dim_sum * c->ctw;
-    const uint32_t W = std::max<uint32_t>(1, std::min<uint32_t>(c->n_active, (uint32_t)c->workers.size()));
+    const uint32_t W = active_workers(c);
     c->prof_cur = -1;
     check_staged_keysets(c);
     for (uint32_t i = 0; i < count; ++i) {
@@ -4492,7 +4437,7 @@ int pirgpu_batch_expand(pirgpu_ctx* c, uint32_t first, uint32_t count, uint64_t*
       HIP_TRY(hipMemcpyAsync(w.d_query, c->bs().d_bquery + (size_t)(first + i) * qwords, qwords * 8,
                              hipMemcpyDeviceToDevice, w.stream));
       w.staged_nq = nq;
-      w.keyset = first + i < c->bs().batch_keysets.size() ? c->bs().batch_keysets[first + i] : 0;
+      w.keyset = keyset_of(c, first + i);
       expand_query_to_sv(c, w, w.d_query, nq);
       HIP_TRY(hipMemcpyAsync(device_dst + (size_t)i * svwords, w.sv_ntt, svwords * 8, hipMemcpyDeviceToDevice,
                              w.stream));
@@ -4542,7 +4487,7 @@ static int batch_expand_packed_impl(pirgpu_ctx* c, uint32_t first_query, uint32_
       return fail(c, PIRGPU_INVALID_ARGUMENT, "invalid packed-exchange buffers or row cuts");
     for (uint32_t s = 0; s < n_ranks; ++s)
       if (row_cuts[s] > row_cuts[s + 1]) return fail(c, PIRGPU_INVALID_ARGUMENT, "row cuts must be non-decreasing");
-    const uint32_t W = std::max<uint32_t>(1, std::min<uint32_t>(c->n_active, (uint32_t)c->workers.size()));
+    const uint32_t W = active_workers(c);
     if (W < std::min<uint32_t>(count, kMaxMfmaQueries))
       return fail(c, PIRGPU_FAILED_PRECONDITION, "packed groups need min(count, 8) workers (pirgpu_set_concurrency)");
     ensure_lanes(c, true);
@@ -4555,13 +4500,9 @@ static int batch_expand_packed_impl(pirgpu_ctx* c, uint32_t first_query, uint32_
     uint32_t g = 0;
     for (uint32_t j0 = 0; j0 < count; j0 += kMaxMfmaQueries, ++g) {
       const uint32_t B = std::min<uint32_t>(kMaxMfmaQueries, count - j0);
-      const uint32_t li = (uint32_t)(c->groups_run++ % nl);
-      BatchLane& ln = c->lanes[li];
-      Worker* members[kMaxMfmaQueries];
-      for (uint32_t q = 0; q < B; ++q) {
-        members[q] = &c->workers[(li * G + q) % W];
-        HIP_TRY(hipStreamWaitEvent(ln.stream, members[q]->ev_done, 0));
-      }
+      const LaneClaim cl = claim_lane(c, nl, B, G);
+      BatchLane& ln = cl.ln;
+      Worker* const* members = cl.members;
       expand_group_on_lane(c, ln, members, B, first + j0);
       // column selectors (dimension 1) of the whole group -> one B-operand buffer
       MfmaPtrs sv{};
@@ -4576,9 +4517,7 @@ static int batch_expand_packed_impl(pirgpu_ctx* c, uint32_t first_query, uint32_
                                  members[q]->sv_ntt + (size_t)(c->sv_off[0] + r0) * ctw, (size_t)nr * ctw * 8,
                                  hipMemcpyDeviceToDevice, ln.stream));
       }
-      for (uint32_t q = 0; q < B; ++q) {  // the members' selection vectors are free once this lane got here
-        HIP_TRY(hipEventRecord(members[q]->ev_done, ln.stream));
-      }
+      release_lane(cl, false);
     }
     if (wait)
       for (BatchLane& ln : c->lanes) HIP_TRY(hipStreamSynchronize(ln.stream));
@@ -4616,14 +4555,10 @@ int pirgpu_batch_run_packed(pirgpu_ctx* c, const uint8_t* device_packed, uint32_
     ensure_batch_capacity(c, (uint32_t)count);
     c->prof_cur = -1;
     PackedInput pk{device_packed, device_rows, per_rank};
-    c->in_batch = true;
-    try {
+    {
+      InBatch in_batch(c);
       batch_run_mfma(c, (uint32_t)count, nullptr, &pk);
-    } catch (...) {
-      c->in_batch = false;
-      throw;
     }
-    c->in_batch = false;
     c->bs().batch_count = (uint32_t)count;
     c->bs().batch_valid = true;
     return PIRGPU_OK;
@@ -4659,20 +4594,6 @@ void check_cuts(pirgpu_ctx* c, const uint32_t* cuts, uint32_t n_ranks, SliceMap&
   }
 }
 
-void lane_after(pirgpu_ctx* c, hipStream_t lane, void* after) {
-  if (!after) return;
-  if (!c->ev_after) HIP_TRY(hipEventCreateWithFlags(&c->ev_after, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(c->ev_after, (hipStream_t)after));
-  HIP_TRY(hipStreamWaitEvent(lane, c->ev_after, 0));
-}
-
-void lane_then(BatchLane& ln, void* then) {
-  if (!then) return;
-  if (!ln.ev_join) HIP_TRY(hipEventCreateWithFlags(&ln.ev_join, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(ln.ev_join, ln.stream));
-  HIP_TRY(hipStreamWaitEvent((hipStream_t)then, ln.ev_join, 0));
-}
-
 void check_slots_ctx(pirgpu_ctx* c) {
   refuse_wide(c);
   refuse_tables(c);
@@ -4704,7 +4625,7 @@ int pirgpu_slots_expand_async(pirgpu_ctx* c, uint32_t first, uint32_t count, uin
     if (!c->bs().staged_count || (uint64_t)first + count > c->bs().staged_count)
       return fail(c, PIRGPU_INVALID_ARGUMENT, "query range outside the staged batch");
     if (!device_packed || !device_sv || count == 0) return fail(c, PIRGPU_INVALID_ARGUMENT, "null buffer");
-    const uint32_t W = std::max<uint32_t>(1, std::min<uint32_t>(c->n_active, (uint32_t)c->workers.size()));
+    const uint32_t W = active_workers(c);
     if (W < std::min<uint32_t>(count, kMaxMfmaQueries))
       return fail(c, PIRGPU_FAILED_PRECONDITION, "groups need min(count, 8) workers (pirgpu_set_concurrency)");
     ensure_lanes(c, true);
@@ -4719,23 +4640,17 @@ int pirgpu_slots_expand_async(pirgpu_ctx* c, uint32_t first, uint32_t count, uin
     uint32_t g = 0;
     for (uint32_t j0 = 0; j0 < count; j0 += kMaxMfmaQueries, ++g) {
       const uint32_t B = std::min<uint32_t>(kMaxMfmaQueries, count - j0);
-      BatchLane& ln = c->lanes[c->groups_run++ % nl];
-      const uint32_t li = (uint32_t)(&ln - c->lanes.data());
-      lane_after(c, ln.stream, after);
-      Worker* members[kMaxMfmaQueries];
-      for (uint32_t q = 0; q < B; ++q) {
-        members[q] = &c->workers[(li * G + q) % W];
-        HIP_TRY(hipStreamWaitEvent(ln.stream, members[q]->ev_done, 0));
-      }
+      const LaneClaim cl = claim_lane(c, nl, B, G, 0, after);
+      BatchLane& ln = cl.ln;
       uint64_t* sv_dst = device_sv + (size_t)j0 * svwords;
-      expand_group_on_lane(c, ln, members, B, first + j0, c->sel_f64, sv_dst);
+      expand_group_on_lane(c, ln, cl.members, B, first + j0, c->sel_f64, sv_dst);
       // the group's column selectors -> B-operand tiles, rank r's slots as piece [r][group g] of the send buffer
       MfmaPtrs sv{};
       for (uint32_t q = 0; q < B; ++q) sv.p[q] = sv_dst + (size_t)q * svwords + (size_t)c->sv_off[1] * ctw;
       for (uint32_t r = 0; r < n_ranks; ++r)
         map.off[r] = ((uint64_t)groups * map.cut[r] + (uint64_t)g * (map.cut[r + 1] - map.cut[r])) * slot_bytes;
       HIP_TRY(launch_sel_pack(ln.stream, c->dp, c->mg, sv, B, device_packed, c->scan_cols, kN, c->sel_f64, &map));
-      for (uint32_t q = 0; q < B; ++q) HIP_TRY(hipEventRecord(members[q]->ev_done, ln.stream));
+      release_lane(cl, false);
       lane_then(ln, then);
     }
     return PIRGPU_OK;
@@ -4753,10 +4668,8 @@ int pirgpu_slots_scan_async(pirgpu_ctx* c, const uint8_t* device_packed, uint32_
     ensure_packed(c);
     ensure_lanes(c, true);
     c->prof_cur = -1;
-    const uint32_t W = std::max<uint32_t>(1, std::min<uint32_t>(c->n_active, (uint32_t)c->workers.size()));
-    const uint32_t nl = lanes_in_use(c, std::min<uint32_t>(kMaxMfmaQueries, W));
-    BatchLane& ln = c->lanes[c->groups_run++ % nl];
-    lane_after(c, ln.stream, after);
+    const uint32_t nl = lanes_in_use(c, std::min<uint32_t>(kMaxMfmaQueries, active_workers(c)));
+    BatchLane& ln = claim_lane(c, nl, 0, 0, 0, after).ln;
     const uint32_t groups = (per_rank + kMaxMfmaQueries - 1) / kMaxMfmaQueries;
     const uint64_t piece = (uint64_t)c->nslots * c->mg.KG * c->mg.tile_bytes;      // my slots of one packed group
     const uint64_t qwords = (uint64_t)c->scan_rows * 2 * c->nslots;                // row sums of one query on my slots
@@ -4795,20 +4708,14 @@ int pirgpu_slots_finish_async(pirgpu_ctx* c, const uint64_t* device_rowsums, uin
       return fail(c, PIRGPU_INVALID_ARGUMENT, "invalid batch");
     ensure_lanes(c, true);
     c->prof_cur = -1;
-    const uint32_t W = std::max<uint32_t>(1, std::min<uint32_t>(c->n_active, (uint32_t)c->workers.size()));
-    const uint32_t nl = lanes_in_use(c, std::min<uint32_t>(kMaxMfmaQueries, W));
+    const uint32_t nl = lanes_in_use(c, std::min<uint32_t>(kMaxMfmaQueries, active_workers(c)));
     const size_t ctw = c->ctw, svwords = (size_t)c->dim_sum * ctw, rwords = (size_t)c->reply_cts * ctw;
     const uint32_t kN = c->k * c->N, RC = c->scan_rows * 2;
     const uint64_t words = (uint64_t)c->scan_rows * ctw;
-    struct Flag {
-      bool& f;
-      explicit Flag(bool& x) : f(x) { f = true; }
-      ~Flag() { f = false; }
-    } flag(c->in_batch);
+    InBatch in_batch(c);
     for (uint32_t j0 = 0; j0 < count; j0 += kMaxMfmaQueries) {
       const uint32_t B = std::min<uint32_t>(kMaxMfmaQueries, count - j0);
-      BatchLane& ln = c->lanes[c->groups_run++ % nl];
-      lane_after(c, ln.stream, after);
+      BatchLane& ln = claim_lane(c, nl, 0, 0, 0, after).ln;
       // rank h's block of the receive buffer holds [count][RC][slots of h]: the group's queries are rows j0 .. j0 + B of
       // it; the inverse transform of the row sums (database.cpp:250-254) gathers them from there (option
       // SLOTS_GATHER_NTT = 0: a separate assembly pass, then the plain in-place transform)
@@ -4819,14 +4726,11 @@ int pirgpu_slots_finish_async(pirgpu_ctx* c, const uint64_t* device_rowsums, uin
         HIP_TRY(c->ops->ntt_inv_gather(ln.stream, c->mode, c->dp, c->k, device_rowsums, ln.lvl[c->d - 1], map, RC, B, count, j0));
       else
         HIP_TRY(launch_slots_assemble(ln.stream, device_rowsums, ln.lvl[c->d - 1], map, RC, kN, B, words, count, j0));
-      uint64_t* lvl_ptrs[PIRGPU_MAX_DIMS];
-      for (uint32_t l = 0; l < c->d; ++l) lvl_ptrs[l] = ln.lvl[l];
-      lvl_ptrs[0] = device_replies + (size_t)j0 * rwords;
-      Stage sg{ln.stream, lvl_ptrs, ln.pt_buf, B, MfmaPtrs{}, false, &ln.up_scratch, &ln.up_scratch_words};
-      for (uint32_t q = 0; q < B; ++q) sg.sel.p[q] = device_sv + (size_t)(j0 + q) * svwords;
-      sg.sel_f64 = c->sel_f64;
-      sg.rows_inverted = gather;
-      post_scan_stage(c, sg, nullptr);
+      LaneStage ls(c, ln, B, device_replies + (size_t)j0 * rwords, nullptr);
+      for (uint32_t q = 0; q < B; ++q) ls.sg.sel.p[q] = device_sv + (size_t)(j0 + q) * svwords;
+      ls.sg.sel_f64 = c->sel_f64;
+      ls.sg.rows_inverted = gather;
+      post_scan_stage(c, ls.sg, nullptr);
       lane_then(ln, then);
     }
     return PIRGPU_OK;

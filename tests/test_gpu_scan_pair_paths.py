@@ -1,5 +1,5 @@
-"""The paired database pass (pir_amd/csrc/scan_mfma_pair.hip, run_pair in ctx.hip) on every path that reaches it and on
-every path that must not -- what tests/test_gpu_scan_pair.py leaves out:
+"""The paired database pass (pir_amd/csrc/scan_mfma_pair.hip, the two-half step of batch_run_mfma in ctx.hip) on
+every path that reaches it and on every path that must not -- what tests/test_gpu_scan_pair.py leaves out:
 
   A  moduli and rings   byte-form top digits that need the byte (37 / 38 / 39-bit primes), three data primes (the unit walk
                         crosses two modulus boundaries), N = 8192 (another shift from slot to modulus)
@@ -390,8 +390,8 @@ NO_PAIR = {
 @pytest.mark.parametrize("name", list(NO_PAIR))
 def test_contexts_that_keep_one_pass_per_group(name, monkeypatch):
     """Every term of may_pair (ctx.hip): 16 queries on 16 workers with the switch at 0 and at 2 queue the same database
-    passes, and both contexts answer what the mode's model answers -- run_pair knows nothing of tables, of the buffer
-    result_primes switches from, of planes or of ciphertext products.  One dimension: the int8 scan and its counter need
+    passes, and both contexts answer what the mode's model answers -- the paired pass (scan_pair_mfma in ctx.hip) knows
+    nothing of tables, of the buffer result_primes switches from, of planes or of ciphertext products.  One dimension: the int8 scan and its counter need
     d >= 2, the batch takes the 64-bit scan and SCAN_LAUNCHES stays where it is -- only the replies say anything there."""
     build, queries, want, run_kw, info, launches = NO_PAIR[name]()
     deltas = []

@@ -108,6 +108,47 @@ def test_single_queries_and_a_mixed_batch_under_two_key_sets(w3):
     db.close()
 
 
+def test_permuted_batch_downloads_its_replies_group_by_group(w3):
+    """pirgpu_batch_set_host_replies on a batch served in another order than it was submitted (ISSUE_BATCH: three groups,
+    served as 1 4 14 17 2 3 15 18 | 0 5 .. 11 | 12 13 16): every group downloads its own replies, one copy each, and
+    reports how many LEADING queries of the batch are complete with it -- 0, 12, 19.  What has been reported is in the
+    host buffer before the batch as a whole is; the replies are those of the plain fetch (pinned to the oracle by
+    test_single_queries_and_a_mixed_batch_under_two_key_sets)."""
+    import ctypes as C
+    w = w3
+    db, srv = w.server()
+    srv.set_concurrency(16)
+    batch = len(ISSUE_BATCH)
+    queries = np.stack([w.query(index_of(i, 3000)) for i in range(batch)])
+    srv.stage_batch(queries, tables=ISSUE_BATCH)
+    srv.run_batch()
+    plain = srv.fetch_batch()
+    n = db.reply_ct_count()
+    lib, h = srv.lib, db.handle
+    host = lib.pirgpu_host_reply_buffer(h, batch)
+    assert host
+    view = np.ctypeslib.as_array(C.cast(host, C.POINTER(C.c_uint64)), shape=(batch, n, 2, srv.k, srv.N))
+    assert view.shape == plain.shape
+    view[:] = 0
+    assert lib.pirgpu_batch_set_host_replies(h, C.c_void_p(host), batch * n) == 0
+    srv.stage_batch(queries, tables=ISSUE_BATCH)
+    srv.run_batch()
+    seen, ready = [], C.c_uint32(0)
+    for _ in range(3):                                             # one report per group
+        assert lib.pirgpu_batch_next_host_replies(h, C.byref(ready)) == 0
+        assert ready.value >= (seen[-1] if seen else 0)
+        assert np.array_equal(view[:ready.value], plain[:ready.value])
+        seen.append(ready.value)
+    assert seen == [0, 12, 19]
+    assert lib.pirgpu_batch_next_host_replies(h, C.byref(ready)) == 0 and ready.value == batch   # nothing left: the total
+    cnt = C.c_uint64(0)
+    assert lib.pirgpu_batch_fetch(h, C.cast(host, C.POINTER(C.c_uint64)), batch * n, C.byref(cnt)) == 0
+    assert cnt.value == batch * n
+    assert np.array_equal(view, plain)
+    assert lib.pirgpu_batch_set_host_replies(h, None, 0) == 0
+    db.close()
+
+
 def test_many_tiny_tables_take_one_launch_per_group():
     """T = 12, 16 queries on 12 distinct tables: served as [0 0 1 1 2 2 3 3][4 .. 11] -- a group of 4 runs and a group of
     8 runs of one query.  One database-pass launch per group; with TABLES_ONE_LAUNCH = 0 one per run; identical replies."""
