@@ -84,6 +84,12 @@ int pirclient_galois_key(const pirclient* c, uint32_t elt, uint64_t* key_out);
  * repeat once per dimension).  reply [n_cts][2][k][N] -> plaintext_out [N].  With wide items (plaintexts_per_item > 1)
  * a whole reply of planes x that many ciphertexts gives plaintext_out [planes][N], one plane's ciphertexts one [N]. */
 int pirclient_process_reply(pirclient* c, const uint64_t* reply, size_t n_cts, uint64_t* plaintext_out);
+/* Packed replies (pirgpu.h, PIRGPU_CREATE_PACKED_REPLIES): pirclient_load_response and pirclient_process_response accept
+ * a reply ciphertext in either form, as SEAL saves it or packed (inner array header with compression byte 0x80), told
+ * apart per ciphertext; packed data that decodes to a coefficient >= its modulus is InvalidArgument.
+ * pirclient_unpack_reply: packed [n_cts][packed words] (what a packed context's fetch returns; 2 * sum_j N w_j / 64 words
+ * each over the reply's moduli, w_j = bit length of q_j - 1) -> reply_out [n_cts][2][r][N], with the same range check. */
+int pirclient_unpack_reply(pirclient* c, const uint64_t* packed, size_t n_cts, uint64_t* reply_out);
 /* expected reply size: (2 * ExpansionRatio)^(d-1) (client.cpp:224-226), times params.plaintexts_per_item */
 uint64_t pirclient_reply_ct_count(const pirclient* c);
 

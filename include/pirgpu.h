@@ -182,6 +182,20 @@ int pirgpu_create(const pirgpu_params* params, pirgpu_ctx** out);
  * refused; d = 1 and the row sums are unchanged.  Counter option "ct_relins" (get / set like "ct_blocks", both forms of
  * the mode): the ciphertexts the upper levels have key-switched so far -- pairs, or rows x queries here. */
 #define PIRGPU_CREATE_CT_DEFERRED 8u
+/* PIRGPU_CREATE_PACKED_REPLIES: replies leave the device at the bit width of their moduli instead of 64 bits a residue
+ * (not in the reference).  For modulus q_j the width is w_j = bit length of q_j - 1; polynomial
+ * (c, j) of a reply ciphertext [2][r][N] (r = result_primes or k) becomes a little-endian bit stream of N w_j bits -- bit b
+ * of coefficient i is stream bit i w_j + b -- stored as N w_j / 64 little-endian words, and a packed ciphertext is its 2 r
+ * polynomials in the order (c, j).  The reply BEFORE packing is bit for bit what the context produces without the flag;
+ * count, order and plane-major layout of the ciphertexts stay.  On such a context pirgpu_reply_ct_words is the packed
+ * word count, and every fetch, download, host-reply and reply-buffer path moves packed words (capacities stay in
+ * ciphertexts); pirgpu_reply_unpack, or pirclient_unpack_reply, gives the residues back.  On the wire a packed reply
+ * ciphertext carries compression byte 0x80 in its inner array header: the client must come from this
+ * tree.  Allowed with wide items, tables, result_primes, PIRGPU_CREATE_STREAMED_DB, every ring degree and d = 1, 2, 3.
+ * One GPU: InvalidArgument at create with a row or slot shard or PIRGPU_CREATE_CT_MULTIPLY; the packed and slot-sharded
+ * entry points, pirgpu_reduce_fixup* and the device reply copies are FailedPrecondition.  Without the flag no kernel is
+ * launched and no buffer allocated for it. */
+#define PIRGPU_CREATE_PACKED_REPLIES 16u
 int pirgpu_create_ex(const pirgpu_params* params, uint32_t flags, pirgpu_ctx** out);
 void pirgpu_destroy(pirgpu_ctx* ctx);
 /* Message of the calling thread's last failed call on this context (falls back to the context's last
@@ -348,11 +362,21 @@ uint64_t pirgpu_reply_ct_count(const pirgpu_ctx* ctx);
 /* CiphertextReencoder::ExpansionRatio (reference ct_reencoder.cpp:29-38); over the first result_primes primes when set */
 uint32_t pirgpu_expansion_ratio(const pirgpu_ctx* ctx);
 /* Words of one REPLY ciphertext: 2 * result_primes * N, or 2 * k * N when result_primes is 0.  Every reply buffer at
- * this ABI is [ciphertext][2][r][N], compact. */
+ * this ABI is [ciphertext][2][r][N], compact.  (PIRGPU_CREATE_PACKED_REPLIES: the packed word count, [ciphertext][words].) */
 uint64_t pirgpu_reply_ct_words(const pirgpu_ctx* ctx);
 /* Test hook for the modulus switch: cts = n coefficient-form ciphertexts [2][k][N] of canonical residues, out =
  * [n][2][r][N]; any 1 <= r < k on any context, whatever its result_primes (the launcher of the query path). */
 int pirgpu_mod_switch(pirgpu_ctx* ctx, const uint64_t* cts, uint64_t n, uint32_t r, uint64_t* out);
+/* Packed replies (PIRGPU_CREATE_PACKED_REPLIES): 1 on a context created with the flag, else 0; and the words of one reply
+ * ciphertext before packing, 2 * r * N (== pirgpu_reply_ct_words without the flag). */
+int pirgpu_reply_packing(const pirgpu_ctx* ctx);
+uint64_t pirgpu_reply_unpacked_words(const pirgpu_ctx* ctx);
+/* Test hooks for packed replies, on any context, for any 1 <= r <= k (the first r data primes): cts = n ciphertexts
+ * [2][r][N] of canonical residues (InvalidArgument otherwise) through the device's pack kernel to out = [n][packed words];
+ * and packed -> out [n][2][r][N] through the host's unpack (what a client runs; InvalidArgument if a coefficient decodes
+ * to a value that is not below its modulus). */
+int pirgpu_reply_pack(pirgpu_ctx* ctx, const uint64_t* cts, uint64_t n, uint32_t r, uint64_t* out);
+int pirgpu_reply_unpack(pirgpu_ctx* ctx, const uint64_t* packed, uint64_t n, uint32_t r, uint64_t* out);
 
 /* Ciphertext-multiplication mode, host only (no context, no device; like pirgpu_plan_table_runs): the auxiliary base a
  * context of this chain multiplies in -- the k + 2 largest primes == 1 (mod 2N) below 2^bits, bits = the size of the

@@ -13,11 +13,12 @@ SOURCES = ["kernels.hip", "scan_mfma.hip", "scan_mfma_pair.hip", "ctx.hip", "wir
            "ctmult.hip",             # ciphertext-multiplication mode: lift, tensor, scale, accumulate
            "ctmult_rowsum.hip",      # ... its deferred rounding: the tensor summed over the children of a row
            "ctmult_shared.hip",      # ... its shared selectors: a level's selectors lifted and transformed once
-           "seed_expand.hip"]        # seed-compressed keys: the c1 halves re-sampled on the device (BLAKE2Xb)
+           "seed_expand.hip",        # seed-compressed keys: the c1 halves re-sampled on the device (BLAKE2Xb)
+           "reply_pack.hip"]         # packed replies: residues to the bit width of their moduli where a reply is produced
 NTT_SOURCE = "ntt_kernels.hip"      # compiled once per ring degree (-DPIRGPU_LOGN)
 NTT_LOGNS = [11, 12, 13, 14]
 NTT_PACK_BYTES = [5, 6, 7]          # ... and once per width of the packed key-switch intermediates (-DPIRGPU_PACK_BYTES)
-HEADERS = ["device_params.h", "env_gate.h", "options.h", "batch_plan.h", "kernels.h", "host_math.h", "wire.h", "wire_codec.h", "arith.h", "ntt_core.h", "ctmult.h", "ctmult_convert.h", "scan_mfma_body.inc", NTT_SOURCE, os.path.join("..", "..", "include", "pirgpu.h")]
+HEADERS = ["device_params.h", "env_gate.h", "options.h", "batch_plan.h", "kernels.h", "host_math.h", "wire.h", "wire_codec.h", "arith.h", "ntt_core.h", "ctmult.h", "ctmult_convert.h", "reply_pack.h", "scan_mfma_body.inc", NTT_SOURCE, os.path.join("..", "..", "include", "pirgpu.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"] + \
     os.environ.get("PIRGPU_BUILD_DEFS", "").split()      # A/B builds of compile-time choices (tools/experiments/r04_ab_ept.sh)
@@ -71,7 +72,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
 CLIENT_LIB = os.path.join(HERE, "libpirclient.so")
 CLIENT_SOURCES = ["client.cpp", "wire_codec.cpp"]
-CLIENT_HEADERS = ["host_math.h", "wire_codec.h", os.path.join("..", "..", "include", "pirgpu.h"),
+CLIENT_HEADERS = ["host_math.h", "wire_codec.h", "reply_pack.h", os.path.join("..", "..", "include", "pirgpu.h"),
                   os.path.join("..", "..", "include", "pirclient.h")]
 CXX = os.environ.get("CXX", "g++")
 

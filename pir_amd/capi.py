@@ -12,6 +12,7 @@ OK, INVALID_ARGUMENT, FAILED_PRECONDITION, UNIMPLEMENTED, INTERNAL = 0, 3, 9, 12
 CREATE_STREAMED_DB = 1          # pirgpu_create_ex flags
 CREATE_CT_MULTIPLY = 4
 CREATE_CT_DEFERRED = 8
+CREATE_PACKED_REPLIES = 16      # replies at the bit width of their moduli
 
 u64p = C.POINTER(C.c_uint64)
 u8p = C.POINTER(C.c_uint8)
@@ -174,6 +175,10 @@ SIGNATURES = {
     "pirgpu_expansion_ratio": (C.c_uint32, [C.c_void_p]),
     "pirgpu_reply_ct_words": (C.c_uint64, [C.c_void_p]),
     "pirgpu_mod_switch": (C.c_int, [C.c_void_p, u64p, C.c_uint64, C.c_uint32, u64p]),
+    "pirgpu_reply_packing": (C.c_int, [C.c_void_p]),
+    "pirgpu_reply_unpacked_words": (C.c_uint64, [C.c_void_p]),
+    "pirgpu_reply_pack": (C.c_int, [C.c_void_p, u64p, C.c_uint64, C.c_uint32, u64p]),
+    "pirgpu_reply_unpack": (C.c_int, [C.c_void_p, u64p, C.c_uint64, C.c_uint32, u64p]),
     "pirgpu_ctmult_plan": (C.c_int, [C.c_uint32, C.c_uint32, u64p, C.c_uint64, C.c_uint64, u64p, C.POINTER(C.c_uint32)]),
     "pirgpu_ctmult_plan_terms": (C.c_int, [C.c_uint32, C.c_uint32, u64p, C.c_uint64, C.c_uint64, C.c_uint64, u64p,
                                            C.POINTER(C.c_uint32)]),
@@ -274,6 +279,7 @@ CLIENT_SIGNATURES = {
     "pirclient_galois_key": (C.c_int, [C.c_void_p, C.c_uint32, u64p]),
     "pirclient_process_reply": (C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p]),
     "pirclient_reply_ct_count": (C.c_uint64, [C.c_void_p]),
+    "pirclient_unpack_reply": (C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p]),
     "pirclient_encrypt": (C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p]),
     "pirclient_decrypt": (C.c_int, [C.c_void_p, u64p, u64p]),
     "pirclient_noise_budget": (C.c_int, [C.c_void_p, u64p, C.POINTER(C.c_int)]),

@@ -99,12 +99,32 @@ class PIRClient:
         """serialization.cpp:32-42 over every Response.reply -> [n_replies, reply_ct_count, 2, reply_k, N] uint64."""
         buf = (C.c_uint8 * max(1, len(response))).from_buffer_copy(response or b"\0")
         # a reply is at least one ciphertext object: bound the output by the response's size
-        per = self.reply_ct_count * 2 * self.reply_k * self.N
+        # (the smaller of its two forms: a reply from a server with packed replies holds packed_reply_ct_words a ciphertext)
+        per = self.reply_ct_count * self.packed_reply_ct_words
         cap = max(1, min(max_replies, len(response) // (per * 8) + 1))
         out = np.empty((cap, self.reply_ct_count, 2, self.reply_k, self.N), dtype=np.uint64)
         n = C.c_size_t()
         self._check(self.lib.pirclient_load_response(self._h, buf, len(response), _ptr(out), cap, C.byref(n)))
         return out[:n.value]
+
+    @property
+    def packed_reply_ct_words(self) -> int:
+        """Words of one reply ciphertext as a server with packed replies hands it out."""
+        q = [int(v) for v in self.params.encryption_parameters.coeff_modulus[:self.reply_k]]
+        return 2 * sum(self.N * (v - 1).bit_length() // 64 for v in q)
+
+    def unpack_reply(self, packed) -> np.ndarray:
+        """pirclient_unpack_reply: packed reply ciphertexts [..., packed_reply_ct_words] (what a server with packed replies
+        returns at the residue level) -> [..., 2, reply_k, N]; a coefficient that is not below its modulus is an error."""
+        a = _u64(packed)
+        if a.ndim < 1 or a.shape[-1] != self.packed_reply_ct_words:
+            raise PirGpuError(3, "packed reply ciphertexts must have %d words each, got shape %s"
+                              % (self.packed_reply_ct_words, list(a.shape)))
+        n = a.size // a.shape[-1]
+        out = np.empty(a.shape[:-1] + (2, self.reply_k, self.N), dtype=np.uint64)
+        if n:
+            self._check(self.lib.pirclient_unpack_reply(self._h, _ptr(a), n, _ptr(out)))
+        return out
 
     def ProcessResponse(self, indexes: Sequence[int], response: bytes) -> List[bytes]:
         """client.cpp:160-185: serialized pir.Response -> one item per index."""

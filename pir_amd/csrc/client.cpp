@@ -810,7 +810,7 @@ struct pirclient {
   }
   void reply_plaintext(const std::pair<const uint8_t*, size_t>& msg, uint64_t* pt) const {
     std::vector<uint64_t> cts;
-    const uint32_t n = wire::load_query(rsh, msg.first, msg.second, cts);
+    const uint32_t n = wire::load_reply(rsh, msg.first, msg.second, cts);
     process_reply(cts.data(), n, pt);
   }
 };
@@ -911,7 +911,7 @@ int pirclient_load_response(pirclient* c, const uint8_t* response, size_t respon
     const size_t per = (size_t)c->reply_ct_count() * c->reply_ct_words();
     std::vector<uint64_t> cts;
     for (size_t i = 0; i < replies.size(); ++i) {
-      const uint32_t n = wire::load_query(c->rsh, replies[i].first, replies[i].second, cts);
+      const uint32_t n = wire::load_reply(c->rsh, replies[i].first, replies[i].second, cts);
       if (n != c->reply_ct_count()) throw Err{PIRGPU_INVALID_ARGUMENT, "Number of ciphertexts in reply does not match expected"};
       memcpy(replies_out + i * per, cts.data(), per * 8);
     }
@@ -938,7 +938,7 @@ int pirclient_process_response(pirclient* c, const uint64_t* indexes, size_t n_i
         continue;
       }
       // wide item: plane j of the reply decodes to bytes [j B, min((j + 1) B, item)) of it
-      const uint32_t n = wire::load_query(c->rsh, replies[i].first, replies[i].second, cts);
+      const uint32_t n = wire::load_reply(c->rsh, replies[i].first, replies[i].second, cts);
       if (n != c->reply_ct_count())
         throw Err{PIRGPU_INVALID_ARGUMENT, "Number of ciphertexts in reply does not match expected"};
       const uint64_t B = c->plane_bytes(), R = c->plane_reply_ct_count();
@@ -964,6 +964,16 @@ int pirclient_process_response_integer(pirclient* c, const uint8_t* response, si
       out[i] = c->decode_int64(pt.data());
     }
     *n_out = replies.size();
+  });
+}
+
+int pirclient_unpack_reply(pirclient* c, const uint64_t* packed, size_t n_cts, uint64_t* reply_out) {
+  if (!c || ((!packed || !reply_out) && n_cts)) return PIRGPU_INVALID_ARGUMENT;
+  return guarded(c, [&] {
+    const size_t pw = rpk::ct_words(c->rsh.N, c->rsh.q, c->rsh.k);
+    for (size_t i = 0; i < n_cts; ++i)
+      if (!rpk::unpack_ct(packed + i * pw, c->rsh.N, c->rsh.q, c->rsh.k, reply_out + i * c->reply_ct_words()))
+        throw Err{PIRGPU_INVALID_ARGUMENT, "packed reply holds a coefficient that is not below its modulus"};
   });
 }
 

@@ -43,6 +43,7 @@
 #include "host_math.h"
 #include "kernels.h"
 #include "options.h"
+#include "reply_pack.h"
 #include "wire.h"
 
 using namespace pirgpu;
@@ -104,6 +105,7 @@ struct Worker {
   const uint64_t* sv_rows = nullptr; // packed multi-GPU exchange: only this shard's dimension-0 selectors, local index
   std::vector<uint64_t*> lvl;  // per level results; lvl[0] = reply
   uint64_t* last = nullptr;    // result_primes: level 0 at k primes, before the compact switch writes the reply to lvl[0]
+                               // (packed replies: level 0 before the pack kernel does)
   uint64_t* pt_buf = nullptr;
   uint64_t* scan_part = nullptr;
   uint64_t* up_scratch = nullptr;    // split upper level (large rings): transformed plaintexts of one block of children
@@ -251,7 +253,11 @@ struct pirgpu_ctx {
   uint32_t N = 0, logN = 0, k = 0, d = 0;
   size_t ctw = 0;  // words per ciphertext
   uint32_t rp = 0;   // pirgpu_params.result_primes (0: level results and replies stay at k primes)
-  size_t rctw = 0;   // words per REPLY ciphertext: 2 rp N, or ctw
+  size_t rctw = 0;   // words per REPLY ciphertext: 2 rp N, or ctw -- packed replies: the packed word count (rpa.ct_words)
+  // PIRGPU_CREATE_PACKED_REPLIES: level 0 lands in the owner's `last` buffer (as with
+  // result_primes) and reply_pack_kernel writes the reply, at the bit width of its moduli, where it went before
+  bool pack = false;
+  ReplyPackArgs rpa{};   // ... its argument block: the first (rp ? rp : k) residues of [2][k][N] ciphertexts
   uint32_t dims[PIRGPU_MAX_DIMS]{};
   uint64_t stride[PIRGPU_MAX_DIMS + 1]{};  // plaintexts under one node of level l
   uint32_t sv_off[PIRGPU_MAX_DIMS + 1]{};  // selection-vector offset of dimension l
@@ -941,7 +947,7 @@ void alloc_worker(pirgpu_ctx* c, Worker& w) {
   w.d_query = c->dalloc<uint64_t>((size_t)(c->dim_sum / c->N + 1) * ctw);
   w.lvl.assign(c->d, nullptr);
   for (uint32_t l = 0; l < c->d; ++l) w.lvl[l] = c->dalloc<uint64_t>(c->lvl_cts[l] * ctw);
-  if (c->rp) w.last = c->dalloc<uint64_t>(c->lvl_cts[0] * ctw);
+  if (c->rp || c->pack) w.last = c->dalloc<uint64_t>(c->lvl_cts[0] * ctw);
   if (c->pt_words) w.pt_buf = c->dalloc<uint64_t>(c->pt_words);
   const uint32_t parts = std::max<uint32_t>(c->scan_nsplit, c->mfma_on ? c->mg.nchunks : 1);
   if (parts > 1) w.scan_part = c->dalloc<uint64_t>((size_t)parts * std::max<uint32_t>(c->scan_rows, 1) * ctw);
@@ -1277,8 +1283,16 @@ void refuse_ctm(const pirgpu_ctx* c) {
                                            "entry points do not serve it"};
 }
 
-// d = 1 with result_primes: the scan's sums are level 0 at k primes -- they go to the worker's `last` buffer
-uint64_t* scan_out(const pirgpu_ctx* c, Worker& w) { return c->rp && c->d == 1 ? w.last : w.lvl[c->d - 1]; }
+// Packed replies serve one GPU and hand out packed words: what sums replies over shards, or copies them to a device
+// buffer whose reader expects residues, does not serve them.
+void refuse_packed(const pirgpu_ctx* c) {
+  if (c->pack)
+    throw Fail{PIRGPU_FAILED_PRECONDITION, "this context packs its replies (PIRGPU_CREATE_PACKED_REPLIES): the multi-GPU "
+                                           "entry points and the device reply copies do not serve it"};
+}
+
+// d = 1 with result_primes or packed replies: the scan's sums are level 0 at k primes -- they go to the worker's `last` buffer
+uint64_t* scan_out(const pirgpu_ctx* c, Worker& w) { return (c->rp || c->pack) && c->d == 1 ? w.last : w.lvl[c->d - 1]; }
 
 void refuse_slot_shard(const pirgpu_ctx* c) {
   if (c->slot_sharded)
@@ -1727,18 +1741,20 @@ void post_scan_stage(pirgpu_ctx* c, const Stage& sg, Worker* profiled) {
   const size_t ctw = c->ctw;
   const uint64_t shard_pts = matrix_pts(c);
   hipStream_t st = sg.stream;
-  if (c->rp && !sg.last) throw Fail{PIRGPU_INTERNAL, "result_primes without a level-0 buffer"};
-  // level l's result at k primes: lvl[l], or -- result_primes, level 0 -- the owner's `last` buffer, from where the
-  // compact switch writes the reply to lvl[0]
-  auto level = [&](uint32_t l) { return c->rp && l == 0 ? sg.last : sg.lvl[l]; };
+  if ((c->rp || c->pack) && !sg.last) throw Fail{PIRGPU_INTERNAL, "result_primes / packed replies without a level-0 buffer"};
+  // level l's result at k primes: lvl[l], or -- result_primes or packed replies, level 0 -- the owner's `last` buffer,
+  // from where the compact switch (or the pack kernel) writes the reply to lvl[0]
+  auto level = [&](uint32_t l) { return (c->rp || c->pack) && l == 0 ? sg.last : sg.lvl[l]; };
   // result_primes: every level result is switched right after its inverse transform (all flavours leave canonical u64
   // residues there: Encode reads them as such) -- in place below the reply, compact for the reply itself
   auto switch_level = [&](uint32_t l) {
     if (!c->rp) return;
     const uint64_t qstride = c->lvl_cts[l] * ctw;
-    if (l == 0)
+    if (l == 0 && !c->pack)
       HIP_TRY(launch_mod_switch(st, c->dp, sg.last, sg.lvl[0], c->lvl_cts[0], k, c->rp, N, true, sg.n, qstride,
                                 c->reply_cts * c->rctw));
+    else if (l == 0)   // packed replies: switched where it lies (stride k kept); the pack kernel reads the first rp residues
+      HIP_TRY(launch_mod_switch(st, c->dp, sg.last, sg.last, c->lvl_cts[0], k, c->rp, N, false, sg.n, qstride, qstride));
     else
       HIP_TRY(launch_mod_switch(st, c->dp, sg.lvl[l], sg.lvl[l], c->lvl_cts[l], k, c->rp, N, false, sg.n, qstride, qstride));
   };
@@ -1827,6 +1843,9 @@ void post_scan_stage(pirgpu_ctx* c, const Stage& sg, Worker* profiled) {
     C *= c->E;
   }
   if (d == 1 && profiled) record(c, *profiled, PH_FINAL);
+  // packed replies: once per query or group, on the stream that produced level 0, to where the reply went before
+  if (c->pack)
+    HIP_TRY(launch_reply_pack(st, c->rpa, sg.last, sg.lvl[0], c->lvl_cts[0], sg.n, c->lvl_cts[0] * ctw, c->reply_cts * c->rctw));
 }
 
 // Everything after the scan for one worker's query: inverse NTT of the row sums and the upper recursion levels
@@ -1897,11 +1916,20 @@ int pirgpu_create_ex(const pirgpu_params* p, uint32_t flags, pirgpu_ctx** out) {
     return code;
   };
   try {
-    if (flags & ~(PIRGPU_CREATE_STREAMED_DB | PIRGPU_CREATE_CT_MULTIPLY | PIRGPU_CREATE_CT_DEFERRED))
+    if (flags & ~(PIRGPU_CREATE_STREAMED_DB | PIRGPU_CREATE_CT_MULTIPLY | PIRGPU_CREATE_CT_DEFERRED | PIRGPU_CREATE_PACKED_REPLIES))
       return bail(PIRGPU_INVALID_ARGUMENT, "unknown pirgpu_create_ex flags " + std::to_string(flags));
     c->streamed = (flags & PIRGPU_CREATE_STREAMED_DB) != 0;
     c->ctm = (flags & PIRGPU_CREATE_CT_MULTIPLY) != 0;
     c->ctm_deferred = (flags & PIRGPU_CREATE_CT_DEFERRED) != 0;
+    c->pack = (flags & PIRGPU_CREATE_PACKED_REPLIES) != 0;
+    if (c->pack && c->ctm)
+      return bail(PIRGPU_INVALID_ARGUMENT, "PIRGPU_CREATE_PACKED_REPLIES with PIRGPU_CREATE_CT_MULTIPLY is not supported");
+    if (c->pack && (p->shard_begin || p->shard_end))
+      return bail(PIRGPU_INVALID_ARGUMENT, "PIRGPU_CREATE_PACKED_REPLIES is served by one GPU: a row shard (shard_begin / "
+                                           "shard_end) is not supported (packed words do not sum over shards)");
+    if (c->pack && (p->slot_begin || p->slot_end))
+      return bail(PIRGPU_INVALID_ARGUMENT, "PIRGPU_CREATE_PACKED_REPLIES is served by one GPU: a slot shard (slot_begin / "
+                                           "slot_end) is not supported");
     if (c->ctm_deferred && !c->ctm)
       return bail(PIRGPU_INVALID_ARGUMENT, "PIRGPU_CREATE_CT_DEFERRED needs PIRGPU_CREATE_CT_MULTIPLY (it is a form of that mode)");
     c->prm = *p;
@@ -2036,6 +2064,10 @@ int pirgpu_create_ex(const pirgpu_params* p, uint32_t flags, pirgpu_ctx** out) {
       return bail(PIRGPU_INVALID_ARGUMENT, "result_primes > 0 is served by one GPU: modulus switching does not commute with "
                                            "the sum over row or slot shards");
     c->rctw = c->rp ? (size_t)2 * c->rp * N : c->ctw;
+    if (c->pack) {
+      c->rpa = reply_pack_args(N, p->coeff_modulus, c->rp ? c->rp : k, k);
+      c->rctw = c->rpa.ct_words;
+    }
     c->device = p->device;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
@@ -2257,6 +2289,58 @@ int pirgpu_mod_switch(pirgpu_ctx* c, const uint64_t* cts, uint64_t n, uint32_t r
     return PIRGPU_OK;
   });
 }
+
+int pirgpu_reply_packing(const pirgpu_ctx* c) { return c && c->pack ? 1 : 0; }
+uint64_t pirgpu_reply_unpacked_words(const pirgpu_ctx* c) { return c ? (uint64_t)2 * (c->rp ? c->rp : c->k) * c->N : 0; }
+
+// Test hooks of packed replies (any context): n ciphertexts [2][r][N] over the first r data primes through the device's
+// pack kernel, and back through the host's unpack (reply_pack.h -- what a client runs).
+int pirgpu_reply_pack(pirgpu_ctx* c, const uint64_t* cts, uint64_t n, uint32_t r, uint64_t* out) {
+  return guarded(c, [&]() -> int {
+    if ((!cts || !out) && n) return fail(c, PIRGPU_INVALID_ARGUMENT, "null buffer");
+    if (r < 1 || r > c->k) return fail(c, PIRGPU_INVALID_ARGUMENT, "r must be in [1, num_data_primes]");
+    if (!n) return PIRGPU_OK;
+    const uint32_t N = c->N;
+    for (uint64_t i = 0; i < n * 2 * r; ++i) {   // the kernel packs canonical residues: a wider value would spill into its neighbour
+      const uint64_t q = c->prm.coeff_modulus[i % r];
+      for (uint32_t e = 0; e < N; ++e)
+        if (cts[i * N + e] >= q) return fail(c, PIRGPU_INVALID_ARGUMENT, "residue out of range (not below its modulus)");
+    }
+    const ReplyPackArgs args = reply_pack_args(N, c->prm.coeff_modulus, r, r);
+    const uint64_t step = 65535 / (2 * r);       // ciphertexts per launch (grid.y)
+    const size_t in_ct = (size_t)2 * r * N, in_words = (size_t)std::min(n, step) * in_ct,
+                 out_words = (size_t)std::min(n, step) * args.ct_words;
+    uint64_t* dev = nullptr;
+    HIP_TRY(hipMalloc((void**)&dev, (in_words + out_words) * 8));
+    try {
+      for (uint64_t at = 0; at < n; at += step) {
+        const uint64_t m = std::min(step, n - at);
+        HIP_TRY(hipMemcpyAsync(dev, cts + at * in_ct, m * in_ct * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(launch_reply_pack(c->stream, args, dev, dev + in_words, m));
+        HIP_TRY(hipMemcpyAsync(out + at * args.ct_words, dev + in_words, m * args.ct_words * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+      }
+    } catch (...) {
+      (void)hipFree(dev);
+      throw;
+    }
+    HIP_TRY(hipFree(dev));
+    return PIRGPU_OK;
+  });
+}
+
+int pirgpu_reply_unpack(pirgpu_ctx* c, const uint64_t* packed, uint64_t n, uint32_t r, uint64_t* out) {
+  return guarded(c, [&]() -> int {
+    if ((!packed || !out) && n) return fail(c, PIRGPU_INVALID_ARGUMENT, "null buffer");
+    if (r < 1 || r > c->k) return fail(c, PIRGPU_INVALID_ARGUMENT, "r must be in [1, num_data_primes]");
+    const size_t pw = rpk::ct_words(c->N, c->prm.coeff_modulus, r);
+    for (uint64_t i = 0; i < n; ++i)
+      if (!rpk::unpack_ct(packed + i * pw, c->N, c->prm.coeff_modulus, r, out + i * 2 * r * c->N))
+        return fail(c, PIRGPU_INVALID_ARGUMENT, "packed reply holds a coefficient that is not below its modulus");
+    return PIRGPU_OK;
+  });
+}
+
 int pirgpu_ctmult_plan(uint32_t N, uint32_t k, const uint64_t* coeff_modulus, uint64_t special_prime, uint64_t plain_modulus,
                        uint64_t* aux_primes, uint32_t* n_aux) {
   return pirgpu_ctmult_plan_terms(N, k, coeff_modulus, special_prime, plain_modulus, 1, aux_primes, n_aux);
@@ -3652,6 +3736,7 @@ uint64_t* pirgpu_reply_device_ptr(pirgpu_ctx* c) { return (c && c->ws_ready) ? c
 int pirgpu_reply_copy_to_device(pirgpu_ctx* c, uint64_t* dst, uint64_t cap) {
   return guarded(c, [&]() -> int {
     refuse_switched(c);
+    refuse_packed(c);
     refuse_ctm(c);
     if (c->workers.empty()) return fail(c, PIRGPU_FAILED_PRECONDITION, "no query has been run");
     Worker& w = c->workers[0];
@@ -3934,7 +4019,7 @@ static void ensure_lanes(pirgpu_ctx* c, bool with_expansion_buffers) {
     for (BatchLane& ln : c->lanes) {
       ln.lvl.assign(c->d, nullptr);
       for (uint32_t l = 0; l < c->d; ++l) ln.lvl[l] = c->dalloc<uint64_t>((size_t)kMaxMfmaQueries * c->lvl_cts[l] * c->ctw);
-      if (c->rp) ln.last = c->dalloc<uint64_t>((size_t)kMaxMfmaQueries * c->lvl_cts[0] * c->ctw);
+      if (c->rp || c->pack) ln.last = c->dalloc<uint64_t>((size_t)kMaxMfmaQueries * c->lvl_cts[0] * c->ctw);
       if (c->pt_words) ln.pt_buf = c->dalloc<uint64_t>((size_t)kMaxMfmaQueries * c->pt_words);
       if (c->mg.nchunks > 1)
         ln.scan_part = c->dalloc<uint64_t>((size_t)kMaxMfmaQueries * c->mg.nchunks * std::max<uint32_t>(c->scan_rows, 1) * c->ctw);
@@ -4477,6 +4562,7 @@ static int batch_expand_packed_impl(pirgpu_ctx* c, uint32_t first_query, uint32_
     refuse_wide(c);
     refuse_tables(c);
     refuse_switched(c);
+    refuse_packed(c);
     refuse_ctm(c);
     ensure_workspace(c);
     if (c->d != 2 || !c->mfma_on)
@@ -4541,6 +4627,7 @@ int pirgpu_batch_run_packed(pirgpu_ctx* c, const uint8_t* device_packed, uint32_
     refuse_wide(c);
     refuse_tables(c);
     refuse_switched(c);
+    refuse_packed(c);
     refuse_ctm(c);
     ensure_workspace(c);
     if (c->d != 2 || !c->mfma_on)
@@ -4598,6 +4685,7 @@ void check_slots_ctx(pirgpu_ctx* c) {
   refuse_wide(c);
   refuse_tables(c);
   refuse_switched(c);
+  refuse_packed(c);
   refuse_ctm(c);
   ensure_workspace(c);
   if (c->d != 2 || !c->mfma_on || c->mg.nchunks != 1 || c->sb != 0 || c->se != c->dims[0])
@@ -4740,6 +4828,7 @@ int pirgpu_slots_finish_async(pirgpu_ctx* c, const uint64_t* device_rowsums, uin
 int pirgpu_batch_reply_copy_to_device(pirgpu_ctx* c, uint64_t* dst, uint64_t cap) {
   return guarded(c, [&]() -> int {
     refuse_switched(c);
+    refuse_packed(c);
     refuse_ctm(c);
     if (!c->bs().batch_valid) return fail(c, PIRGPU_FAILED_PRECONDITION, "no batch has been run");
     const uint64_t total = (uint64_t)c->bs().batch_count * c->reply_cts;
@@ -4756,6 +4845,7 @@ int pirgpu_batch_reply_copy_to_device(pirgpu_ctx* c, uint64_t* dst, uint64_t cap
 int pirgpu_batch_reply_copy_to_device_async(pirgpu_ctx* c, uint64_t* dst, uint64_t cap) {
   int rc = guarded(c, [&]() -> int {
     refuse_switched(c);
+    refuse_packed(c);
     refuse_ctm(c);
     return PIRGPU_OK;
   });
@@ -4825,6 +4915,7 @@ int pirgpu_ntt_inverse(pirgpu_ctx* c, uint64_t* polys, uint64_t count, int key_l
 int pirgpu_reduce_fixup_device(pirgpu_ctx* c, uint64_t* device_ptr, uint64_t count) {
   return guarded(c, [&]() -> int {
     refuse_switched(c);
+    refuse_packed(c);
     refuse_ctm(c);
     if (!device_ptr) return fail(c, PIRGPU_INVALID_ARGUMENT, "null buffer");
     HIP_TRY(launch_reduce_splits(c->stream, c->dp, device_ptr, 1, count * c->ctw, device_ptr));
@@ -4836,6 +4927,7 @@ int pirgpu_reduce_fixup_device(pirgpu_ctx* c, uint64_t* device_ptr, uint64_t cou
 int pirgpu_reduce_fixup_device_async(pirgpu_ctx* c, uint64_t* device_ptr, uint64_t count, void* stream) {
   return guarded(c, [&]() -> int {
     refuse_switched(c);
+    refuse_packed(c);
     refuse_ctm(c);
     if (!device_ptr) return fail(c, PIRGPU_INVALID_ARGUMENT, "null buffer");
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;

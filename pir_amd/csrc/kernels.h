@@ -169,6 +169,19 @@ hipError_t launch_mod_switch(hipStream_t st, const DevParams* P, const uint64_t*
                              uint32_t k, uint32_t r, uint32_t N, bool compact, uint32_t n_queries = 1,
                              uint64_t in_qstride = 0, uint64_t out_qstride = 0);
 
+// Packed replies (reply_pack.hip): n_cts ciphertexts [2][in_r][N] of canonical residues per query,
+// the first r residues of each component packed to w[j] bits a coefficient, into n_cts * ct_words words per query.
+// Polynomial (c, j) of a ciphertext starts at word c * ct_words / 2 + off[j] of it.  Query q reads in + q * in_qstride and
+// writes out + q * out_qstride.  reply_pack_args: the argument block for the moduli q[0 .. r), w[j] = bit length of q[j] - 1.
+struct ReplyPackArgs {                 // by-value kernel argument
+  uint32_t N, r, in_r, ct_words;
+  uint32_t off[kMaxPrimes];
+  uint8_t w[kMaxPrimes];
+};
+ReplyPackArgs reply_pack_args(uint32_t N, const uint64_t* q, uint32_t r, uint32_t in_r);
+hipError_t launch_reply_pack(hipStream_t st, const ReplyPackArgs& args, const uint64_t* in, uint64_t* out, uint64_t n_cts,
+                             uint32_t n_queries = 1, uint64_t in_qstride = 0, uint64_t out_qstride = 0);
+
 // the same for the integer flavour at N = 32768 (ntt_ring32k.hip): scratch holds canonical u64 residues (upper_ntt of
 // that degree), `acc` canonical partial sums
 hipError_t launch_upper_mac_int(hipStream_t st, const DevParams* P, const uint64_t* scratch, const MfmaPtrs& svq,

@@ -62,7 +62,8 @@ class PIRClient {
     return out;
   }
 
-  // client.cpp:160-185: serialized pir.Response -> one item per index
+  // client.cpp:160-185: serialized pir.Response -> one item per index (reply ciphertexts as SEAL saves them or, from a
+  // server with packed replies, in the packed form: told apart per ciphertext)
   StatusOr<std::vector<std::string>> ProcessResponse(const std::vector<std::size_t>& indexes,
                                                      const std::string& response) const {
     std::vector<uint64_t> idx(indexes.begin(), indexes.end());

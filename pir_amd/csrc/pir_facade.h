@@ -95,10 +95,12 @@ class PIRDatabase {
   // the u64 staging copy is never allocated (pirgpu_create_ex, PIRGPU_CREATE_STREAMED_DB).  ct_multiplication: serve
   // params->use_ciphertext_multiplication with this project's exact product (PIRGPU_CREATE_CT_MULTIPLY); without it the
   // field stays Unimplemented as before.  ct_deferred (with ct_multiplication only): one rounding and one
-  // relinearisation per row of an upper level instead of one per child (PIRGPU_CREATE_CT_DEFERRED)
+  // relinearisation per row of an upper level instead of one per child (PIRGPU_CREATE_CT_DEFERRED).  packed_replies:
+  // replies leave the device, and go onto the wire, at the bit width of their moduli (PIRGPU_CREATE_PACKED_REPLIES);
+  // multiply() then returns packed words, ProcessRequest a response only a client of this tree reads
   static StatusOr<std::shared_ptr<PIRDatabase>> Create(std::shared_ptr<PIRParameters> params, int device = 0,
                                                        bool streamed = false, bool ct_multiplication = false,
-                                                       bool ct_deferred = false) {
+                                                       bool ct_deferred = false, bool packed_replies = false) {
     if (params->coeff_modulus.size() < 2 || params->coeff_modulus.size() > PIRGPU_MAX_PRIMES + 1 ||
         params->dimensions.empty() || params->dimensions.size() > PIRGPU_MAX_DIMS)
       return InvalidArgumentError("invalid parameters");
@@ -122,7 +124,8 @@ class PIRDatabase {
     p.device = device;
     pirgpu_ctx* ctx = nullptr;
     int rc = pirgpu_create_ex(&p, (streamed ? PIRGPU_CREATE_STREAMED_DB : 0u) | (ct_multiplication ? PIRGPU_CREATE_CT_MULTIPLY : 0u) |
-                                      (ct_deferred ? PIRGPU_CREATE_CT_DEFERRED : 0u),
+                                      (ct_deferred ? PIRGPU_CREATE_CT_DEFERRED : 0u) |
+                                      (packed_replies ? PIRGPU_CREATE_PACKED_REPLIES : 0u),
                               &ctx);
     if (rc) return detail::FromRc(nullptr, rc);
     return std::shared_ptr<PIRDatabase>(new PIRDatabase(ctx, std::move(params)));
@@ -132,8 +135,8 @@ class PIRDatabase {
   static StatusOr<std::shared_ptr<PIRDatabase>> Create(const std::vector<std::string>& rawdb,
                                                        std::shared_ptr<PIRParameters> params, int device = 0,
                                                        bool streamed = false, bool ct_multiplication = false,
-                                                       bool ct_deferred = false) {
-    auto db = Create(std::move(params), device, streamed, ct_multiplication, ct_deferred);
+                                                       bool ct_deferred = false, bool packed_replies = false) {
+    auto db = Create(std::move(params), device, streamed, ct_multiplication, ct_deferred, packed_replies);
     if (!db.ok()) return db.status();
     Status s = (*db)->populate(rawdb);
     if (!s.ok()) return s;
@@ -198,6 +201,7 @@ class PIRDatabase {
     }
     const uint64_t n = pirgpu_reply_ct_count(ctx_);
     const size_t rwords = pirgpu_reply_ct_words(ctx_);   // a reply ciphertext has result_primes residues when that is set
+                                                         // (packed replies: its packed words)
     std::vector<uint64_t> out(n * rwords);
     uint64_t got = 0;
     int rc = pirgpu_multiply(ctx_, in.data(), selection_vector.size(), out.data(), n, &got);

@@ -44,6 +44,8 @@
 // The same for the device's seed expansion: where a back end lacks it, seed-compressed keys are
 // expanded on the host as before.
 #pragma weak pirgpu_keyset_set_keys_seeded
+// ... and for packed replies: a back end without the query serves unpacked replies.
+#pragma weak pirgpu_reply_packing
 
 namespace pirgpu {
 namespace wire {
@@ -346,6 +348,7 @@ struct Server {               // what serving needs to know about a context
   size_t ctw;
   Shape rsh;                  // the level the replies are at: sh, or (result_primes) its first r primes with their parms_id
   size_t rctw;                // words per reply ciphertext
+  bool packed = false;        // the context packs its replies (PIRGPU_CREATE_PACKED_REPLIES): rctw packed words, copied as they are
   uint64_t n_reply;
   uint32_t nq_expected;
   struct RelinCache* relin = nullptr;   // per context (Combiner)
@@ -367,6 +370,7 @@ const uint8_t* key_id_of(const Job& job, size_t* len) {
 
 // Response.reply (payload.proto:39-42) for one query: n ciphertexts, written straight into the response buffer
 // Upper bound of what append_reply adds for a reply of n ciphertexts (tags and varint lengths: < 32 bytes each)
+// (a packed ciphertext is never larger than the saved one)
 size_t reply_bytes_bound(const Shape& sh, uint64_t n) { return 32 + n * (32 + saved_ciphertext_size(sh)); }
 
 // The level the replies of a context with these parameters are at: the data level, or -- pirgpu_params.result_primes --
@@ -383,14 +387,19 @@ Shape reply_shape(const pirgpu_params& prm, const Shape& sh) {
 
 // `ready(i)` (optional) is called before ciphertext i is copied: the caller can wait there for the part of the download
 // that holds it.
+// packed: the ciphertexts are ctw packed words each and go out as they are, behind the packed form's prefix (inner
+// compression byte 0x80) -- nothing is unpacked here.
 void append_reply(OutBuf& out, const Shape& sh, const uint64_t* cts_words, uint64_t n, size_t ctw,
-                  const std::function<void(uint64_t)>& ready = nullptr) {
-  const size_t ct_size = saved_ciphertext_size(sh);
+                  const std::function<void(uint64_t)>& ready = nullptr, bool packed = false) {
+  const size_t ct_size = packed ? saved_ciphertext_size_packed(sh) : saved_ciphertext_size(sh);
   std::string per_ct_head;                                    // Ciphertexts.ct = 1: tag + length + the object's prefix
   per_ct_head.push_back((char)((1 << 3) | 2));
   put_varint(per_ct_head, ct_size);
   const size_t per_ct = per_ct_head.size() + ct_size;         // tag + length + object
-  append_ciphertext_prefix(per_ct_head, sh);
+  if (packed)
+    append_ciphertext_prefix_packed(per_ct_head, sh);
+  else
+    append_ciphertext_prefix(per_ct_head, sh);
   std::string reply_head;
   reply_head.push_back((char)((1 << 3) | 2));                 // Response.reply = 1, length-delimited
   put_varint(reply_head, n * per_ct);
@@ -753,7 +762,7 @@ void run_single(const Server& sv, Job& job, const std::pair<const uint8_t*, size
   append_reply(job.out, sv.rsh, hr, got, sv.rctw, [&](uint64_t i) {
     if (i == 0 && !wrc) wrc = pirgpu_query_fetch_wait(sv.ctx, 0);
     if (i == first_part && !wrc) wrc = pirgpu_query_fetch_wait(sv.ctx, 1);
-  });
+  }, sv.packed);
   if (!wrc && first_part >= got) wrc = pirgpu_query_fetch_wait(sv.ctx, 1);
   if (wrc) throw Err{wrc, pirgpu_last_error(sv.ctx)};
 }
@@ -960,7 +969,7 @@ void finish_window(const Server& sv, Window& w, Trace& trace) {
     if (job.rc || !job.uniform || job.mismatch) return;
     try {
       for (uint32_t i = w.runs[r].first; i < w.runs[r].second; ++i)
-        append_reply(job.out, sv.rsh, w.hr + (size_t)i * rwords, sv.n_reply, sv.rctw);
+        append_reply(job.out, sv.rsh, w.hr + (size_t)i * rwords, sv.n_reply, sv.rctw, nullptr, sv.packed);
     } catch (const std::exception& e) {
       fail_job(job, PIRGPU_INTERNAL, e.what());
     }
@@ -1042,7 +1051,8 @@ void serve(pirgpu_ctx* ctx, Combiner& cb, int first_set, Job* const* jobs, size_
   sv.sh = make_shape(sv.prm);
   sv.ctw = (size_t)2 * sv.sh.k * sv.sh.N;
   sv.rsh = reply_shape(sv.prm, sv.sh);
-  sv.rctw = (size_t)2 * sv.rsh.k * sv.rsh.N;   // == pirgpu_reply_ct_words(ctx)
+  sv.packed = pirgpu_reply_packing && pirgpu_reply_packing(ctx) != 0;
+  sv.rctw = sv.packed ? pirgpu::rpk::ct_words(sv.rsh.N, sv.rsh.q, sv.rsh.k) : (size_t)2 * sv.rsh.k * sv.rsh.N;   // == pirgpu_reply_ct_words(ctx)
   sv.n_reply = pirgpu_reply_ct_count(ctx);
   uint64_t dim_sum = 0;
   for (uint32_t l = 0; l < sv.prm.num_dimensions; ++l) dim_sum += sv.prm.dimensions[l];
@@ -1312,13 +1322,13 @@ extern "C" {
 
 void pirgpu_free(void* p) { pool_release(static_cast<uint8_t*>(p)); }
 
-int pirgpu_wire_save_reply(const pirgpu_params* params, const uint64_t* cts, uint64_t n, uint8_t** out, size_t* out_len) {
+static int save_reply(const pirgpu_params* params, const uint64_t* cts, uint64_t n, uint8_t** out, size_t* out_len, bool packed) {
   if (!params || (!cts && n) || !out || !out_len) return PIRGPU_INVALID_ARGUMENT;
   if (params->result_primes >= params->num_data_primes) return PIRGPU_INVALID_ARGUMENT;
   try {
     const Shape rsh = reply_shape(*params, make_shape(*params));
     OutBuf buf;
-    append_reply(buf, rsh, cts, n, (size_t)2 * rsh.k * rsh.N);
+    append_reply(buf, rsh, cts, n, packed ? pirgpu::rpk::ct_words(rsh.N, rsh.q, rsh.k) : (size_t)2 * rsh.k * rsh.N, nullptr, packed);
     *out = buf.release(out_len);
     return PIRGPU_OK;
   } catch (const Err& e) {
@@ -1326,6 +1336,14 @@ int pirgpu_wire_save_reply(const pirgpu_params* params, const uint64_t* cts, uin
   } catch (const std::exception&) {
     return PIRGPU_INTERNAL;
   }
+}
+
+int pirgpu_wire_save_reply(const pirgpu_params* params, const uint64_t* cts, uint64_t n, uint8_t** out, size_t* out_len) {
+  return save_reply(params, cts, n, out, out_len, false);
+}
+int pirgpu_wire_save_reply_packed(const pirgpu_params* params, const uint64_t* packed, uint64_t n, uint8_t** out,
+                                  size_t* out_len) {
+  return save_reply(params, packed, n, out, out_len, true);
 }
 
 void pirgpu_wire_forget(pirgpu_ctx* ctx) {

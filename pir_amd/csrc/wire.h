@@ -33,6 +33,10 @@ int pirgpu_wire_validate_request(const struct pirgpu_params* params, const uint8
 // pirgpu_free.
 int pirgpu_wire_save_reply(const struct pirgpu_params* params, const uint64_t* cts, uint64_t n, uint8_t** out,
                            size_t* out_len);
+// The same for a context with packed replies (PIRGPU_CREATE_PACKED_REPLIES): packed = n reply ciphertexts of
+// rpk::ct_words(N, q, r) packed words each, copied as they are behind the packed form's headers.
+int pirgpu_wire_save_reply_packed(const struct pirgpu_params* params, const uint64_t* packed, uint64_t n, uint8_t** out,
+                                  size_t* out_len);
 // A pinned key set is never evicted or released (one pin per request in flight that uses it; slot handles as handed out
 // by pirgpu_keyset_lookup / _claim).
 struct pirgpu_ctx;

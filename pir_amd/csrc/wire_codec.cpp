@@ -222,14 +222,14 @@ void put_bytes_field(std::string& s, uint32_t field, const std::string& payload)
 
 void put_u64(std::string& s, uint64_t v) { s.append(reinterpret_cast<const char*>(&v), 8); }
 
-void put_header(std::string& s, uint64_t total_size) {
+void put_header(std::string& s, uint64_t total_size, uint8_t compr_mode) {
   uint8_t h[kHeader] = {0};
   h[0] = (uint8_t)(kSealMagic & 0xff);
   h[1] = (uint8_t)(kSealMagic >> 8);
   h[2] = 0x10;  // header size
   h[3] = 3;     // version major
   h[4] = 5;     // version minor
-  h[5] = 0;     // compr_mode_type::none (seal.BUILD:15: zlib off)
+  h[5] = compr_mode;   // compr_mode_type::none (seal.BUILD:15: zlib off); 0x80: the array of a packed reply (reply_pack.h)
   memcpy(h + 8, &total_size, 8);
   s.append(reinterpret_cast<const char*>(h), kHeader);
 }
@@ -250,10 +250,13 @@ struct CtView {
   const uint8_t* seed = nullptr;   // null: fully expanded
   const uint8_t* obj_end = nullptr;
   uint32_t nres = 0;
+  bool packed = false;             // a packed reply: `words` holds rpk::ct_words words, count is still 2 nres N
 };
 }  // namespace
 
-static CtView view_ciphertext(Cursor& c, const Shape& sh, bool key_level) {
+// allow_packed (replies only): the inner array header may carry compression byte 0x80 -- SEAL defines 0 and 1 -- and the
+// array then holds its `count` coefficients at the bit width of their moduli.
+static CtView view_ciphertext(Cursor& c, const Shape& sh, bool key_level, bool allow_packed = false) {
   CtView v;
   const uint8_t* obj_end = c.header();
   Cursor o{c.p, obj_end};
@@ -269,10 +272,32 @@ static CtView view_ciphertext(Cursor& c, const Shape& sh, bool key_level) {
   if (N != sh.N || cm != nres) throw Err{PIRGPU_INVALID_ARGUMENT, "ciphertext data is invalid (shape mismatch)"};
   if ((is_ntt != 0) != key_level) throw Err{PIRGPU_INVALID_ARGUMENT, "ciphertext NTT form does not match its level"};
   // IntArray<ct_coeff_type>
-  const uint8_t* arr_end = Cursor{o.p, o.end}.header();
+  o.need(kHeader);
+  v.packed = allow_packed && o.p[5] == rpk::kPackedComprByte;
+  const uint8_t* arr_end;
+  if (v.packed) {   // every check of Cursor::header but the compression byte
+    const uint16_t magic = (uint16_t)(o.p[0] | (o.p[1] << 8));
+    if (magic != kSealMagic || o.p[2] != 0x10) throw Err{PIRGPU_INVALID_ARGUMENT, "loaded SEALHeader is invalid"};
+    if (o.p[3] != 3) throw Err{PIRGPU_INVALID_ARGUMENT, "incompatible SEAL version"};
+    uint64_t size;
+    memcpy(&size, o.p + 8, 8);
+    if (size < kHeader || size > (uint64_t)(o.end - o.p)) throw Err{PIRGPU_INVALID_ARGUMENT, "SEAL object size mismatch"};
+    arr_end = o.p + size;
+  } else {
+    arr_end = Cursor{o.p, o.end}.header();
+  }
   Cursor a{o.p + kHeader, arr_end};
   uint64_t count = a.u64();
   const uint64_t full = 2ull * nres * sh.N;
+  if (v.packed) {
+    if (count != full) throw Err{PIRGPU_INVALID_ARGUMENT, "ciphertext data is invalid (coefficient count)"};
+    a.need(rpk::ct_words(sh.N, sh.q, nres) * 8);
+    v.words = a.p;
+    v.count = count;
+    v.nres = nres;
+    v.obj_end = obj_end;
+    return v;
+  }
   if (count != full && count != full / 2)
     throw Err{PIRGPU_INVALID_ARGUMENT, "ciphertext data is invalid (coefficient count)"};
   a.need(count * 8);
@@ -372,6 +397,27 @@ size_t saved_ciphertext_size(const Shape& sh) {
 void append_ciphertext(std::string& out, const Shape& sh, const uint64_t* ct) {
   append_ciphertext_prefix(out, sh);
   out.append(reinterpret_cast<const char*>(ct), 2ull * sh.k * sh.N * 8);
+}
+
+size_t saved_ciphertext_size_packed(const Shape& sh) {
+  return kHeader + 32 + 1 + 4 * 8 + kHeader + 8 + rpk::ct_words(sh.N, sh.q, sh.k) * 8;
+}
+
+// The same object with its coefficients packed: outer header, parms_id and shape fields as above, the inner array header
+// with compression byte 0x80 and the packed size, the count still 2 k N.
+void append_ciphertext_prefix_packed(std::string& out, const Shape& sh) {
+  put_header(out, saved_ciphertext_size_packed(sh));
+  for (int i = 0; i < 4; ++i) put_u64(out, sh.data_id[i]);
+  out.push_back(0);  // is_ntt_form
+  put_u64(out, 2);
+  put_u64(out, sh.N);
+  put_u64(out, sh.k);
+  double scale = 1.0;
+  uint64_t sbits;
+  memcpy(&sbits, &scale, 8);
+  put_u64(out, sbits);
+  put_header(out, kHeader + 8 + rpk::ct_words(sh.N, sh.q, sh.k) * 8, rpk::kPackedComprByte);
+  put_u64(out, 2ull * sh.k * sh.N);
 }
 
 void append_ciphertext_prefix(std::string& out, const Shape& sh) {
@@ -586,6 +632,23 @@ Shape make_shape(const pirgpu_params& prm) {
 }
 
 
+// A reply ciphertext in either form: as Ciphertext::save writes it, or packed (inner compression byte 0x80: the array
+// holds the 2 k N coefficients at the bit width of their moduli).  Either way every coefficient must be below its modulus.
+static void load_reply_ciphertext(Cursor& c, const Shape& sh, uint64_t* out) {
+  const uint8_t* start = c.p;
+  const CtView v = view_ciphertext(c, sh, false, true);
+  if (!v.packed) {
+    c.p = start;
+    load_ciphertext_into(c, sh, false, out);
+    return;
+  }
+  if (!rpk::unpack_ct(v.words, sh.N, sh.q, v.nres, out))
+    throw Err{PIRGPU_INVALID_ARGUMENT, "ciphertext data is invalid (coefficient out of range)"};
+  c.p = v.obj_end;
+}
+
+static uint32_t load_cts(const Shape& sh, const uint8_t* data, size_t len, std::vector<uint64_t>& qbuf, bool allow_packed);
+
 // LoadCiphertexts (serialization.cpp:32-42) of one Ciphertexts message -> residues, count
 uint32_t load_query_into(const Shape& sh, const uint8_t* data, size_t len, uint64_t* dst, uint32_t max_cts) {
   Reader qr{data, data + len};
@@ -614,6 +677,14 @@ uint32_t load_query_into(const Shape& sh, const uint8_t* data, size_t len, uint6
 }
 
 uint32_t load_query(const Shape& sh, const uint8_t* data, size_t len, std::vector<uint64_t>& qbuf) {
+  return load_cts(sh, data, len, qbuf, false);
+}
+
+uint32_t load_reply(const Shape& sh, const uint8_t* data, size_t len, std::vector<uint64_t>& qbuf) {
+  return load_cts(sh, data, len, qbuf, true);
+}
+
+static uint32_t load_cts(const Shape& sh, const uint8_t* data, size_t len, std::vector<uint64_t>& qbuf, bool allow_packed) {
   Reader qr{data, data + len};
   std::vector<uint64_t> one;
   qbuf.clear();
@@ -626,7 +697,12 @@ uint32_t load_query(const Shape& sh, const uint8_t* data, size_t len, std::vecto
     if ((tag >> 3) == 1 && (tag & 7) == 2) {
       if (!qr.bytes(d, l)) throw Err{PIRGPU_INVALID_ARGUMENT, "malformed Ciphertexts.ct"};
       Cursor c{d, d + l};
-      load_ciphertext(c, sh, false, one);
+      if (allow_packed) {
+        one.resize(2ull * sh.k * sh.N);
+        load_reply_ciphertext(c, sh, one.data());
+      } else {
+        load_ciphertext(c, sh, false, one);
+      }
       qbuf.insert(qbuf.end(), one.begin(), one.end());
       ++nq;
     } else if (!qr.skip((uint32_t)(tag & 7))) {

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/pirgpu.h"
+#include "reply_pack.h"
 
 namespace pirgpu {
 namespace wire {
@@ -87,7 +88,7 @@ struct Err {
 };
 
 void put_u64(std::string& s, uint64_t v);
-void put_header(std::string& s, uint64_t total_size);
+void put_header(std::string& s, uint64_t total_size, uint8_t compr_mode = 0);
 
 struct Cursor {
   const uint8_t* p;
@@ -141,6 +142,10 @@ size_t saved_ciphertext_size(const Shape& sh);
 void append_ciphertext(std::string& out, const Shape& sh, const uint64_t* ct);
 // Everything of that object before the 2 k N raw words (the same bytes for every data-level ciphertext of a context).
 void append_ciphertext_prefix(std::string& out, const Shape& sh);
+// Packed replies: the same object with compression byte 0x80 in its inner array header, the
+// count still 2 k N, followed by the rpk::ct_words(N, q, k) packed words -- its size, and everything before those words.
+size_t saved_ciphertext_size_packed(const Shape& sh);
+void append_ciphertext_prefix_packed(std::string& out, const Shape& sh);
 // Ciphertext::save of a size-2 ciphertext: data level (k primes, coefficient form) or, with
 // key_level, the (k+1)-prime NTT-form body of a PublicKey.
 std::string save_ciphertext(const Shape& sh, const uint64_t* ct, bool key_level = false,
@@ -175,6 +180,9 @@ std::string save_kswitch_keys(const Shape& sh, const std::vector<const uint64_t*
 
 // LoadCiphertexts (serialization.cpp:32-42) of one pir.Ciphertexts message -> residues [n][2][k][N]; returns n.
 uint32_t load_query(const Shape& sh, const uint8_t* data, size_t len, std::vector<uint64_t>& qbuf);
+// The same for the Ciphertexts message of a REPLY: every ciphertext in either form, as saved or packed (told apart by
+// the inner header byte), unpacked to residues [n][2][k][N]; a packed coefficient >= its modulus is InvalidArgument.
+uint32_t load_reply(const Shape& sh, const uint8_t* data, size_t len, std::vector<uint64_t>& qbuf);
 // the same into caller-owned memory with room for max_cts ciphertexts; returns the number of ciphertexts in the message
 // (all of them parsed and validated; those beyond max_cts are not stored)
 uint32_t load_query_into(const Shape& sh, const uint8_t* data, size_t len, uint64_t* dst, uint32_t max_cts);

@@ -61,14 +61,16 @@ class PIRDatabase:
 
     def __init__(self, params: PIRParameters, device: int = 0, shard: Optional[Sequence[int]] = None,
                  slots: Optional[Sequence[int]] = None, streamed: bool = False, ct_multiplication: bool = False,
-                 ct_deferred: bool = False):
+                 ct_deferred: bool = False, packed_replies: bool = False):
         """shard: rows [begin, end) of dimension 0 this context holds; slots: NTT slots [begin, end) of every plaintext
         it holds (multi-GPU partitionings; default: the whole database).  streamed: loads go in
         row bands straight into the scan's operand layout, the u64 staging copy is never allocated (pirgpu_create_ex,
         DESIGN.md section 6.3).  ct_multiplication: the reference's ciphertext-multiplication mode with this project's
         exact product (PIRGPU_CREATE_CT_MULTIPLY; needs params.use_ciphertext_multiplication).  ct_deferred
         (with ct_multiplication only): one rounding and one relinearisation per row instead of one per child
-        (PIRGPU_CREATE_CT_DEFERRED)."""
+        (PIRGPU_CREATE_CT_DEFERRED).  packed_replies: replies leave the device at the bit width of their moduli
+        (PIRGPU_CREATE_PACKED_REPLIES): every reply array is then [reply_cts, words] of packed
+        words instead of [reply_cts, 2, reply_k, N]; PIRServer.unpack_replies gives the residues back."""
         self.params = params
         enc = params.encryption_parameters
         self.N = enc.poly_modulus_degree
@@ -79,6 +81,7 @@ class PIRDatabase:
         h = C.c_void_p()
         flags = (capi.CREATE_STREAMED_DB if streamed else 0) | (capi.CREATE_CT_MULTIPLY if ct_multiplication else 0)
         flags |= capi.CREATE_CT_DEFERRED if ct_deferred else 0
+        flags |= capi.CREATE_PACKED_REPLIES if packed_replies else 0
         rc = self.lib.pirgpu_create_ex(C.byref(p), flags, C.byref(h))
         if rc != 0:
             raise PirGpuError(rc, self.lib.pirgpu_create_error().decode())
@@ -112,10 +115,11 @@ class PIRDatabase:
     # -- reference interface ------------------------------------------------------
     @classmethod
     def Create(cls, params: PIRParameters, rawdb=None, device: int = 0, shard=None, slots=None,
-               streamed: bool = False, ct_multiplication: bool = False, ct_deferred: bool = False) -> "PIRDatabase":
+               streamed: bool = False, ct_multiplication: bool = False, ct_deferred: bool = False,
+               packed_replies: bool = False) -> "PIRDatabase":
         """database.cpp:40-58: Create(params) / Create(rawdb, params)."""
         db = cls(params, device=device, shard=shard, slots=slots, streamed=streamed, ct_multiplication=ct_multiplication,
-                 ct_deferred=ct_deferred)
+                 ct_deferred=ct_deferred, packed_replies=packed_replies)
         if rawdb is not None:
             db.populate(rawdb)
         return db
@@ -260,8 +264,45 @@ class PIRDatabase:
         return int(self.lib.pirgpu_expansion_ratio(self._h))
 
     def reply_ct_words(self) -> int:
-        """Words of one reply ciphertext: 2 * reply_k * N."""
+        """Words of one reply ciphertext: 2 * reply_k * N, or the packed word count on a context with packed replies."""
         return int(self.lib.pirgpu_reply_ct_words(self._h))
+
+    def reply_packing(self) -> bool:
+        """True on a context created with packed_replies (PIRGPU_CREATE_PACKED_REPLIES)."""
+        return bool(self.lib.pirgpu_reply_packing(self._h))
+
+    def reply_unpacked_words(self) -> int:
+        """Words of one reply ciphertext before packing: 2 * reply_k * N."""
+        return int(self.lib.pirgpu_reply_unpacked_words(self._h))
+
+    def reply_ct_shape(self) -> tuple:
+        """Shape of one reply ciphertext in every reply array: (2, reply_k, N), or (words,) with packed replies."""
+        return (self.reply_ct_words(),) if self.reply_packing() else (2, self.reply_k, self.N)
+
+    def reply_pack(self, cts, r: int) -> np.ndarray:
+        """Test hook (any context): [n, 2, r, N] canonical residues of the first r data primes through the device's pack
+        kernel -> [n, words]."""
+        c = _u64(cts)
+        if c.ndim != 4 or c.shape[1:] != (2, int(r), self.N) or not 1 <= int(r) <= self.k:
+            raise PirGpuError(3, "ciphertexts must have shape [n, 2, r, %d] with 1 <= r <= %d, got %s (r = %s)"
+                              % (self.N, self.k, list(c.shape), r))
+        out = np.empty((c.shape[0], self._packed_words(int(r))), dtype=np.uint64)
+        self._check(self.lib.pirgpu_reply_pack(self._h, _ptr(c), c.shape[0], int(r), _ptr(out)))
+        return out
+
+    def reply_unpack(self, packed, r: int) -> np.ndarray:
+        """Test hook (any context): [n, words] packed over the first r data primes -> [n, 2, r, N] (the host's unpack)."""
+        a = _u64(packed)
+        if not 1 <= int(r) <= self.k or a.ndim != 2 or a.shape[1] != self._packed_words(int(r)):
+            raise PirGpuError(3, "packed ciphertexts must have shape [n, words of r primes] with 1 <= r <= %d, got %s (r = %s)"
+                              % (self.k, list(a.shape), r))
+        out = np.empty((a.shape[0], 2, int(r), self.N), dtype=np.uint64)
+        self._check(self.lib.pirgpu_reply_unpack(self._h, _ptr(a), a.shape[0], int(r), _ptr(out)))
+        return out
+
+    def _packed_words(self, r: int) -> int:
+        q = [int(v) for v in self._cparams.coeff_modulus[:r]]
+        return 2 * sum(self.N * (v - 1).bit_length() // 64 for v in q)
 
     def mod_switch(self, cts, r: int) -> np.ndarray:
         """Test hook: [n, 2, k, N] coefficient-form ciphertexts switched down to their first r primes -> [n, 2, r, N]."""
@@ -309,7 +350,7 @@ class PIRDatabase:
         if sv.ndim != 4 or sv.shape[1:] != (2, self.k, self.N):
             raise PirGpuError(3, "selection vector must have shape [n, 2, %d, %d], got %s" % (self.k, self.N, list(sv.shape)))
         n = self.reply_ct_count()
-        out = np.empty((n, 2, self.reply_k, self.N), dtype=np.uint64)
+        out = np.empty((n,) + self.reply_ct_shape(), dtype=np.uint64)
         cnt = C.c_uint64(0)
         self._check(self.lib.pirgpu_multiply(self._h, _ptr(sv), sv.shape[0], _ptr(out), n, C.byref(cnt)))
         return out[: cnt.value]
@@ -488,7 +529,7 @@ class PIRServer:
             self.set_galois_keys(galois_keys)
         q = self._cts(query, 4, "query")
         n = self.db.reply_ct_count()
-        out = np.empty((n, 2, self.reply_k, self.N), dtype=np.uint64)
+        out = np.empty((n,) + self.db.reply_ct_shape(), dtype=np.uint64)
         cnt = C.c_uint64(0)
         self._check(self.lib.pirgpu_process_query(self.db.handle, _ptr(q), q.shape[0], _ptr(out), n, C.byref(cnt)))
         return out[: cnt.value]
@@ -611,9 +652,16 @@ class PIRServer:
         """hipDeviceSynchronize() through the library's own HIP runtime (every stream of the device)."""
         self._check(self.lib.pirgpu_device_synchronize(self.db.handle))
 
+    def unpack_replies(self, replies) -> np.ndarray:
+        """Packed replies [..., reply_cts, words] (what a context with packed_replies returns) -> residues
+        [..., reply_cts, 2, reply_k, N]."""
+        a = _u64(replies)
+        flat = a.reshape(-1, a.shape[-1])
+        return self.db.reply_unpack(flat, self.reply_k).reshape(a.shape[:-1] + (2, self.reply_k, self.N))
+
     def fetch_reply(self) -> np.ndarray:
         n = self.db.reply_ct_count()
-        out = np.empty((n, 2, self.reply_k, self.N), dtype=np.uint64)
+        out = np.empty((n,) + self.db.reply_ct_shape(), dtype=np.uint64)
         cnt = C.c_uint64(0)
         self._check(self.lib.pirgpu_query_fetch(self.db.handle, _ptr(out), n, C.byref(cnt)))
         return out[: cnt.value]
@@ -643,7 +691,7 @@ class PIRServer:
 
     def fetch_batch(self) -> np.ndarray:
         n = self.db.reply_ct_count()
-        out = np.empty((self._batch_count, n, 2, self.reply_k, self.N), dtype=np.uint64)
+        out = np.empty((self._batch_count, n) + self.db.reply_ct_shape(), dtype=np.uint64)
         cnt = C.c_uint64(0)
         self._check(self.lib.pirgpu_batch_fetch(self.db.handle, _ptr(out), self._batch_count * n, C.byref(cnt)))
         return out
