@@ -196,6 +196,23 @@ int pirgpu_create(const pirgpu_params* params, pirgpu_ctx** out);
  * entry points, pirgpu_reduce_fixup* and the device reply copies are FailedPrecondition.  Without the flag no kernel is
  * launched and no buffer allocated for it. */
 #define PIRGPU_CREATE_PACKED_REPLIES 16u
+/* PIRGPU_CREATE_CT_COMPACT_REPLY: the reply of a ciphertext-multiplication context, modulus-switched and bit-packed (not
+ * in the reference).  Valid only together with PIRGPU_CREATE_CT_MULTIPLY, with or without
+ * PIRGPU_CREATE_CT_DEFERRED; without the CT flag the create is InvalidArgument.  Every level is computed bit for bit as
+ * on a CT context without the flag, at all k primes -- the product is defined over the full modulus Q, nothing below
+ * level 0 is switched.  The finished level-0 ciphertext of every plane (with d = 1: the row sum) is then switched to the
+ * first r = result_primes primes by the drop steps of section 6.4 (0 <= r < k is accepted on such a context; r = 0 keeps
+ * all k primes; r >= k stays InvalidArgument) and packed as PIRGPU_CREATE_PACKED_REPLIES packs, over those r (or k)
+ * moduli.  pirgpu_reply_ct_count stays the number of planes, pirgpu_reply_ct_words is the packed word count,
+ * pirgpu_reply_packing is 1, pirgpu_reply_unpacked_words is 2 r N (2 k N at r = 0); the wire form is that of a packed
+ * reply at level r, and the client (pirclient with use_ciphertext_multiplication and the same result_primes) decrypts at
+ * that level.  PIRGPU_CREATE_PACKED_REPLIES beside PIRGPU_CREATE_CT_MULTIPLY stays InvalidArgument with or without this
+ * flag, and so does result_primes on a CT context without it.  Everything PIRGPU_CREATE_CT_MULTIPLY refuses otherwise
+ * stays refused (row and slot shards, PIRGPU_CREATE_STREAMED_DB, tables > 1, N = 32768, k > 6); the multi-GPU entry
+ * points, pirgpu_reduce_fixup* and the device reply copies are FailedPrecondition.  The transparent-ciphertext rule and
+ * the hooks pirgpu_ct_multiply, pirgpu_ct_multiply_sum, pirgpu_relinearize, pirgpu_mod_switch and pirgpu_reply_pack are
+ * unchanged.  (Bit 32 stays unknown: flags 32 | 16 remain InvalidArgument.) */
+#define PIRGPU_CREATE_CT_COMPACT_REPLY 64u
 int pirgpu_create_ex(const pirgpu_params* params, uint32_t flags, pirgpu_ctx** out);
 void pirgpu_destroy(pirgpu_ctx* ctx);
 /* Message of the calling thread's last failed call on this context (falls back to the context's last

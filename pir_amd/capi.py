@@ -13,6 +13,7 @@ CREATE_STREAMED_DB = 1          # pirgpu_create_ex flags
 CREATE_CT_MULTIPLY = 4
 CREATE_CT_DEFERRED = 8
 CREATE_PACKED_REPLIES = 16      # replies at the bit width of their moduli
+CREATE_CT_COMPACT_REPLY = 64    # with CREATE_CT_MULTIPLY: the reply switched to result_primes primes and packed (section 6.6)
 
 u64p = C.POINTER(C.c_uint64)
 u8p = C.POINTER(C.c_uint8)

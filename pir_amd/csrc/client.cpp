@@ -703,7 +703,7 @@ struct pirclient {
     if (prm.use_ciphertext_multiplication) {
       if (n_cts != 1)
         throw Err{PIRGPU_INVALID_ARGUMENT, "Number of ciphertexts in reply must be 1 when using CT multiplication"};
-      decrypt(reply, pt_out);
+      decrypt_level(reply, reply_primes(), pt_out);   // a compact reply (PIRGPU_CREATE_CT_COMPACT_REPLY) is at level result_primes
       return;
     }
     const size_t ratio = reply_ratio();

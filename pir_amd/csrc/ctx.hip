@@ -255,7 +255,8 @@ struct pirgpu_ctx {
   uint32_t rp = 0;   // pirgpu_params.result_primes (0: level results and replies stay at k primes)
   size_t rctw = 0;   // words per REPLY ciphertext: 2 rp N, or ctw -- packed replies: the packed word count (rpa.ct_words)
   // PIRGPU_CREATE_PACKED_REPLIES: level 0 lands in the owner's `last` buffer (as with
-  // result_primes) and reply_pack_kernel writes the reply, at the bit width of its moduli, where it went before
+  // result_primes) and reply_pack_kernel writes the reply, at the bit width of its moduli, where it went before.  Set by
+  // PIRGPU_CREATE_CT_COMPACT_REPLY as well (section 6.6): there rp switches level 0 alone, before the pack
   bool pack = false;
   ReplyPackArgs rpa{};   // ... its argument block: the first (rp ? rp : k) residues of [2][k][N] ciphertexts
   uint32_t dims[PIRGPU_MAX_DIMS]{};
@@ -418,6 +419,7 @@ struct pirgpu_ctx {
   // multiply ciphertext by ciphertext (exact BFV product + relinearisation) instead of re-encoding: E = 1 at every level
   bool ctm = false;
   bool ctm_deferred = false;                // PIRGPU_CREATE_CT_DEFERRED: one rounding and one key switch per row
+  bool ctm_compact = false;                 // PIRGPU_CREATE_CT_COMPACT_REPLY: sets `pack`, lets rp be non-zero (reply only)
   uint32_t kb = 0;                          // primes of the auxiliary base (k + 2)
   uint64_t aux_primes[PIRGPU_MAX_PRIMES]{};
   DevParams hp_aux{};                       // the auxiliary base as the "data primes" of a second parameter block:
@@ -1287,7 +1289,7 @@ void refuse_ctm(const pirgpu_ctx* c) {
 // buffer whose reader expects residues, does not serve them.
 void refuse_packed(const pirgpu_ctx* c) {
   if (c->pack)
-    throw Fail{PIRGPU_FAILED_PRECONDITION, "this context packs its replies (PIRGPU_CREATE_PACKED_REPLIES): the multi-GPU "
+    throw Fail{PIRGPU_FAILED_PRECONDITION, "this context packs its replies (PIRGPU_CREATE_PACKED_REPLIES, PIRGPU_CREATE_CT_COMPACT_REPLY): the multi-GPU "
                                            "entry points and the device reply copies do not serve it"};
 }
 
@@ -1677,6 +1679,9 @@ void ctm_relinearize(pirgpu_ctx* c, hipStream_t st, const CtmRegions& r, uint32_
 void post_scan_ctm_level(pirgpu_ctx* c, const Stage& sg, uint32_t l) {
   const uint32_t N = c->N, k = c->k, nq = sg.n, dim = c->dims[l];
   const size_t ctw = c->ctw;
+  // PIRGPU_CREATE_CT_COMPACT_REPLY: level 0 at k primes lands in the owner's `last` buffer (same stride), the carry of a
+  // row's sum from block to block included; post_scan_stage switches and packs it from there
+  uint64_t* const out = c->pack && l == 0 ? sg.last : sg.lvl[l];
   const uint64_t nch = c->lvl_rows[l + 1], rows = c->lvl_rows[l];
   hipStream_t st = sg.stream;
   if (nq > (uint32_t)kMaxMfmaQueries || sg.local_rows || sg.sel_f64) throw Fail{PIRGPU_INTERNAL, "unexpected stage in ciphertext-multiplication mode"};
@@ -1718,7 +1723,7 @@ void post_scan_ctm_level(pirgpu_ctx* c, const Stage& sg, uint32_t l) {
       c->options.counter(OPT_CT_RELINS) += (uint64_t)fin * nq;
       ctm_relinearize(c, st, r, fin * nq, key);
       // relin + (0, d1) into the finished rows: the accumulation with one child per row (pirgpu_relinearize's form)
-      HIP_TRY(launch_ctm_accumulate(st, c->dp, k, N, r.yq, r.d, sg.lvl[l] + (size_t)(j0 / dim) * ctw, c->lvl_cts[l] * ctw, 1,
+      HIP_TRY(launch_ctm_accumulate(st, c->dp, k, N, r.yq, r.d, out + (size_t)(j0 / dim) * ctw, c->lvl_cts[l] * ctw, 1,
                                     nq, 0, fin, fin));
       if ((j0 + nj) % dim != 0 && j0 + nj < nch) ctm_carry_row(c, st, r, nq, fin);
       continue;
@@ -1729,7 +1734,7 @@ void post_scan_ctm_level(pirgpu_ctx* c, const Stage& sg, uint32_t l) {
     else
       ctm_products(c, st, r, sg.lvl[l + 1], c->lvl_cts[l + 1] * ctw, ws.selc, dim, nq, (uint32_t)j0, n);
     ctm_relinearize(c, st, r, n, key);
-    HIP_TRY(launch_ctm_accumulate(st, c->dp, k, N, r.yq, r.d, sg.lvl[l], c->lvl_cts[l] * ctw, dim, nq, (uint32_t)j0, nj,
+    HIP_TRY(launch_ctm_accumulate(st, c->dp, k, N, r.yq, r.d, out, c->lvl_cts[l] * ctw, dim, nq, (uint32_t)j0, nj,
                                   (uint32_t)rows));
   }
 }
@@ -1747,8 +1752,9 @@ void post_scan_stage(pirgpu_ctx* c, const Stage& sg, Worker* profiled) {
   auto level = [&](uint32_t l) { return (c->rp || c->pack) && l == 0 ? sg.last : sg.lvl[l]; };
   // result_primes: every level result is switched right after its inverse transform (all flavours leave canonical u64
   // residues there: Encode reads them as such) -- in place below the reply, compact for the reply itself
+  // (ciphertext-multiplication mode: the product is defined over Q, so only the finished level 0 is switched)
   auto switch_level = [&](uint32_t l) {
-    if (!c->rp) return;
+    if (!c->rp || (c->ctm && l != 0)) return;
     const uint64_t qstride = c->lvl_cts[l] * ctw;
     if (l == 0 && !c->pack)
       HIP_TRY(launch_mod_switch(st, c->dp, sg.last, sg.lvl[0], c->lvl_cts[0], k, c->rp, N, true, sg.n, qstride,
@@ -1773,6 +1779,7 @@ void post_scan_stage(pirgpu_ctx* c, const Stage& sg, Worker* profiled) {
     if (c->ctm) {   // ciphertext by ciphertext: one result ciphertext per node at every level, nothing re-encoded
       if (l == 0 && profiled) record(c, *profiled, PH_FINAL);
       post_scan_ctm_level(c, sg, (uint32_t)l);
+      switch_level((uint32_t)l);
       continue;
     }
     const uint64_t nch = ceil_div(shard_pts, c->stride[l + 1]);
@@ -1916,7 +1923,8 @@ int pirgpu_create_ex(const pirgpu_params* p, uint32_t flags, pirgpu_ctx** out) {
     return code;
   };
   try {
-    if (flags & ~(PIRGPU_CREATE_STREAMED_DB | PIRGPU_CREATE_CT_MULTIPLY | PIRGPU_CREATE_CT_DEFERRED | PIRGPU_CREATE_PACKED_REPLIES))
+    if (flags & ~(PIRGPU_CREATE_STREAMED_DB | PIRGPU_CREATE_CT_MULTIPLY | PIRGPU_CREATE_CT_DEFERRED | PIRGPU_CREATE_PACKED_REPLIES |
+                  PIRGPU_CREATE_CT_COMPACT_REPLY))
       return bail(PIRGPU_INVALID_ARGUMENT, "unknown pirgpu_create_ex flags " + std::to_string(flags));
     c->streamed = (flags & PIRGPU_CREATE_STREAMED_DB) != 0;
     c->ctm = (flags & PIRGPU_CREATE_CT_MULTIPLY) != 0;
@@ -1932,6 +1940,12 @@ int pirgpu_create_ex(const pirgpu_params* p, uint32_t flags, pirgpu_ctx** out) {
                                            "slot_end) is not supported");
     if (c->ctm_deferred && !c->ctm)
       return bail(PIRGPU_INVALID_ARGUMENT, "PIRGPU_CREATE_CT_DEFERRED needs PIRGPU_CREATE_CT_MULTIPLY (it is a form of that mode)");
+    // PIRGPU_CREATE_CT_COMPACT_REPLY: the finished reply of a ciphertext-multiplication context is
+    // switched to result_primes primes and packed; PIRGPU_CREATE_PACKED_REPLIES itself stays refused there (above)
+    c->ctm_compact = (flags & PIRGPU_CREATE_CT_COMPACT_REPLY) != 0;
+    if (c->ctm_compact && !c->ctm)
+      return bail(PIRGPU_INVALID_ARGUMENT, "PIRGPU_CREATE_CT_COMPACT_REPLY needs PIRGPU_CREATE_CT_MULTIPLY (it is a form of that mode)");
+    if (c->ctm_compact) c->pack = true;
     c->prm = *p;
     const uint32_t N = p->poly_modulus_degree, k = p->num_data_primes;
     if (N < 2048 || N > 32768 || (N & (N - 1)))
@@ -1959,8 +1973,9 @@ int pirgpu_create_ex(const pirgpu_params* p, uint32_t flags, pirgpu_ctx** out) {
       if (p->slot_begin || p->slot_end)
         return bail(PIRGPU_INVALID_ARGUMENT, "PIRGPU_CREATE_CT_MULTIPLY is served by one GPU: a slot shard (slot_begin / "
                                              "slot_end) is not supported");
-      if (p->result_primes)
-        return bail(PIRGPU_INVALID_ARGUMENT, "PIRGPU_CREATE_CT_MULTIPLY with result_primes > 0 is not supported");
+      if (p->result_primes && !c->ctm_compact)
+        return bail(PIRGPU_INVALID_ARGUMENT, "PIRGPU_CREATE_CT_MULTIPLY with result_primes > 0 is not supported (without "
+                                             "PIRGPU_CREATE_CT_COMPACT_REPLY)");
       if (p->tables > 1) return bail(PIRGPU_INVALID_ARGUMENT, "PIRGPU_CREATE_CT_MULTIPLY with tables > 1 is not supported");
     }
     if (p->special_prime == 0)

@@ -98,9 +98,12 @@ class PIRDatabase {
   // relinearisation per row of an upper level instead of one per child (PIRGPU_CREATE_CT_DEFERRED).  packed_replies:
   // replies leave the device, and go onto the wire, at the bit width of their moduli (PIRGPU_CREATE_PACKED_REPLIES);
   // multiply() then returns packed words, ProcessRequest a response only a client of this tree reads
+  // ct_compact_reply (with ct_multiplication only): the finished reply is switched to params->result_primes primes and
+  // packed (PIRGPU_CREATE_CT_COMPACT_REPLY); replies are handled as with packed_replies
   static StatusOr<std::shared_ptr<PIRDatabase>> Create(std::shared_ptr<PIRParameters> params, int device = 0,
                                                        bool streamed = false, bool ct_multiplication = false,
-                                                       bool ct_deferred = false, bool packed_replies = false) {
+                                                       bool ct_deferred = false, bool packed_replies = false,
+                                                       bool ct_compact_reply = false) {
     if (params->coeff_modulus.size() < 2 || params->coeff_modulus.size() > PIRGPU_MAX_PRIMES + 1 ||
         params->dimensions.empty() || params->dimensions.size() > PIRGPU_MAX_DIMS)
       return InvalidArgumentError("invalid parameters");
@@ -125,7 +128,8 @@ class PIRDatabase {
     pirgpu_ctx* ctx = nullptr;
     int rc = pirgpu_create_ex(&p, (streamed ? PIRGPU_CREATE_STREAMED_DB : 0u) | (ct_multiplication ? PIRGPU_CREATE_CT_MULTIPLY : 0u) |
                                       (ct_deferred ? PIRGPU_CREATE_CT_DEFERRED : 0u) |
-                                      (packed_replies ? PIRGPU_CREATE_PACKED_REPLIES : 0u),
+                                      (packed_replies ? PIRGPU_CREATE_PACKED_REPLIES : 0u) |
+                                      (ct_compact_reply ? PIRGPU_CREATE_CT_COMPACT_REPLY : 0u),
                               &ctx);
     if (rc) return detail::FromRc(nullptr, rc);
     return std::shared_ptr<PIRDatabase>(new PIRDatabase(ctx, std::move(params)));
@@ -135,8 +139,9 @@ class PIRDatabase {
   static StatusOr<std::shared_ptr<PIRDatabase>> Create(const std::vector<std::string>& rawdb,
                                                        std::shared_ptr<PIRParameters> params, int device = 0,
                                                        bool streamed = false, bool ct_multiplication = false,
-                                                       bool ct_deferred = false, bool packed_replies = false) {
-    auto db = Create(std::move(params), device, streamed, ct_multiplication, ct_deferred, packed_replies);
+                                                       bool ct_deferred = false, bool packed_replies = false,
+                                                       bool ct_compact_reply = false) {
+    auto db = Create(std::move(params), device, streamed, ct_multiplication, ct_deferred, packed_replies, ct_compact_reply);
     if (!db.ok()) return db.status();
     Status s = (*db)->populate(rawdb);
     if (!s.ok()) return s;

@@ -182,7 +182,9 @@ def create_pir_parameters(dbsize: int, bytes_per_item: int = 0, dimensions: int 
 
     result_primes = r >= 1 (not in the reference) opts in to modulus-switched results: the server switches every level
     result and the reply down to the first r data primes (r below their number), which shrinks the re-encoding and the
-    reply; the client must be created with the same parameters.
+    reply; the client must be created with the same parameters.  With use_ciphertext_multiplication the server must be
+    created with ct_compact_reply (PIRGPU_CREATE_CT_COMPACT_REPLY): only the finished reply is then switched, once, and
+    the client decrypts it at level r.
 
     tables = T > 1 (not in the reference): everything above describes ONE table -- dbsize items, its plaintexts, its
     dimensions -- and the server context holds T of them; a query names its table beside the request.  The client is

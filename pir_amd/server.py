@@ -61,7 +61,7 @@ class PIRDatabase:
 
     def __init__(self, params: PIRParameters, device: int = 0, shard: Optional[Sequence[int]] = None,
                  slots: Optional[Sequence[int]] = None, streamed: bool = False, ct_multiplication: bool = False,
-                 ct_deferred: bool = False, packed_replies: bool = False):
+                 ct_deferred: bool = False, packed_replies: bool = False, ct_compact_reply: bool = False):
         """shard: rows [begin, end) of dimension 0 this context holds; slots: NTT slots [begin, end) of every plaintext
         it holds (multi-GPU partitionings; default: the whole database).  streamed: loads go in
         row bands straight into the scan's operand layout, the u64 staging copy is never allocated (pirgpu_create_ex,
@@ -70,7 +70,10 @@ class PIRDatabase:
         (with ct_multiplication only): one rounding and one relinearisation per row instead of one per child
         (PIRGPU_CREATE_CT_DEFERRED).  packed_replies: replies leave the device at the bit width of their moduli
         (PIRGPU_CREATE_PACKED_REPLIES): every reply array is then [reply_cts, words] of packed
-        words instead of [reply_cts, 2, reply_k, N]; PIRServer.unpack_replies gives the residues back."""
+        words instead of [reply_cts, 2, reply_k, N]; PIRServer.unpack_replies gives the residues back.
+        ct_compact_reply (with ct_multiplication only; PIRGPU_CREATE_CT_COMPACT_REPLY): the
+        finished reply is switched to params.result_primes primes (0: all of them) and packed; replies come back the
+        way a context with packed_replies returns them."""
         self.params = params
         enc = params.encryption_parameters
         self.N = enc.poly_modulus_degree
@@ -82,6 +85,7 @@ class PIRDatabase:
         flags = (capi.CREATE_STREAMED_DB if streamed else 0) | (capi.CREATE_CT_MULTIPLY if ct_multiplication else 0)
         flags |= capi.CREATE_CT_DEFERRED if ct_deferred else 0
         flags |= capi.CREATE_PACKED_REPLIES if packed_replies else 0
+        flags |= capi.CREATE_CT_COMPACT_REPLY if ct_compact_reply else 0
         rc = self.lib.pirgpu_create_ex(C.byref(p), flags, C.byref(h))
         if rc != 0:
             raise PirGpuError(rc, self.lib.pirgpu_create_error().decode())
@@ -116,10 +120,10 @@ class PIRDatabase:
     @classmethod
     def Create(cls, params: PIRParameters, rawdb=None, device: int = 0, shard=None, slots=None,
                streamed: bool = False, ct_multiplication: bool = False, ct_deferred: bool = False,
-               packed_replies: bool = False) -> "PIRDatabase":
+               packed_replies: bool = False, ct_compact_reply: bool = False) -> "PIRDatabase":
         """database.cpp:40-58: Create(params) / Create(rawdb, params)."""
         db = cls(params, device=device, shard=shard, slots=slots, streamed=streamed, ct_multiplication=ct_multiplication,
-                 ct_deferred=ct_deferred, packed_replies=packed_replies)
+                 ct_deferred=ct_deferred, packed_replies=packed_replies, ct_compact_reply=ct_compact_reply)
         if rawdb is not None:
             db.populate(rawdb)
         return db
@@ -268,7 +272,8 @@ class PIRDatabase:
         return int(self.lib.pirgpu_reply_ct_words(self._h))
 
     def reply_packing(self) -> bool:
-        """True on a context created with packed_replies (PIRGPU_CREATE_PACKED_REPLIES)."""
+        """True on a context created with packed_replies (PIRGPU_CREATE_PACKED_REPLIES) or ct_compact_reply
+        (PIRGPU_CREATE_CT_COMPACT_REPLY)."""
         return bool(self.lib.pirgpu_reply_packing(self._h))
 
     def reply_unpacked_words(self) -> int:
@@ -653,7 +658,7 @@ class PIRServer:
         self._check(self.lib.pirgpu_device_synchronize(self.db.handle))
 
     def unpack_replies(self, replies) -> np.ndarray:
-        """Packed replies [..., reply_cts, words] (what a context with packed_replies returns) -> residues
+        """Packed replies [..., reply_cts, words] (what a context with packed_replies or ct_compact_reply returns) -> residues
         [..., reply_cts, 2, reply_k, N]."""
         a = _u64(replies)
         flat = a.reshape(-1, a.shape[-1])
