@@ -68,6 +68,29 @@ int pirclient_load_response(pirclient* c, const uint8_t* response, size_t respon
  * Serializable<RelinKeys> of PIRClient::initialize produce, client.cpp:47-54: every key sample carries c0 and the
  * 64-byte seed its uniform half is re-sampled from) or, with enabled == 0, fully expanded objects. */
 int pirclient_set_seeded_keys(pirclient* c, int enabled);
+/* Compact queries (pirgpu.h, pirgpu_query_stage_compact).  Replaces: encryptor_->encrypt(pt,
+ * query[c]) of createQueryFor -- client.cpp:137 -- for a client that knows the server is this tree's.  mode:
+ *   0  public-key queries, saved as Ciphertext::save writes them: today's requests, byte for byte (default);
+ *   1  every query ciphertext of pirclient_create_request is encrypted SYMMETRICALLY at the data level and sent
+ *      seed-compressed: a fresh 64-byte public seed from the client's generator, c1 = sample_poly_uniform(BlakePRNG(
+ *      seed), q_0 .. q_{k-1}) in coefficient form, c0 = -(c1 s + e) + the plaintext with the scaling the public-key path
+ *      applies; on the wire c0 (k N words) and the seed behind the array -- SEAL 3.5.6's Serializable<Ciphertext> of
+ *      Encryptor::encrypt_symmetric, as this tree reads it (unverified against a SEAL build);
+ *   2  the same with c0 packed: inner array header with compression byte 0x80, the count still k N, polynomial j as
+ *      N w_j / 64 words at w_j = bit length of q_j - 1 bits a coefficient.  Only this tree's server reads this form.
+ * Three forms of a query ciphertext therefore exist on the wire: as saved, seed-compressed, seed-compressed and packed.
+ * A symmetric query has one error term where a public-key query has three: its noise budget is not below that one's. */
+int pirclient_set_compact_queries(pirclient* c, int mode);
+/* words of one compact query ciphertext: k N + 8 (packed = 0) or sum_j N w_j / 64 + 8 (packed = 1) */
+uint64_t pirclient_query_compact_words(const pirclient* c, int packed);
+/* pirclient_create_query for the residue-level compact entry points: compact_out [query_ct_count][query_compact_words],
+ * every ciphertext c0 (plain or packed) followed by the 8 words of its seed.  cap_cts = room in ciphertexts. */
+int pirclient_create_query_compact(pirclient* c, uint64_t index, int packed, uint64_t* compact_out, size_t cap_cts,
+                                   uint32_t* n_cts);
+/* pirclient_save_request around compact query ciphertexts ([n_queries][query_ct_count][query_compact_words]): the wire
+ * form of mode 1 (packed = 0) or mode 2 (packed = 1). */
+int pirclient_save_request_compact(pirclient* c, const uint64_t* queries, size_t n_queries, int packed, uint8_t** request,
+                                   size_t* request_len);
 
 /* ---- residue-level halves of the same calls (what sits between SEAL objects in the reference) ---- */
 

@@ -464,6 +464,34 @@ int pirgpu_batch_run(pirgpu_ctx* ctx);
  * the GPU or on its way back to the host (what pirgpu_process_request(s) do with two request windows in flight). */
 int pirgpu_batch_stage_async(pirgpu_ctx* ctx, const uint64_t* pinned_queries, uint32_t nq, uint32_t count);
 int pirgpu_batch_unstage(pirgpu_ctx* ctx);
+/* Compact queries.  Replaces: LoadCiphertexts (serialization.h:44) of a query the client
+ * encrypted under the secret key and saved as Serializable<Ciphertext> -- the reference's client.cpp:137 encrypts under
+ * the public key, so only this tree's client (pirclient_set_compact_queries) writes such a query.  A compact query
+ * ciphertext is c0, [k][N] residues in coefficient form at the data level, plus the 64-byte public seed that defines
+ * c1 = sample_poly_uniform(BlakePRNG(seed), q_0 .. q_{k-1}).  c0 comes in one of two forms:
+ *   packed = 0   k N little-endian u64 words;
+ *   packed = 1   polynomial j as the bit stream of its N coefficients at w_j = bit length of q_j - 1 bits each, N w_j / 64
+ *                words (the stream of a packed reply, section 6.8).
+ * In both the 8 words of the seed follow c0; query_compact_words is the size of one compact ciphertext in words
+ * (k N + 8, or sum_j N w_j / 64 + 8).  `compact` holds [nq] (query_stage_compact) or [count][nq] (batch_stage_compact)
+ * of them back to back.  The words are uploaded as they are, c0 is unpacked and c1 re-sampled by kernels on the device
+ * (query_expand.hip, seed_expand.hip), and the context is then in exactly the state pirgpu_query_stage /
+ * pirgpu_batch_stage(_async) leaves with the expanded [2][k][N] ciphertexts: run, fetch, key sets, tables and every
+ * context kind work as they do there.  The _async forms take pinned host memory and return before the upload is done;
+ * batch_stage_compact_async uploads and expands in the same pieces of 8 queries pirgpu_batch_stage_async uploads in.
+ * Every c0 coefficient is checked on the host before anything is queued: one that is not below its modulus (a packed
+ * value may be anywhere in [q, 2^w)) fails the call with InvalidArgument "ciphertext data is invalid (coefficient out of
+ * range)" and nothing is staged.  A row- or slot-sharded context fails with FailedPrecondition: compact queries do not
+ * feed the multi-GPU entry points.
+ *   query_expand        test hook in the manner of pirgpu_expand_seeds: n compact ciphertexts -> out[n][2][k][N].
+ *   query_expand_stats  [0] compact ciphertexts expanded on the device so far, [1] draws those expansions rejected. */
+uint64_t pirgpu_query_compact_words(const pirgpu_ctx* ctx, int packed);
+int pirgpu_query_stage_compact(pirgpu_ctx* ctx, const uint64_t* compact, uint32_t nq, int packed);
+int pirgpu_query_stage_compact_async(pirgpu_ctx* ctx, const uint64_t* pinned_compact, uint32_t nq, int packed);
+int pirgpu_batch_stage_compact(pirgpu_ctx* ctx, const uint64_t* compact, uint32_t nq, uint32_t count, int packed);
+int pirgpu_batch_stage_compact_async(pirgpu_ctx* ctx, const uint64_t* pinned_compact, uint32_t nq, uint32_t count, int packed);
+int pirgpu_query_expand(pirgpu_ctx* ctx, const uint64_t* compact, uint32_t n, int packed, uint64_t* out);
+int pirgpu_query_expand_stats(pirgpu_ctx* ctx, uint64_t stats[2]);
 int pirgpu_batch_select(pirgpu_ctx* ctx, uint32_t which);
 int pirgpu_batch_fetch(pirgpu_ctx* ctx, uint64_t* replies, uint64_t reply_capacity, uint64_t* reply_count);
 /* Replies on their way to the host while the batch is still running: with a PINNED host buffer set here (capacity in

@@ -14,7 +14,8 @@ SOURCES = ["kernels.hip", "scan_mfma.hip", "scan_mfma_pair.hip", "ctx.hip", "wir
            "ctmult_rowsum.hip",      # ... its deferred rounding: the tensor summed over the children of a row
            "ctmult_shared.hip",      # ... its shared selectors: a level's selectors lifted and transformed once
            "seed_expand.hip",        # seed-compressed keys: the c1 halves re-sampled on the device (BLAKE2Xb)
-           "reply_pack.hip"]         # packed replies: residues to the bit width of their moduli where a reply is produced
+           "reply_pack.hip",         # packed replies: residues to the bit width of their moduli where a reply is produced
+           "query_expand.hip"]       # compact queries: packed c0 halves to residues where a query is staged
 NTT_SOURCE = "ntt_kernels.hip"      # compiled once per ring degree (-DPIRGPU_LOGN)
 NTT_LOGNS = [11, 12, 13, 14]
 NTT_PACK_BYTES = [5, 6, 7]          # ... and once per width of the packed key-switch intermediates (-DPIRGPU_PACK_BYTES)

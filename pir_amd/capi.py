@@ -160,6 +160,13 @@ SIGNATURES = {
     "pirgpu_batch_set_keysets": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32]),
     "pirgpu_batch_stage_async": (C.c_int, [C.c_void_p, u64p, C.c_uint32, C.c_uint32]),
     "pirgpu_batch_unstage": (C.c_int, [C.c_void_p]),
+    "pirgpu_query_compact_words": (C.c_uint64, [C.c_void_p, C.c_int]),
+    "pirgpu_query_stage_compact": (C.c_int, [C.c_void_p, u64p, C.c_uint32, C.c_int]),
+    "pirgpu_query_stage_compact_async": (C.c_int, [C.c_void_p, u64p, C.c_uint32, C.c_int]),
+    "pirgpu_batch_stage_compact": (C.c_int, [C.c_void_p, u64p, C.c_uint32, C.c_uint32, C.c_int]),
+    "pirgpu_batch_stage_compact_async": (C.c_int, [C.c_void_p, u64p, C.c_uint32, C.c_uint32, C.c_int]),
+    "pirgpu_query_expand": (C.c_int, [C.c_void_p, u64p, C.c_uint32, C.c_int, u64p]),
+    "pirgpu_query_expand_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "pirgpu_batch_select": (C.c_int, [C.c_void_p, C.c_uint32]),
     "pirgpu_keyset_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "pirgpu_process_requests": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
@@ -273,6 +280,11 @@ CLIENT_SIGNATURES = {
                                                       C.POINTER(C.c_size_t)]),
     "pirclient_free": (None, [C.c_void_p]),
     "pirclient_set_seeded_keys": (C.c_int, [C.c_void_p, C.c_int]),
+    "pirclient_set_compact_queries": (C.c_int, [C.c_void_p, C.c_int]),
+    "pirclient_query_compact_words": (C.c_uint64, [C.c_void_p, C.c_int]),
+    "pirclient_create_query_compact": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, u64p, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "pirclient_save_request_compact": (C.c_int, [C.c_void_p, u64p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p),
+                                                  C.POINTER(C.c_size_t)]),
     "pirclient_save_request": (C.c_int, [C.c_void_p, u64p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "pirclient_load_response": (C.c_int, [C.c_void_p, u8p, C.c_size_t, u64p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "pirclient_query_ct_count": (C.c_uint32, [C.c_void_p]),

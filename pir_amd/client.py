@@ -71,6 +71,36 @@ class PIRClient:
         sends, client.cpp:47-54) or fully expanded ones."""
         self._check(self.lib.pirclient_set_seeded_keys(self._h, 1 if enabled else 0))
 
+    def set_compact_queries(self, mode: int) -> None:
+        """Query ciphertexts of CreateRequest: 0 public-key, as saved (default); 1 symmetric and seed-compressed; 2 the
+        same with c0 packed to the bit width of its moduli (only this tree's server reads 2)."""
+        self._check(self.lib.pirclient_set_compact_queries(self._h, int(mode)))
+
+    def query_compact_words(self, packed: bool) -> int:
+        return int(self.lib.pirclient_query_compact_words(self._h, 1 if packed else 0))
+
+    def create_query_compact(self, index: int, packed: bool = False) -> np.ndarray:
+        """create_query_for, symmetric: [query_ct_count, query_compact_words(packed)] -- c0 (plain or packed) + seed."""
+        n = self.query_ct_count
+        out = np.empty((n, self.query_compact_words(packed)), dtype=np.uint64)
+        got = C.c_uint32()
+        self._check(self.lib.pirclient_create_query_compact(self._h, int(index), 1 if packed else 0, _ptr(out), n,
+                                                            C.byref(got)))
+        return out[:got.value]
+
+    def SaveRequestCompact(self, queries: Sequence[np.ndarray], packed: bool = False) -> bytes:
+        """SaveRequest around compact queries (each [query_ct_count, query_compact_words(packed)])."""
+        cw = self.query_compact_words(packed)
+        q = _u64(np.stack([_u64(x).reshape(self.query_ct_count, cw) for x in queries])) if len(queries) \
+            else np.zeros((0,), dtype=np.uint64)
+        out, n = C.c_void_p(), C.c_size_t()
+        self._check(self.lib.pirclient_save_request_compact(self._h, _ptr(q), len(queries), 1 if packed else 0,
+                                                            C.byref(out), C.byref(n)))
+        try:
+            return C.string_at(out, n.value)
+        finally:
+            self.lib.pirclient_free(out)
+
     # -- reference interface -------------------------------------------------------
     def CreateRequest(self, indexes: Sequence[int]) -> bytes:
         """client.cpp:80-90 -> serialized pir.Request."""

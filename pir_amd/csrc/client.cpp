@@ -248,6 +248,7 @@ struct pirclient {
   std::string galois_blob_seeded, relin_blob_seeded;  // the same keys, seed-compressed (the default on the wire)
   std::map<uint32_t, std::vector<uint8_t>> galois_seeds;
   bool seeded_keys = true;
+  int compact_mode = 0;   // pirclient_set_compact_queries: 0 public-key queries, 1 seeded, 2 seeded and packed
 
   // decryption / encryption constants
   std::vector<uint64_t> inv_punct;   // (Q/q_j)^-1 mod q_j
@@ -508,7 +509,10 @@ struct pirclient {
         }
       }
     }
-    // multiply_add_plain_with_scaling_variant: c0 += floor(Q/t) m + floor((m (Q mod t) + (t+1)/2) / t)
+    add_scaled_plain(pt, n_coeffs, ct);
+  }
+  // multiply_add_plain_with_scaling_variant: c0 += floor(Q/t) m + floor((m (Q mod t) + (t+1)/2) / t)
+  void add_scaled_plain(const uint64_t* pt, size_t n_coeffs, uint64_t* ct) const {
     const uint64_t half_t = (t + 1) >> 1;
     for (size_t i = 0; i < n_coeffs; ++i) {
       if (!pt[i]) continue;
@@ -519,6 +523,51 @@ struct pirclient {
         o[i] = m.add(o[i], m.add(m.mul(pt[i] % m.q, delta_mod[j]), fix % m.q));
       }
     }
+  }
+
+  // Symmetric encryption at the data level, the public half from a seed (SEAL 3.5.6 Encryptor::encrypt_symmetric with
+  // save_seed, as this tree reads it; unverified against a SEAL build -- DESIGN.md section 6.9): a fresh 64-byte
+  // public seed from the client's generator as in rlwe_zero_sym, c1 = sample_poly_uniform(BlakePRNG(seed), data moduli)
+  // in coefficient form, c0 = -(c1 s + e) + the plaintext scaled as encrypt() scales it.  ct [2][k][N]; the pair
+  // (c0, seed) is the whole ciphertext: a compact query (pirgpu.h, pirgpu_query_stage_compact).
+  void encrypt_symmetric(const uint64_t* pt, size_t n_coeffs, uint64_t* ct, uint8_t* seed_out) {
+    if (n_coeffs > N) throw Err{PIRGPU_INVALID_ARGUMENT, "plaintext has more coefficients than the ring degree"};
+    for (size_t i = 0; i < n_coeffs; ++i)
+      if (pt[i] >= t) throw Err{PIRGPU_INVALID_ARGUMENT, "plaintext coefficient is not reduced modulo plain_modulus"};
+    uint64_t* c0 = ct;
+    uint64_t* c1 = ct + (size_t)k * N;
+    for (size_t i = 0; i < wire::kSeedBytes; i += 8) {
+      const uint64_t v = rng.u64();
+      memcpy(seed_out + i, &v, 8);
+    }
+    {
+      wire::SealPrng pub(seed_out);
+      uint64_t mods[PIRGPU_MAX_PRIMES];
+      for (uint32_t j = 0; j < k; ++j) mods[j] = mod[j].q;
+      wire::sample_poly_uniform(pub, mods, k, N, c1);
+    }
+    const std::vector<int> e = sample_noise();
+    for (uint32_t j = 0; j < k; ++j) {
+      const Modulus& m = mod[j];
+      uint64_t* o = c0 + (size_t)j * N;
+      memcpy(o, c1 + (size_t)j * N, (size_t)N * 8);
+      m.ntt(o);
+      for (uint32_t i = 0; i < N; ++i) o[i] = m.mul(o[i], s_ntt[(size_t)j * N + i]);
+      m.intt(o);
+      for (uint32_t i = 0; i < N; ++i) o[i] = m.neg(m.add(o[i], m.from_signed(e[i])));
+    }
+    add_scaled_plain(pt, n_coeffs, ct);
+  }
+  // (c0 [k][N], seed) -> the compact layout: c0 plain or packed (rpk::pack_poly, polynomial by polynomial), then the seed
+  size_t compact_words(bool packed) const { return wire::query_compact_words(sh, packed); }
+  void to_compact(const uint64_t* c0, const uint8_t* seed, bool packed, uint64_t* out) const {
+    uint8_t* o = reinterpret_cast<uint8_t*>(out);
+    for (uint32_t j = 0; j < k; ++j) {
+      const uint32_t w = packed ? rpk::width(mod[j].q) : 64;
+      rpk::pack_poly(c0 + (size_t)j * N, N, w, o);
+      o += rpk::poly_words(N, w) * 8;
+    }
+    memcpy(o, seed, wire::kSeedBytes);
   }
 
   // A ciphertext at level r is [2][r][N] over q_0..q_{r-1}; r = k is the data level.
@@ -665,7 +714,9 @@ struct pirclient {
   // (d_0 + ... + d_{l-1}) + index_l, i.e. in ciphertext pos / N at coefficient pos % N, and carries the inverse of
   // the factor the expansion of that ciphertext multiplies in (N for full ciphertexts, next_power_two(dim_sum % N)
   // for the last one, client.cpp:122-125).
-  void create_query(uint64_t desired_index, uint64_t* out) {
+  // seeds_out != nullptr (compact queries): every ciphertext is encrypted symmetrically instead, c1 from the seed
+  // written to seeds_out[c][kSeedBytes]
+  void create_query(uint64_t desired_index, uint64_t* out, uint8_t* seeds_out = nullptr) {
     if (desired_index >= prm.num_items)
       throw Err{PIRGPU_INVALID_ARGUMENT, "invalid index " + std::to_string(desired_index)};
     const std::vector<uint64_t> indices = calculate_indices(desired_index);
@@ -684,8 +735,19 @@ struct pirclient {
       std::fill(pt.begin(), pt.end(), 0);
       for (const auto& h : hot)
         if (h.first / N == c) pt[h.first % N] = h.second;
-      encrypt(pt.data(), N, out + (size_t)c * ct_words());
+      if (seeds_out) encrypt_symmetric(pt.data(), N, out + (size_t)c * ct_words(), seeds_out + (size_t)c * wire::kSeedBytes);
+      else encrypt(pt.data(), N, out + (size_t)c * ct_words());
     }
+  }
+  // the same query in the compact layout: out [query_ct_count][compact_words(packed)]
+  void create_query_compact(uint64_t desired_index, bool packed, uint64_t* out) {
+    const uint32_t nq = query_ct_count();
+    std::vector<uint64_t> q((size_t)nq * ct_words());
+    std::vector<uint8_t> seeds((size_t)nq * wire::kSeedBytes);
+    create_query(desired_index, q.data(), seeds.data());
+    for (uint32_t c = 0; c < nq; ++c)
+      to_compact(q.data() + (size_t)c * ct_words(), seeds.data() + (size_t)c * wire::kSeedBytes, packed,
+                 out + (size_t)c * compact_words(packed));
   }
   uint64_t invert_mod_t(uint64_t m) const {  // client.cpp:69-78 (try_invert_uint_mod: extended Euclid)
     int64_t a = (int64_t)(m % t), b = (int64_t)t, x0 = 1, x1 = 0;
@@ -784,8 +846,29 @@ struct pirclient {
     wire::put_bytes_field(out, 3, seeded_keys ? relin_blob_seeded : relin_blob);
     return out;
   }
+  // the same around compact query ciphertexts: queries [n][query_ct_count][compact_words(packed)]
+  std::string save_request_compact(const uint64_t* queries, size_t n, bool packed) const {
+    std::string out;
+    const uint32_t nq = query_ct_count();
+    const size_t cw = compact_words(packed);
+    for (size_t i = 0; i < n; ++i) {
+      std::string cts;
+      for (uint32_t c = 0; c < nq; ++c)
+        wire::put_bytes_field(cts, 1, wire::save_query_compact(sh, queries + (i * nq + c) * cw, packed));
+      wire::put_bytes_field(out, 1, cts);
+    }
+    wire::put_bytes_field(out, 2, seeded_keys ? galois_blob_seeded : galois_blob);
+    wire::put_bytes_field(out, 3, seeded_keys ? relin_blob_seeded : relin_blob);
+    return out;
+  }
   std::string create_request(const uint64_t* indexes, size_t n) {  // client.cpp:80-90
     const uint32_t nq = query_ct_count();
+    if (compact_mode) {   // pirclient_set_compact_queries: symmetric, seeded (1) and packed (2)
+      const bool packed = compact_mode == 2;
+      std::vector<uint64_t> q(n * (size_t)nq * compact_words(packed));
+      for (size_t i = 0; i < n; ++i) create_query_compact(indexes[i], packed, q.data() + i * nq * compact_words(packed));
+      return save_request_compact(q.data(), n, packed);
+    }
     std::vector<uint64_t> q(n * (size_t)nq * ct_words());
     for (size_t i = 0; i < n; ++i) create_query(indexes[i], q.data() + i * nq * ct_words());
     return save_request(q.data(), n);
@@ -869,6 +952,42 @@ int pirclient_set_seeded_keys(pirclient* c, int enabled) {
   if (!c) return PIRGPU_INVALID_ARGUMENT;
   c->seeded_keys = enabled != 0;
   return PIRGPU_OK;
+}
+
+int pirclient_set_compact_queries(pirclient* c, int mode) {
+  if (!c) return PIRGPU_INVALID_ARGUMENT;
+  if (mode < 0 || mode > 2) {
+    c->err = "compact query mode must be 0 (public-key), 1 (seeded) or 2 (seeded and packed)";
+    return PIRGPU_INVALID_ARGUMENT;
+  }
+  c->compact_mode = mode;
+  return PIRGPU_OK;
+}
+uint64_t pirclient_query_compact_words(const pirclient* c, int packed) { return c ? c->compact_words(packed != 0) : 0; }
+
+int pirclient_create_query_compact(pirclient* c, uint64_t index, int packed, uint64_t* compact_out, size_t cap_cts,
+                                   uint32_t* n_cts) {
+  if (!c || !compact_out) return PIRGPU_INVALID_ARGUMENT;
+  return guarded(c, [&] {
+    if (cap_cts < c->query_ct_count()) throw Err{PIRGPU_INVALID_ARGUMENT, "compact_out too small"};
+    c->create_query_compact(index, packed != 0, compact_out);
+    if (n_cts) *n_cts = c->query_ct_count();
+  });
+}
+
+int pirclient_save_request_compact(pirclient* c, const uint64_t* queries, size_t n_queries, int packed, uint8_t** request,
+                                   size_t* request_len) {
+  if (!c || (!queries && n_queries) || !request || !request_len) return PIRGPU_INVALID_ARGUMENT;
+  *request = nullptr;
+  *request_len = 0;
+  return guarded(c, [&] {
+    const std::string s = c->save_request_compact(queries, n_queries, packed != 0);
+    uint8_t* buf = (uint8_t*)malloc(s.size() ? s.size() : 1);
+    if (!buf) throw Err{PIRGPU_INTERNAL, "out of memory"};
+    memcpy(buf, s.data(), s.size());
+    *request = buf;
+    *request_len = s.size();
+  });
 }
 
 void pirclient_free(void* p) { free(p); }

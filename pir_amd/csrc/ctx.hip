@@ -323,6 +323,14 @@ struct pirgpu_ctx {
   size_t h_seeds_cap = 0;
   hipEvent_t ev_seed_pin[2] = {nullptr, nullptr};   // "the copy out of this half of h_seed_pin is done"
   uint64_t seed_objects = 0;                // objects expanded on the device so far
+  // compact queries (pirgpu_query_stage_compact / pirgpu_batch_stage_compact): the compact words
+  // of cq_cap queries as they were uploaded, then 8 seed words per ciphertext gathered by query_unpack_kernel.  Written
+  // and read on `stream` only, so its reuse from call to call is covered by stream order
+  uint64_t* d_cq_stage = nullptr;
+  uint32_t cq_cap = 0;                      // queries the stage holds
+  uint64_t* h_cq_stats = nullptr;           // ... their pinned copy, read behind a wait (synchronous calls)
+  uint64_t* d_cq_stats = nullptr;           // the expansion kernel's counters for queries: [0] draws rejected, [1] overrun
+  uint64_t cq_objects = 0;                  // compact ciphertexts expanded on the device so far
   std::map<uint32_t, uint64_t*> xpow;       // shift -> NTT_j(x^(-shift)), [k][N] doubles (NTT-domain last expansion level)
   std::map<uint32_t, uint16_t*> gperm;      // Galois element g -> [2][N] u16: sigma_g / sigma_(g^-1) on NTT positions (galois_perm_table)
 
@@ -2153,6 +2161,9 @@ void pirgpu_destroy(pirgpu_ctx* c) {
     for (auto& kv : ks.keys) (void)hipFree(kv.second);
   for (uint64_t* p : c->key_pool) (void)hipFree(p);
   if (c->d_seeds) (void)hipFree(c->d_seeds);
+  if (c->d_cq_stage) (void)hipFree(c->d_cq_stage);
+  if (c->d_cq_stats) (void)hipFree(c->d_cq_stats);
+  if (c->h_cq_stats) (void)hipHostFree(c->h_cq_stats);
   if (c->h_seed_pin) (void)hipHostFree(c->h_seed_pin);
   if (c->h_seeds) (void)hipHostFree(c->h_seeds);
   for (hipEvent_t e : c->ev_seed_pin)
@@ -3247,9 +3258,10 @@ constexpr size_t kSeedBytes = 64;
 constexpr size_t kSeedStatWords = 2;
 constexpr size_t kSeedStageBytes = 128u << 20;   // the stage holds as many keys as fit in this, at least 1, at most 16
 
-static SeedExpandArgs seed_expand_args(const pirgpu_ctx* c) {
+// n_mod = k + 1: the key level; n_mod = k: the data level (compact queries, section 6.9), a prefix of the same walk
+static SeedExpandArgs seed_expand_args(const pirgpu_ctx* c, bool key_level = true) {
   SeedExpandArgs a{};
-  a.n_mod = c->k + 1;
+  a.n_mod = key_level ? c->k + 1 : c->k;
   a.N = c->N;
   const uint64_t max_random = 0x7FFFFFFFFFFFFFFFull;
   for (uint32_t j = 0; j < a.n_mod; ++j) {
@@ -3966,6 +3978,199 @@ int pirgpu_batch_unstage(pirgpu_ctx* c) {
     b.batch_keyset_gens.clear();
     b.batch_tables.clear();
     b.st_pieces = 0;
+    return PIRGPU_OK;
+  });
+}
+
+// ---- compact queries: c0 (plain or packed words) + the 64-byte seed of c1 per ciphertext ----
+static QueryUnpackArgs cq_args(const pirgpu_ctx* c, bool packed) {
+  return query_unpack_args(c->N, c->prm.coeff_modulus, c->k, packed);
+}
+
+uint64_t pirgpu_query_compact_words(const pirgpu_ctx* c, int packed) { return c ? cq_args(c, packed != 0).obj_words : 0; }
+
+// every c0 coefficient below its modulus (a packed value may be anywhere in [q, 2^w)); c1 needs no check
+static bool cq_in_range(const pirgpu_ctx* c, const QueryUnpackArgs& a, const uint64_t* compact, size_t n_cts) {
+  bool ok = true;
+  for (size_t i = 0; i < n_cts; ++i)
+    for (uint32_t j = 0; j < c->k; ++j)
+      ok &= rpk::check_poly(compact + i * a.obj_words + a.off[j], c->N, a.w[j], c->prm.coeff_modulus[j]);
+  return ok;
+}
+
+static void refuse_compact(const pirgpu_ctx* c) {
+  if (c->slot_sharded || c->sb != 0 || c->se != c->dims[0])
+    throw Fail{PIRGPU_FAILED_PRECONDITION, "compact queries are staged on one GPU: this context is a row or slot shard"};
+}
+
+// the stage for `count` queries of nq ciphertexts: plain-form words (the larger form), then the gathered seeds.  Grows
+// by the rule of ensure_batch_capacity.
+static void ensure_cq_stage(pirgpu_ctx* c, uint32_t count) {
+  if (!c->d_cq_stats) {
+    HIP_TRY(hipMalloc((void**)&c->d_cq_stats, 2 * 8));
+    HIP_TRY(hipMemsetAsync(c->d_cq_stats, 0, 2 * 8, c->stream));
+  }
+  if (!c->h_cq_stats) HIP_TRY(hipHostMalloc((void**)&c->h_cq_stats, 2 * 8, hipHostMallocDefault));
+  if (count <= c->cq_cap) return;
+  const uint32_t nq = c->dim_sum / c->N + 1;
+  if (c->d_cq_stage) {
+    HIP_TRY(hipStreamSynchronize(c->stream));   // its only reader and writer
+    HIP_TRY(hipFree(c->d_cq_stage));
+    c->d_cq_stage = nullptr;
+  }
+  const uint32_t cap = std::max<uint32_t>(count, std::min<uint32_t>(4096, 2 * c->cq_cap));
+  c->cq_cap = 0;
+  HIP_TRY(hipMalloc((void**)&c->d_cq_stage, (size_t)cap * nq * ((size_t)c->k * c->N + 8 + 8) * 8));
+  c->cq_cap = cap;
+}
+static uint64_t* cq_seed_area(const pirgpu_ctx* c) {
+  return c->d_cq_stage + (size_t)c->cq_cap * (c->dim_sum / c->N + 1) * ((size_t)c->k * c->N + 8);
+}
+
+// queries [q0, q0 + n) of a call, nq ciphertexts each: upload their compact words to the stage, unpack c0 and re-sample
+// c1 into dst, one array of ciphertexts [query][nq][2][k][N], all on the main stream
+static void cq_expand_queue(pirgpu_ctx* c, const QueryUnpackArgs& a, const uint64_t* compact, uint32_t nq, uint32_t q0,
+                            uint32_t n, uint64_t* dst) {
+  const size_t at = (size_t)q0 * nq, cts = (size_t)n * nq, dst_qstride = (size_t)nq * c->ctw;
+  uint64_t* stage = c->d_cq_stage + at * a.obj_words;
+  uint64_t* seeds = cq_seed_area(c) + at * 8;
+  HIP_TRY(hipMemcpyAsync(stage, compact + at * a.obj_words, cts * a.obj_words * 8, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(launch_query_unpack(c->stream, a, stage, dst + (size_t)q0 * dst_qstride, seeds, nq, c->ctw, n, dst_qstride));
+  const SeedExpandArgs sa = seed_expand_args(c, false);
+  const size_t half = (size_t)c->k * c->N;
+  HIP_TRY(launch_seed_expand(c->stream, sa, reinterpret_cast<const uint8_t*>(seeds), (uint32_t)cts,
+                             dst + (size_t)q0 * dst_qstride + half, c->ctw, c->d_cq_stats));
+  c->cq_objects += cts;
+}
+
+// The one wait of a synchronous call: the kernel's counters come back in stream order behind the expansion, as the key
+// path's do; an overrun of the kernel's stream bound is an error (and is cleared).  The asynchronous entry points do
+// not look at the flag: it cannot be set for a modulus a context accepts -- a prime below 2^61 accepts more than 7 draws
+// of 8, and max_refills allows four times the stream an object needs without a rejection -- so the check is a guard for
+// the kernel's own arithmetic, which the synchronous calls and the hook exercise on the same code.
+static void cq_wait_checked(pirgpu_ctx* c) {
+  HIP_TRY(hipMemcpyAsync(c->h_cq_stats, c->d_cq_stats, 2 * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (c->h_cq_stats[1]) {
+    HIP_TRY(hipMemsetAsync(c->d_cq_stats + 1, 0, 8, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    throw Fail{PIRGPU_INTERNAL, "seed expansion ran past its stream bound"};
+  }
+}
+
+static int query_stage_compact_impl(pirgpu_ctx* c, const uint64_t* compact, uint32_t nq, int packed, bool wait) {
+  return guarded(c, [&]() -> int {
+    refuse_compact(c);
+    ensure_workspace(c);
+    Worker& w = c->workers[0];
+    if (!compact || nq != c->dim_sum / c->N + 1)  // reference server.cpp:154-158
+      return fail(c, PIRGPU_INVALID_ARGUMENT,
+                  "Number of ciphertexts doesn't match number of items for oblivious expansion.");
+    const QueryUnpackArgs a = cq_args(c, packed != 0);
+    if (!cq_in_range(c, a, compact, nq))
+      return fail(c, PIRGPU_INVALID_ARGUMENT, "ciphertext data is invalid (coefficient out of range)");
+    ensure_cq_stage(c, 1);
+    HIP_TRY(hipStreamWaitEvent(c->stream, w.ev_done, 0));
+    cq_expand_queue(c, a, compact, nq, 0, 1, w.d_query);
+    if (wait) cq_wait_checked(c);   // the caller may reuse `compact` at once
+    w.staged_nq = nq;
+    return PIRGPU_OK;
+  });
+}
+
+int pirgpu_query_stage_compact(pirgpu_ctx* c, const uint64_t* compact, uint32_t nq, int packed) {
+  return query_stage_compact_impl(c, compact, nq, packed, true);
+}
+
+int pirgpu_query_stage_compact_async(pirgpu_ctx* c, const uint64_t* pinned_compact, uint32_t nq, int packed) {
+  return query_stage_compact_impl(c, pinned_compact, nq, packed, false);
+}
+
+static int batch_stage_compact_impl(pirgpu_ctx* c, const uint64_t* compact, uint32_t nq, uint32_t count, int packed,
+                                    bool async) {
+  return guarded(c, [&]() -> int {
+    refuse_compact(c);
+    ensure_workspace(c);
+    if (!compact || nq != c->dim_sum / c->N + 1)  // reference server.cpp:154-158
+      return fail(c, PIRGPU_INVALID_ARGUMENT,
+                  "Number of ciphertexts doesn't match number of items for oblivious expansion.");
+    if (count == 0 || count > 4096) return fail(c, PIRGPU_INVALID_ARGUMENT, "batch size must be in [1, 4096]");
+    const QueryUnpackArgs a = cq_args(c, packed != 0);
+    if (!cq_in_range(c, a, compact, (size_t)count * nq))
+      return fail(c, PIRGPU_INVALID_ARGUMENT, "ciphertext data is invalid (coefficient out of range)");
+    ensure_batch_capacity(c, count);
+    ensure_cq_stage(c, count);
+    BatchSet& b = c->bs();
+    // head-stream work queued earlier may still import queries of this set's previous batch: uploads go behind it
+    if (c->ev_head_tail) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_head_tail, 0));
+    if (async) {
+      // as pirgpu_batch_stage_async: a piece's event is recorded behind its expansion, so a group still waits for
+      // exactly the pieces that hold its queries
+      const uint32_t pieces = (count + kStagePiece - 1) / kStagePiece;
+      while (b.st_events.size() < pieces) {
+        hipEvent_t e;
+        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        b.st_events.push_back(e);
+      }
+      for (uint32_t p = 0; p < pieces; ++p) {
+        const uint32_t q0 = p * kStagePiece, n = std::min<uint32_t>(kStagePiece, count - q0);
+        cq_expand_queue(c, a, compact, nq, q0, n, b.d_bquery);
+        HIP_TRY(hipEventRecord(b.st_events[p], c->stream));
+      }
+      b.st_pieces = pieces;
+    } else {
+      for (uint32_t q0 = 0; q0 < count; q0 += 1024)   // the launch bounds of the two kernels (65535 objects)
+        cq_expand_queue(c, a, compact, nq, q0, std::min<uint32_t>(1024, count - q0), b.d_bquery);
+      cq_wait_checked(c);
+      b.st_pieces = 0;
+    }
+    b.batch_count = count;
+    b.staged_count = count;
+    b.batch_keysets.assign(count, 0);
+    b.batch_keyset_gens.assign(count, 0);
+    b.batch_tables.clear();
+    b.batch_valid = false;
+    return PIRGPU_OK;
+  });
+}
+
+int pirgpu_batch_stage_compact(pirgpu_ctx* c, const uint64_t* compact, uint32_t nq, uint32_t count, int packed) {
+  return batch_stage_compact_impl(c, compact, nq, count, packed, false);
+}
+
+int pirgpu_batch_stage_compact_async(pirgpu_ctx* c, const uint64_t* pinned_compact, uint32_t nq, uint32_t count, int packed) {
+  return batch_stage_compact_impl(c, pinned_compact, nq, count, packed, true);
+}
+
+int pirgpu_query_expand(pirgpu_ctx* c, const uint64_t* compact, uint32_t n, int packed, uint64_t* out) {
+  return guarded(c, [&]() -> int {
+    if (n && (!compact || !out)) return fail(c, PIRGPU_INVALID_ARGUMENT, "null buffer");
+    if (!n) return PIRGPU_OK;
+    const QueryUnpackArgs a = cq_args(c, packed != 0);
+    if (!cq_in_range(c, a, compact, n))
+      return fail(c, PIRGPU_INVALID_ARGUMENT, "ciphertext data is invalid (coefficient out of range)");
+    // the staging path itself, one ciphertext per "query": pieces of kStagePiece, each uploaded, unpacked and expanded
+    const uint32_t nq = c->dim_sum / c->N + 1;
+    ensure_cq_stage(c, (n + nq - 1) / nq);
+    DevScratch buf;
+    uint64_t* d_out = buf.get<uint64_t>((size_t)n * c->ctw * 8);
+    for (uint32_t q0 = 0; q0 < n; q0 += kStagePiece)
+      cq_expand_queue(c, a, compact, 1, q0, std::min<uint32_t>(kStagePiece, n - q0), d_out);
+    HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)n * c->ctw * 8, hipMemcpyDeviceToHost, c->stream));
+    cq_wait_checked(c);
+    return PIRGPU_OK;
+  });
+}
+
+int pirgpu_query_expand_stats(pirgpu_ctx* c, uint64_t stats[2]) {
+  return guarded(c, [&]() -> int {
+    if (!stats) return fail(c, PIRGPU_INVALID_ARGUMENT, "null buffer");
+    stats[0] = c->cq_objects;
+    stats[1] = 0;
+    if (c->d_cq_stats) {
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      HIP_TRY(hipMemcpy(&stats[1], c->d_cq_stats, 8, hipMemcpyDeviceToHost));
+    }
     return PIRGPU_OK;
   });
 }

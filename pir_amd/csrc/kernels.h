@@ -286,4 +286,18 @@ struct SeedExpandArgs {                // by-value kernel argument
 hipError_t launch_seed_expand(hipStream_t st, const SeedExpandArgs& args, const uint8_t* seeds, uint32_t n_obj, uint64_t* out,
                               uint64_t obj_stride, uint64_t* stats);
 
+// Compact queries (query_expand.hip): n_cts compact ciphertexts per query, obj_words words each --
+// polynomial j of c0 as N w[j] / 64 words at off[j] (w[j] = 64: plain words), then the 8 seed words -- at
+// in[query][ct][obj_words].  Ciphertext ct of query q gets its c0 half, [k][N] canonical residues, at
+// out + q * out_qstride + ct * ct_stride, and its seed at seeds[(q * n_cts + ct) * 8]; the c1 half is launch_seed_expand's.
+// query_unpack_args: the argument block for the moduli q[0 .. k), packed ? w[j] = bit length of q[j] - 1 : 64.
+struct QueryUnpackArgs {               // by-value kernel argument
+  uint32_t N, k, obj_words;
+  uint32_t off[kMaxPrimes];
+  uint8_t w[kMaxPrimes];
+};
+QueryUnpackArgs query_unpack_args(uint32_t N, const uint64_t* q, uint32_t k, bool packed);
+hipError_t launch_query_unpack(hipStream_t st, const QueryUnpackArgs& args, const uint64_t* in, uint64_t* out, uint64_t* seeds,
+                               uint32_t n_cts, uint64_t ct_stride, uint32_t n_queries = 1, uint64_t out_qstride = 0);
+
 }  // namespace pirgpu

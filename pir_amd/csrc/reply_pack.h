@@ -75,6 +75,34 @@ inline bool unpack_poly(const void* in, uint32_t N, uint32_t w, uint64_t q, uint
   return !bad;
 }
 
+// unpack_poly for its verdict alone: in[N w / 64] at any alignment, nothing stored; false if a coefficient is >= q
+// (compact queries, DESIGN.md section 6.9: the host checks what the device unpacks)
+inline bool check_poly(const void* in, uint32_t N, uint32_t w, uint64_t q) {
+  const uint8_t* p = static_cast<const uint8_t*>(in);
+  const uint64_t mask = w >= 64 ? ~0ull : (1ull << w) - 1;
+  uint64_t acc = 0;       // unread bits of the current word, at the bottom
+  uint32_t have = 0;
+  uint64_t bad = 0;
+  for (uint32_t i = 0; i < N; ++i) {
+    uint64_t v;
+    if (have >= w) {
+      v = acc & mask;
+      acc = w < 64 ? acc >> w : 0;
+      have -= w;
+    } else {
+      uint64_t next;
+      memcpy(&next, p, 8);
+      p += 8;
+      v = have ? (acc | next << have) & mask : next & mask;
+      const uint32_t took = w - have;            // bits taken from `next`, 1 .. 64
+      acc = took < 64 ? next >> took : 0;
+      have = 64 - took;
+    }
+    bad |= (uint64_t)(v >= q);
+  }
+  return !bad;
+}
+
 // ct [2][in_r][N], the first r residues of each component -> out[ct_words(N, q, r)]
 inline void pack_ct(const uint64_t* ct, uint32_t N, const uint64_t* q, uint32_t r, uint32_t in_r, void* out) {
   uint8_t* o = static_cast<uint8_t*>(out);

@@ -46,6 +46,10 @@
 #pragma weak pirgpu_keyset_set_keys_seeded
 // ... and for packed replies: a back end without the query serves unpacked replies.
 #pragma weak pirgpu_reply_packing
+// ... and for compact queries: without the entry points, seed-compressed queries are expanded on
+// the host as before.
+#pragma weak pirgpu_query_stage_compact_async
+#pragma weak pirgpu_batch_stage_compact_async
 
 namespace pirgpu {
 namespace wire {
@@ -572,6 +576,16 @@ bool seed_expand_on_device() {
   return !(v && v[0] == '0');
 }
 
+// The same for compact queries: PIRGPU_WIRE_QUERY_EXPAND=0 (behind PIRGPU_ALLOW_ENV=1; read per
+// window and per lone request) keeps the host expansion for every query.  The replies are the same bytes either way.
+bool query_expand_on_device(const Server& sv) {
+  if (!pirgpu_query_stage_compact_async || !pirgpu_batch_stage_compact_async) return false;
+  // a row or slot shard stages expanded queries only (its multi-GPU entry points are not fed from compact staging)
+  if (sv.prm.slot_end || (sv.prm.shard_end && (sv.prm.shard_begin || sv.prm.shard_end != sv.prm.dimensions[0]))) return false;
+  const char* v = pirgpu_env("PIRGPU_WIRE_QUERY_EXPAND");
+  return !(v && v[0] == '0');
+}
+
 // SEALDeserialize<GaloisKeys> (server.cpp:46-48) with the device-resident key cache: a client that
 // repeats its (multi-MB) key object byte for byte finds its keys resident; a new client's keys are parsed -- the
 // objects of a seed-compressed Serializable<GaloisKeys>, what the reference client sends (client.cpp:47-54), are
@@ -728,7 +742,13 @@ void run_single(const Server& sv, Job& job, const std::pair<const uint8_t*, size
   uint64_t* hq = pirgpu_host_query_buffer(sv.ctx, 1);
   uint64_t* hr = pirgpu_host_reply_buffer(sv.ctx, 1);
   if (!hq || !hr) throw Err{PIRGPU_INTERNAL, pirgpu_last_error(sv.ctx)};
-  const uint32_t nq = load_query_into(sv.sh, qm.first, qm.second, hq, sv.nq_expected);
+  // a compact query (every ciphertext seed-compressed, of one form, the expected number of them) goes to the device as
+  // it is; anything else is expanded here
+  uint32_t n_seen = 0;
+  const int form = query_expand_on_device(sv) ? query_compact_form(sv.sh, qm.first, qm.second, &n_seen) : 0;
+  const bool compact = form && n_seen == sv.nq_expected;
+  const uint32_t nq = compact ? load_query_compact_into(sv.sh, qm.first, qm.second, form == 2, hq, sv.nq_expected)
+                              : load_query_into(sv.sh, qm.first, qm.second, hq, sv.nq_expected);
   // the direct API's selection survives a request exactly as it was -- a selection that had gone stale stays stale
   // (round-tripping it through a handle would have re-validated it against the slot's next tenant)
   uint32_t callers_sel[2];
@@ -738,7 +758,8 @@ void run_single(const Server& sv, Job& job, const std::pair<const uint8_t*, size
   int rc = pirgpu_query_use_keyset(sv.ctx, job.slot);
   if (!rc && with_tables) rc = pirgpu_query_use_table(sv.ctx, job.table);
   uint64_t got = 0;
-  if (!rc) rc = pirgpu_query_stage_async(sv.ctx, hq, nq);   // pinned staging, untouched until the fetch below returns
+  // pinned staging, untouched until the fetch below returns
+  if (!rc) rc = compact ? pirgpu_query_stage_compact_async(sv.ctx, hq, nq, form == 2) : pirgpu_query_stage_async(sv.ctx, hq, nq);
   if (!rc) rc = pirgpu_query_run(sv.ctx);      // asynchronous: every kernel of the path is queued
   const std::string msg = rc ? pirgpu_last_error(sv.ctx) : "";
   pirgpu_keyset_selection_set(sv.ctx, callers_sel);
@@ -847,7 +868,7 @@ void verify_keys_of(const Server& sv, Window& w) {
 // Parses the queries of `items` into the window's pinned staging (on the pool's threads: 128 KiB + a range check per
 // ciphertext), drops what failed, maps the response buffers, stages the queries asynchronously and queues the window.
 void begin_window(const Server& sv, Window& w, const std::vector<Item>& items, Trace& trace) {
-  const size_t qwords = (size_t)sv.nq_expected * sv.ctw;
+  size_t qwords = (size_t)sv.nq_expected * sv.ctw;
   (void)pirgpu_batch_select(sv.ctx, (uint32_t)w.set);
   auto unselect = finally([&] { (void)pirgpu_batch_select(sv.ctx, (uint32_t)w.home); });
   w.room = (uint32_t)items.size();
@@ -869,12 +890,37 @@ void begin_window(const Server& sv, Window& w, const std::vector<Item>& items, T
     std::string msg;
   };
   std::vector<Outcome> res(items.size());
+  // Compact queries: a window whose EVERY query is compact, of one form and of the expected
+  // ciphertext count is staged as it lies on the wire -- c0 and seed copied, nothing expanded on this side -- and
+  // unpacked and expanded on the device piece by piece.  A mixed window is expanded here as before (the rule of key sets).
+  int form = 0;
+  if (query_expand_on_device(sv)) {
+    std::vector<int> forms(items.size(), -1);   // -1: the request has failed already, it does not vote
+    Pool::get().parallel_for(items.size(), 16, [&](size_t i) {
+      const Job& job = *items[i].job;
+      if (job.rc) return;
+      const auto& qm = job.pr.queries[items[i].qi];
+      uint32_t n_seen = 0;
+      const int f = query_compact_form(sv.sh, qm.first, qm.second, &n_seen);
+      forms[i] = n_seen == sv.nq_expected ? f : 0;
+    });
+    for (int f : forms) {
+      if (f < 0) continue;
+      if (f == 0 || (form && form != f)) {
+        form = 0;
+        break;
+      }
+      form = f;
+    }
+  }
+  if (form) qwords = (size_t)sv.nq_expected * query_compact_words(sv.sh, form == 2);   // the window's stride in w.hq
   Pool::get().parallel_for(items.size(), 8, [&](size_t i) {
     const Job& job = *items[i].job;
     if (job.rc) return;
     try {
       const auto& qm = job.pr.queries[items[i].qi];
-      res[i].nq = load_query_into(sv.sh, qm.first, qm.second, w.hq + i * qwords, sv.nq_expected);
+      res[i].nq = form ? load_query_compact_into(sv.sh, qm.first, qm.second, form == 2, w.hq + i * qwords, sv.nq_expected)
+                       : load_query_into(sv.sh, qm.first, qm.second, w.hq + i * qwords, sv.nq_expected);
     } catch (const Err& e) {
       res[i].code = e.code;
       res[i].msg = e.msg;
@@ -930,7 +976,9 @@ void begin_window(const Server& sv, Window& w, const std::vector<Item>& items, T
     CtxLock lock(sv.ctx);
     const uint32_t before = pirgpu_get_concurrency(sv.ctx);
     int rc = pirgpu_set_concurrency(sv.ctx, std::max<uint32_t>(before, 16));
-    if (!rc) rc = pirgpu_batch_stage_async(sv.ctx, w.hq, sv.nq_expected, count);   // piecewise: group 0 starts after 1 MB
+    // piecewise: group 0 starts after 1 MB (compact: after its piece is uploaded, unpacked and expanded)
+    if (!rc) rc = form ? pirgpu_batch_stage_compact_async(sv.ctx, w.hq, sv.nq_expected, count, form == 2)
+                       : pirgpu_batch_stage_async(sv.ctx, w.hq, sv.nq_expected, count);
     if (!rc) rc = pirgpu_batch_set_keysets(sv.ctx, w.slots.data(), count);
     if (!rc && ctx_tables(sv.ctx) > 1) rc = pirgpu_batch_set_tables(sv.ctx, w.tables.data(), count);
     // every group sends its replies to the pinned buffer as soon as they exist: finish_window only waits

@@ -235,9 +235,9 @@ void put_header(std::string& s, uint64_t total_size, uint8_t compr_mode) {
 }
 
 // Ciphertext::load (+ is_valid_for): returns residues [2][nres][N].
-void load_ciphertext(Cursor& c, const Shape& sh, bool key_level, std::vector<uint64_t>& out) {
+void load_ciphertext(Cursor& c, const Shape& sh, bool key_level, std::vector<uint64_t>& out, int packed_mode) {
   out.resize(2ull * (key_level ? sh.k + 1 : sh.k) * sh.N);
-  load_ciphertext_into(c, sh, key_level, out.data());
+  load_ciphertext_into(c, sh, key_level, out.data(), packed_mode);
 }
 
 // The structure of one saved Ciphertext, every check of Ciphertext::load short of the coefficient ranges made: where
@@ -250,13 +250,16 @@ struct CtView {
   const uint8_t* seed = nullptr;   // null: fully expanded
   const uint8_t* obj_end = nullptr;
   uint32_t nres = 0;
-  bool packed = false;             // a packed reply: `words` holds rpk::ct_words words, count is still 2 nres N
+  bool packed = false;             // `words` holds the `count` coefficients at the bit width of their moduli:
+                                   // rpk::ct_words words (a reply), half of them (the c0 of a compact query)
 };
 }  // namespace
 
-// allow_packed (replies only): the inner array header may carry compression byte 0x80 -- SEAL defines 0 and 1 -- and the
-// array then holds its `count` coefficients at the bit width of their moduli.
-static CtView view_ciphertext(Cursor& c, const Shape& sh, bool key_level, bool allow_packed = false) {
+// packed_mode: the inner array header may carry compression byte 0x80 -- SEAL defines 0 and 1 -- and the array then
+// holds its `count` coefficients at the bit width of their moduli.  kPackedReply: the whole
+// ciphertext, count = 2 nres N.  kPackedQuery (section 6.9): the seed-compressed form alone, count = nres N and the seed
+// behind the array; the byte on a full-size array stays the error it was (Unimplemented, as for any compression byte).
+static CtView view_ciphertext(Cursor& c, const Shape& sh, bool key_level, int packed_mode = kPackedNone) {
   CtView v;
   const uint8_t* obj_end = c.header();
   Cursor o{c.p, obj_end};
@@ -273,7 +276,7 @@ static CtView view_ciphertext(Cursor& c, const Shape& sh, bool key_level, bool a
   if ((is_ntt != 0) != key_level) throw Err{PIRGPU_INVALID_ARGUMENT, "ciphertext NTT form does not match its level"};
   // IntArray<ct_coeff_type>
   o.need(kHeader);
-  v.packed = allow_packed && o.p[5] == rpk::kPackedComprByte;
+  v.packed = packed_mode != kPackedNone && o.p[5] == rpk::kPackedComprByte;
   const uint8_t* arr_end;
   if (v.packed) {   // every check of Cursor::header but the compression byte
     const uint16_t magic = (uint16_t)(o.p[0] | (o.p[1] << 8));
@@ -290,12 +293,23 @@ static CtView view_ciphertext(Cursor& c, const Shape& sh, bool key_level, bool a
   uint64_t count = a.u64();
   const uint64_t full = 2ull * nres * sh.N;
   if (v.packed) {
-    if (count != full) throw Err{PIRGPU_INVALID_ARGUMENT, "ciphertext data is invalid (coefficient count)"};
-    a.need(rpk::ct_words(sh.N, sh.q, nres) * 8);
+    const bool query = packed_mode == kPackedQuery;
+    if (query && count == full)   // the byte on a full-size query array: what Cursor::header says about it, as before
+      throw Err{PIRGPU_UNIMPLEMENTED, "compressed SEAL objects are not supported (reference builds SEAL without zlib)"};
+    if (count != (query ? full / 2 : full)) throw Err{PIRGPU_INVALID_ARGUMENT, "ciphertext data is invalid (coefficient count)"};
+    a.need(rpk::ct_words(sh.N, sh.q, nres) * (query ? 4 : 8));
     v.words = a.p;
     v.count = count;
     v.nres = nres;
     v.obj_end = obj_end;
+    if (query) {
+      // the new form is exact: the array ends with its stream, so the seed lies right behind the last packed word
+      if (a.p + rpk::ct_words(sh.N, sh.q, nres) * 4 != arr_end)
+        throw Err{PIRGPU_INVALID_ARGUMENT, "ciphertext data is invalid (packed array size)"};
+      Cursor sc{arr_end, o.end};
+      sc.need(kSeedBytes);
+      v.seed = sc.p;
+    }
     return v;
   }
   if (count != full && count != full / 2)
@@ -333,9 +347,19 @@ static void check_coefficient_range(const Shape& sh, const uint8_t* words, uint3
     }
 }
 
-void load_ciphertext_into(Cursor& c, const Shape& sh, bool key_level, uint64_t* out) {
-  const CtView v = view_ciphertext(c, sh, key_level);
-  memcpy(out, v.words, v.count * 8);
+void load_ciphertext_into(Cursor& c, const Shape& sh, bool key_level, uint64_t* out, int packed_mode) {
+  if (packed_mode == kPackedReply) throw Err{PIRGPU_INTERNAL, "packed replies are loaded by load_reply"};
+  const CtView v = view_ciphertext(c, sh, key_level, packed_mode);
+  if (v.packed) {   // a compact query's c0 (the range check below gives the verdict)
+    const uint8_t* p = v.words;
+    for (uint32_t j = 0; j < v.nres; ++j) {
+      const uint32_t w = rpk::width(sh.q[j]);
+      (void)rpk::unpack_poly(p, sh.N, w, sh.q[j], out + (size_t)j * sh.N);
+      p += rpk::poly_words(sh.N, w) * 8;
+    }
+  } else {
+    memcpy(out, v.words, v.count * 8);
+  }
   if (v.seed) {
     SealPrng rng(v.seed);
     uint64_t mods[PIRGPU_MAX_PRIMES + 1];
@@ -636,7 +660,7 @@ Shape make_shape(const pirgpu_params& prm) {
 // holds the 2 k N coefficients at the bit width of their moduli).  Either way every coefficient must be below its modulus.
 static void load_reply_ciphertext(Cursor& c, const Shape& sh, uint64_t* out) {
   const uint8_t* start = c.p;
-  const CtView v = view_ciphertext(c, sh, false, true);
+  const CtView v = view_ciphertext(c, sh, false, kPackedReply);
   if (!v.packed) {
     c.p = start;
     load_ciphertext_into(c, sh, false, out);
@@ -664,9 +688,9 @@ uint32_t load_query_into(const Shape& sh, const uint8_t* data, size_t len, uint6
       if (!qr.bytes(d, l)) throw Err{PIRGPU_INVALID_ARGUMENT, "malformed Ciphertexts.ct"};
       Cursor c{d, d + l};
       if (nq < max_cts) {
-        load_ciphertext_into(c, sh, false, dst + (size_t)nq * ctw);
+        load_ciphertext_into(c, sh, false, dst + (size_t)nq * ctw, kPackedQuery);
       } else {
-        load_ciphertext(c, sh, false, spill);
+        load_ciphertext(c, sh, false, spill, kPackedQuery);
       }
       ++nq;
     } else if (!qr.skip((uint32_t)(tag & 7))) {
@@ -701,7 +725,7 @@ static uint32_t load_cts(const Shape& sh, const uint8_t* data, size_t len, std::
         one.resize(2ull * sh.k * sh.N);
         load_reply_ciphertext(c, sh, one.data());
       } else {
-        load_ciphertext(c, sh, false, one);
+        load_ciphertext(c, sh, false, one, kPackedQuery);
       }
       qbuf.insert(qbuf.end(), one.begin(), one.end());
       ++nq;
@@ -710,6 +734,100 @@ static uint32_t load_cts(const Shape& sh, const uint8_t* data, size_t len, std::
     }
   }
   return nq;
+}
+
+// ------------------------------------------------------------------ compact queries
+
+size_t query_compact_words(const Shape& sh, bool packed) {
+  return (packed ? rpk::ct_words(sh.N, sh.q, sh.k) / 2 : (size_t)sh.k * sh.N) + kSeedBytes / 8;
+}
+
+// walks the ct fields of one Ciphertexts message
+template <typename F>
+static void for_each_ct(const uint8_t* data, size_t len, F&& fn) {
+  Reader qr{data, data + len};
+  while (qr.p < qr.end) {
+    uint64_t tag;
+    if (!qr.varint(tag)) throw Err{PIRGPU_INVALID_ARGUMENT, "malformed Ciphertexts"};
+    const uint8_t* d;
+    size_t l;
+    if ((tag >> 3) == 1 && (tag & 7) == 2) {
+      if (!qr.bytes(d, l)) throw Err{PIRGPU_INVALID_ARGUMENT, "malformed Ciphertexts.ct"};
+      fn(d, l);
+    } else if (!qr.skip((uint32_t)(tag & 7))) {
+      throw Err{PIRGPU_INVALID_ARGUMENT, "malformed Ciphertexts"};
+    }
+  }
+}
+
+int query_compact_form(const Shape& sh, const uint8_t* data, size_t len, uint32_t* n_cts) {
+  uint32_t n = 0;
+  int form = -1;   // nothing seen yet
+  try {
+    for_each_ct(data, len, [&](const uint8_t* d, size_t l) {
+      Cursor c{d, d + l};
+      const CtView v = view_ciphertext(c, sh, false, kPackedQuery);
+      const int f = !v.seed ? 0 : v.packed ? 2 : 1;
+      form = form < 0 || form == f ? f : 0;
+      ++n;
+    });
+  } catch (const Err&) {
+    form = 0;   // the ordinary loader reports it
+  }
+  if (n_cts) *n_cts = n;
+  return form < 0 ? 0 : form;
+}
+
+uint32_t load_query_compact_into(const Shape& sh, const uint8_t* data, size_t len, bool packed, uint64_t* dst,
+                                 uint32_t max_cts) {
+  const size_t cw = query_compact_words(sh, packed);
+  uint32_t n = 0;
+  for_each_ct(data, len, [&](const uint8_t* d, size_t l) {
+    Cursor c{d, d + l};
+    const CtView v = view_ciphertext(c, sh, false, kPackedQuery);
+    if (!v.seed || v.packed != packed)
+      throw Err{PIRGPU_INVALID_ARGUMENT, "ciphertext data is invalid (not the compact form of its window)"};
+    if (packed) {
+      const uint8_t* p = v.words;
+      bool ok = true;
+      for (uint32_t j = 0; j < v.nres; ++j) {
+        const uint32_t w = rpk::width(sh.q[j]);
+        ok &= rpk::check_poly(p, sh.N, w, sh.q[j]);
+        p += rpk::poly_words(sh.N, w) * 8;
+      }
+      if (!ok) throw Err{PIRGPU_INVALID_ARGUMENT, "ciphertext data is invalid (coefficient out of range)"};
+    } else {
+      check_coefficient_range(sh, v.words, 1, v.nres);
+    }
+    if (n < max_cts) {
+      uint8_t* o = reinterpret_cast<uint8_t*>(dst + (size_t)n * cw);
+      memcpy(o, v.words, (cw - kSeedBytes / 8) * 8);
+      memcpy(o + (cw - kSeedBytes / 8) * 8, v.seed, kSeedBytes);
+    }
+    ++n;
+  });
+  return n;
+}
+
+std::string save_query_compact(const Shape& sh, const void* obj, bool packed) {
+  const size_t c0_bytes = (query_compact_words(sh, packed) - kSeedBytes / 8) * 8;
+  std::string body;
+  for (int i = 0; i < 4; ++i) put_u64(body, sh.data_id[i]);
+  body.push_back(0);  // is_ntt_form
+  put_u64(body, 2);
+  put_u64(body, sh.N);
+  put_u64(body, sh.k);
+  double scale = 1.0;
+  uint64_t sbits;
+  memcpy(&sbits, &scale, 8);
+  put_u64(body, sbits);
+  put_header(body, kHeader + 8 + c0_bytes, packed ? rpk::kPackedComprByte : 0);
+  put_u64(body, (uint64_t)sh.k * sh.N);
+  body.append(static_cast<const char*>(obj), c0_bytes + kSeedBytes);   // the array, then the seed behind it
+  std::string out;
+  put_header(out, kHeader + body.size());
+  out.append(body);
+  return out;
 }
 
 }  // namespace wire

@@ -134,9 +134,12 @@ struct Shape {
 Shape make_shape(const pirgpu_params& prm);
 
 // Ciphertext::load (+ is_valid_for): residues [2][nres][N]; key_level = (k+1)-prime NTT-form object.
-void load_ciphertext(Cursor& c, const Shape& sh, bool key_level, std::vector<uint64_t>& out);
+// packed_mode = kPackedQuery (the ciphertexts of a query): the seed-compressed form may carry its c0 packed (inner
+// compression byte 0x80); it is unpacked and expanded like the plain seed-compressed form.
+enum { kPackedNone = 0, kPackedReply = 1, kPackedQuery = 2 };
+void load_ciphertext(Cursor& c, const Shape& sh, bool key_level, std::vector<uint64_t>& out, int packed_mode = kPackedNone);
 // the same into caller-owned memory of 2 * nres * N words (e.g. pinned staging)
-void load_ciphertext_into(Cursor& c, const Shape& sh, bool key_level, uint64_t* out);
+void load_ciphertext_into(Cursor& c, const Shape& sh, bool key_level, uint64_t* out, int packed_mode = kPackedNone);
 // Ciphertext::save of a data-level ciphertext appended to `out` (exactly saved_ciphertext_size bytes)
 size_t saved_ciphertext_size(const Shape& sh);
 void append_ciphertext(std::string& out, const Shape& sh, const uint64_t* ct);
@@ -186,6 +189,24 @@ uint32_t load_reply(const Shape& sh, const uint8_t* data, size_t len, std::vecto
 // the same into caller-owned memory with room for max_cts ciphertexts; returns the number of ciphertexts in the message
 // (all of them parsed and validated; those beyond max_cts are not stored)
 uint32_t load_query_into(const Shape& sh, const uint8_t* data, size_t len, uint64_t* dst, uint32_t max_cts);
+
+// Compact queries.  A query ciphertext is accepted in three forms: as Ciphertext::save writes it,
+// seed-compressed (c0 and the 64-byte seed of c1), and seed-compressed with inner compression byte 0x80, the c0 array
+// then holding its k N coefficients at the bit width of their moduli (the stream of rpk::pack_poly, polynomial by
+// polynomial).  The compact layout of the C ABI (pirgpu_query_stage_compact) is c0 as it lies on the wire followed by
+// the 8 words of the seed: query_compact_words words a ciphertext.
+size_t query_compact_words(const Shape& sh, bool packed);
+// The form of one Ciphertexts message from its headers alone: 1 = every ciphertext seed-compressed with plain c0,
+// 2 = every ciphertext seed-compressed with packed c0, 0 = anything else (fully expanded, mixed, empty or malformed:
+// load_query_into reports what there is to report).  n_cts (optional) receives the number of ciphertexts walked.
+int query_compact_form(const Shape& sh, const uint8_t* data, size_t len, uint32_t* n_cts);
+// The splitting loader of a message of that form: every check Ciphertext::load makes, c0 range-checked where it lies
+// (any alignment), then c0 and the seed copied as they are into dst[i][query_compact_words] for i < max_cts -- nothing
+// is unpacked or expanded.  Returns the number of ciphertexts in the message (all validated).
+uint32_t load_query_compact_into(const Shape& sh, const uint8_t* data, size_t len, bool packed, uint64_t* dst,
+                                 uint32_t max_cts);
+// One compact query ciphertext (c0 in its form + seed, query_compact_words words at any alignment) as it goes on the wire.
+std::string save_query_compact(const Shape& sh, const void* obj, bool packed);
 
 }  // namespace wire
 }  // namespace pirgpu

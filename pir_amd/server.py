@@ -686,6 +686,45 @@ class PIRServer:
         if tables is not None:
             self.set_batch_tables(tables)
 
+    # -- compact queries: c0 (plain or packed words) + the seed of c1, expanded on the device ----
+    def query_compact_words(self, packed: bool) -> int:
+        """Words of one compact query ciphertext: k N + 8, or sum_j N w_j / 64 + 8."""
+        return int(self.lib.pirgpu_query_compact_words(self.db.handle, 1 if packed else 0))
+
+    def _compact(self, compact, ndim: int, packed: bool) -> np.ndarray:
+        a = _u64(compact)
+        if a.ndim != ndim or a.shape[-1] != self.query_compact_words(packed):
+            raise PirGpuError(3, "compact queries must be %d-dimensional with %d words per ciphertext, got %s"
+                              % (ndim, self.query_compact_words(packed), a.shape))
+        return a
+
+    def stage_query_compact(self, compact, packed: bool = False) -> None:
+        """compact: [nq, query_compact_words(packed)]; leaves what stage_query leaves with the expanded query."""
+        a = self._compact(compact, 2, packed)
+        self._check(self.lib.pirgpu_query_stage_compact(self.db.handle, _ptr(a), a.shape[0], 1 if packed else 0))
+
+    def stage_batch_compact(self, queries, packed: bool = False, tables: Optional[Sequence[int]] = None) -> None:
+        """queries: [count, nq, query_compact_words(packed)]; leaves what stage_batch leaves with the expanded queries."""
+        a = self._compact(queries, 3, packed)
+        if tables is not None and len(tables) != a.shape[0]:
+            raise PirGpuError(3, "%d tables for %d queries" % (len(tables), a.shape[0]))
+        self._batch_count = a.shape[0]
+        self._check(self.lib.pirgpu_batch_stage_compact(self.db.handle, _ptr(a), a.shape[1], a.shape[0], 1 if packed else 0))
+        if tables is not None:
+            self.set_batch_tables(tables)
+
+    def query_expand(self, compact, packed: bool = False) -> np.ndarray:
+        """Test hook: [n, query_compact_words(packed)] -> [n, 2, k, N], expanded on the device."""
+        a = self._compact(compact, 2, packed)
+        out = np.empty((a.shape[0], 2, self.k, self.N), dtype=np.uint64)
+        self._check(self.lib.pirgpu_query_expand(self.db.handle, _ptr(a), a.shape[0], 1 if packed else 0, _ptr(out)))
+        return out
+
+    def query_expand_stats(self) -> Dict[str, int]:
+        st = (C.c_uint64 * 2)()
+        self._check(self.lib.pirgpu_query_expand_stats(self.db.handle, st))
+        return {"expanded": int(st[0]), "rejected": int(st[1])}
+
     def run_batch(self) -> None:
         self._check(self.lib.pirgpu_batch_run(self.db.handle))
 
