@@ -733,6 +733,25 @@ int pirgpu_ntt_mode(const pirgpu_ctx* ctx);
  * well, info[4] = 128-bit products summed before a reduction (2^(128 - 2 bits), at most 2^30), info[5] = flags: bit 0 =
  * fp64 fold of the scan's digit diagonals for single queries, bit 1 = for groups of queries, bit 2 = 28-bit limb accumulators in the 64-bit scan; info[6..7] = 0. */
 int pirgpu_arith_info(pirgpu_ctx* ctx, uint32_t info[8]);
+/* The walk this context's oblivious expansion takes for a group of B queries (1 .. 8) that each expand n slots
+ * (1 .. N) out of one query ciphertext, with the selectors produced by the last level (every path but pirgpu_expand);
+ * read-only, launches nothing.  One word per level j = 0 .. ceil_log2(n) - 1, in the order the levels are queued; *count
+ * receives their number (n = 1: none), at most `cap` of them are written to out.  head_split = 1: the walk as a batch
+ * takes it when HEAD_MODE (or asynchronous staging) moves the first HEAD_LEVELS levels to the head stream -- the head's
+ * levels, then the lane's, picked up from the state the head left -- where the context's dimensions allow the split (one
+ * query ciphertext per query, B > 1, at least two levels left for the lane); the unsplit walk otherwise.
+ * Bits of a word:  0-1 form (0 unfused: digits, products of all moduli, combine; 1 fused: special-prime product, then
+ * products + combine in one kernel; 2 last level in the NTT domain; 3 last level in coefficient form),  2 the tree is read
+ * as 5-byte polynomials,  3 ... written as 5-byte polynomials,  4 the digit kernel also transforms c0 (wide NTT-domain last
+ * level),  5 looped transforms in the digit kernel,  6 the level's kernels read c0 in NTT form,  7 the tree it leaves has c0
+ * in NTT form,  8 c0 is converted in place before the level,  9 ... after it,  10 the combine step is cut at n * B
+ * outputs,  11 only the special-prime product is inverse-transformed,  12 the level runs on the head stream,  13-14 0, or
+ * the internal error the level would raise (1: 5-byte tree at a level that cannot read it, 2: 5-byte tree at an unfused
+ * level, 3: NTT-form c0 at an unfused level; the walk ends there),  15 the context's batch path writes selectors as
+ * doubles,  16-19 the level j.  After a walk whose last word has form 0 or 1 (or an empty one) the leaves still get their
+ * forward transform. */
+int pirgpu_expansion_forms(pirgpu_ctx* ctx, uint32_t B, uint32_t n, int head_split, uint32_t* out, uint32_t cap,
+                           uint32_t* count);
 
 #ifdef __cplusplus
 }

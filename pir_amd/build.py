@@ -19,7 +19,7 @@ SOURCES = ["kernels.hip", "scan_mfma.hip", "scan_mfma_pair.hip", "ctx.hip", "wir
 NTT_SOURCE = "ntt_kernels.hip"      # compiled once per ring degree (-DPIRGPU_LOGN)
 NTT_LOGNS = [11, 12, 13, 14]
 NTT_PACK_BYTES = [5, 6, 7]          # ... and once per width of the packed key-switch intermediates (-DPIRGPU_PACK_BYTES)
-HEADERS = ["device_params.h", "env_gate.h", "options.h", "batch_plan.h", "kernels.h", "host_math.h", "wire.h", "wire_codec.h", "arith.h", "ntt_core.h", "ctmult.h", "ctmult_convert.h", "reply_pack.h", "scan_mfma_body.inc", NTT_SOURCE, os.path.join("..", "..", "include", "pirgpu.h")]
+HEADERS = ["device_params.h", "env_gate.h", "options.h", "batch_plan.h", "expansion_plan.h", "kernels.h", "host_math.h", "wire.h", "wire_codec.h", "arith.h", "ntt_core.h", "ctmult.h", "ctmult_convert.h", "reply_pack.h", "scan_mfma_body.inc", NTT_SOURCE, os.path.join("..", "..", "include", "pirgpu.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"] + \
     os.environ.get("PIRGPU_BUILD_DEFS", "").split()      # A/B builds of compile-time choices (tools/experiments/r04_ab_ept.sh)

@@ -241,6 +241,8 @@ SIGNATURES = {
     "pirgpu_scan_bytes": (C.c_uint64, [C.c_void_p]),
     "pirgpu_scan_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "pirgpu_arith_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "pirgpu_expansion_forms": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.c_uint32,
+                                         C.POINTER(C.c_uint32)]),
 }
 
 _lib = None

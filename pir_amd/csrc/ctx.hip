@@ -38,6 +38,7 @@
 
 #include "../../include/pirgpu.h"
 #include "batch_plan.h"
+#include "expansion_plan.h"
 #include "ctmult.h"
 #include "device_params.h"
 #include "host_math.h"
@@ -1104,6 +1105,23 @@ struct TreeState {
   bool c0ntt = false;        // ... with their c0 polynomials in NTT form (fused levels, ks_combine_c0_ntt)
 };
 
+// The context's resolved options as the plan (expansion_plan.h) reads them.
+static ExpandOptions expand_options(const pirgpu_ctx* c) {
+  ExpandOptions o;
+  o.mode = c->mode;
+  o.fuse_last_level = c->fuse_last_level;
+  o.last_level_ntt = c->last_level_ntt;
+  o.fuse_mac_combine = c->fuse_mac_combine;
+  o.fuse_mac_nodes = c->fuse_mac_nodes;
+  o.tree40 = c->tree40;
+  o.pack40 = c->pack40;
+  o.c0_ntt = c->c0_ntt;
+  o.c0_ntt_split = c->c0_ntt_split;
+  o.loop_transforms = c->loop_transforms;
+  o.loop_min_sources = c->loop_min_sources;
+  return o;
+}
+
 // Levels [j_begin, j_end) of the tree (j_end clamped to the tree's depth).  `from` (j_begin > 0): where the earlier levels
 // left the tree -- that buffer is only READ; the first level here writes res_a, later ones ping-pong res_a / res_b.
 // `to` (j_end < depth): receives the state after level j_end - 1 instead of the function running to the leaves.
@@ -1115,101 +1133,67 @@ uint64_t* expand_core(pirgpu_ctx* c, hipStream_t st, uint64_t* res_a, uint64_t* 
                       const std::function<void()>& after_first = nullptr) {
   const uint32_t N = c->N, k = c->k;
   if (n > N) throw Fail{PIRGPU_INVALID_ARGUMENT, "Cannot expand more items from a CT than poly modulus degree"};
-  const uint32_t logm = hm::ceil_log2(n);
-  const bool fuse_last = sel_dst && c->mode != kNttInt && c->fuse_last_level;
-  if (sel_f64 && !(fuse_last && c->last_level_ntt && n >= 2)) throw Fail{PIRGPU_INTERNAL, "double-form selectors need the NTT-domain last level"};
+  const ExpandOptions eo = expand_options(c);
+  if (sel_f64 && !(sel_dst && eo.mode != kNttInt && eo.fuse_last_level && eo.last_level_ntt && n >= 2))
+    throw Fail{PIRGPU_INTERNAL, "double-form selectors need the NTT-domain last level"};
   uint64_t *cur = res_a, *nxt = res_b;
-  bool cur40 = false;   // `cur` holds 5-byte polynomials (between fused levels) instead of doubles
-  bool c0ntt = false;   // `cur` holds its c0 polynomials in NTT form
+  TreeFlags in;
   if (from) {
     cur = from->cur;
-    cur40 = from->cur40;
-    c0ntt = from->c0ntt;
+    in.cur40 = from->cur40;
+    in.c0ntt = from->c0ntt;
     nxt = res_a;
   }
-  const uint32_t j_stop = std::min(j_end, logm);
-  // c0 in NTT form through the fused levels (ks_combine_c0_ntt): only for a tree whose leaves are consumed in NTT form by
-  // ks_last_ntt_kernel -- pirgpu_expand's coefficient-form results keep the coefficient-form tree
-  const bool c0_path = c->c0_ntt && fuse_last && c->last_level_ntt && c->mode != kNttInt && c->fuse_mac_combine;
-  const uint32_t fuse_from = B > 1 ? std::max<uint32_t>(c->fuse_mac_nodes / 2, 1) : c->fuse_mac_nodes;
-  // level j runs the fused form (special-prime product, then data products + combine in one kernel)
-  auto level_fused = [&](uint32_t j) {
-    return c->mode != kNttInt && c->fuse_mac_combine && ((1u << j) * B) >= fuse_from && !(fuse_last && j + 1 == logm);
-  };
-  for (uint32_t j = j_begin; j < j_stop; ++j) {
-    // (picking a tree up from another buffer: after its first level here the ping-pong is res_a <-> res_b)
-    auto level_done = [&]() {
-      if (from && j == j_begin) {
-        nxt = res_b;
-        if (after_first) after_first();
-      }
-    };
+  // every decision of the walk (forms, 5-byte tree, c0 in NTT form, looped transforms) is the plan's: expansion_plan.h
+  const ExpandPlan plan = plan_expansion(N, c->logN, k, B, n, sel_dst != nullptr, eo, j_begin, j_end, from ? &in : nullptr);
+  for (const ExpandLevel& L : plan.levels) {
+    const uint32_t j = L.j, nodes = L.nodes;
     const uint32_t g = (N >> j) + 1;
     const KeyPtrs key = keys_for(c, g, ksets, B);   // per query of the group: its own client's key
-    const uint32_t nodes = (1u << j) * B;
-    const bool last_ntt = fuse_last && j + 1 == logm && c->last_level_ntt;
-    const bool c0_in_digit = last_ntt && !c0ntt && ks_digit_takes_c0(nodes);
-    if (cur40 && !(last_ntt ? (c0ntt || c0_in_digit) : true)) throw Fail{PIRGPU_INTERNAL, "5-byte tree reached a level that cannot read it"};
-    // the root enters a fused level directly (a group wide enough at level 0): its c0 goes to NTT form in place --
-    // never in a buffer handed over by another stream (`from` is read-only; its owner converted it after ITS last level)
-    if (c0_path && !c0ntt && level_fused(j) && !cur40 && !(from && j == j_begin)) {
-      HIP_TRY(c->ops->tree_c0_fwd(st, c->mode, c->dp, k, cur, nodes));
-      c0ntt = true;
+    if (L.invalid == kTree40Unreadable) throw Fail{PIRGPU_INTERNAL, "5-byte tree reached a level that cannot read it"};
+    // (never in a buffer handed over by another stream: `from` is read-only; its owner converted it after ITS last level)
+    if (L.c0_before) HIP_TRY(c->ops->tree_c0_fwd(st, c->mode, c->dp, k, cur, nodes));
+    HIP_TRY(c->ops->ks_digit(st, c->mode, c->dp, k, cur, g, nodes, dig, c->pack40, L.c0_in_digit ? prod : nullptr, L.tin40,
+                             L.loop_targets));
+    if (L.invalid == kTree40Unfused) throw Fail{PIRGPU_INTERNAL, "5-byte tree reached an unfused level"};
+    if (L.invalid == kC0NttUnfused) throw Fail{PIRGPU_INTERNAL, "NTT-form c0 reached an unfused level"};
+    HIP_TRY(c->ops->ks_mac_intt(st, c->mode, c->dp, k, dig, key, nodes, prod, c->pack40, L.mac_base, L.mac_count));
+    switch (L.form) {
+      case kLevelFused:
+        // special-prime product first (the only one that goes through HBM), then the data residues with the combine
+        // step in their epilogue: no data products in HBM, no separate combine pass
+        HIP_TRY(c->ops->ks_mac_combine(st, c->mode, c->dp, k, dig, key, prod, cur, g, nodes, 1u << j, nxt, c->pack40, L.tin40,
+                                       L.tout40, L.c0ntt() ? xpow_table(c, st, 1u << j) : nullptr,
+                                       L.c0ntt() ? galois_perm_table(c, st, g) : nullptr, c->c0_ntt_split));
+        break;
+      case kLevelLastNtt: {
+        // last level in the NTT domain: only the special-prime product is inverse-transformed
+        const uint64_t* X = xpow_table(c, st, 1u << j);
+        HIP_TRY(c->ops->ks_last_ntt(st, c->mode, c->dp, k, cur, dig, key, prod, X, g, galois_inverse(g, N), 1u << j, n, B,
+                                    *sel_dst, nodes, c->pack40, sel_f64, L.c0_in_digit, L.c0ntt() ? (L.tin40 ? 2 : 1) : 0,
+                                    galois_perm_table(c, st, g)));
+        return nullptr;
+      }
+      case kLevelLastCoeff:
+        HIP_TRY(c->ops->ks_last_level(st, c->mode, c->dp, k, cur, prod, g, 1u << j, n, B, *sel_dst, nodes, c->pack40));
+        return nullptr;
+      case kLevelUnfused:
+        HIP_TRY(launch_ks_combine(st, c->dp, c->mode, N, k, cur, prod, galois_inverse(g, N), nodes, 1u << j, true, L.hi_limit,
+                                  c->pack40, nxt, c->pack_bytes));
+        break;
     }
-    HIP_TRY(c->ops->ks_digit(st, c->mode, c->dp, k, cur, g, nodes, dig, c->pack40, c0_in_digit ? prod : nullptr, cur40,
-                             c->loop_transforms && (uint64_t)nodes * k >= c->loop_min_sources));
-    // (a group of B queries reaches the width at which the fused form pays one level earlier than a single query:
-    // measured +0.6 % batched with the threshold at 64 tree ciphertexts, while a single query loses latency below 128)
-    if (level_fused(j)) {
-      // special-prime product first (the only one that goes through HBM), then the data residues with the combine
-      // step in their epilogue: no data products in HBM, no separate combine pass.  Between two fused levels (and into
-      // the NTT-domain last level) the tree is written as 5-byte polynomials: these launches are HBM-bound
-      const uint32_t next_nodes = nodes * 2;
-      const bool next_last = j + 2 == logm;
-      const bool next_reads40 = next_last ? (fuse_last && c->last_level_ntt && (c0ntt || ks_digit_takes_c0(next_nodes)))
-                                          : (next_nodes >= fuse_from);
-      const bool out40 = c->tree40 && c->pack40 && j + 1 < logm && next_reads40 && (1u << j) < (N >> ntt_log_ept((int)c->logN));
-      HIP_TRY(c->ops->ks_mac_intt(st, c->mode, c->dp, k, dig, key, nodes, prod, c->pack40, k, 1));
-      HIP_TRY(c->ops->ks_mac_combine(st, c->mode, c->dp, k, dig, key, prod, cur, g, nodes, 1u << j, nxt, c->pack40, cur40,
-                                     out40, c0ntt ? xpow_table(c, st, 1u << j) : nullptr,
-                                     c0ntt ? galois_perm_table(c, st, g) : nullptr, c->c0_ntt_split));
-      cur40 = out40;
-      std::swap(cur, nxt);
-      level_done();
-      continue;
-    }
-    if (cur40 && !last_ntt) throw Fail{PIRGPU_INTERNAL, "5-byte tree reached an unfused level"};
-    if (c0ntt && !last_ntt) throw Fail{PIRGPU_INTERNAL, "NTT-form c0 reached an unfused level"};
-    if (fuse_last && j + 1 == logm && c->last_level_ntt) {
-      // last level in the NTT domain: only the special-prime product is inverse-transformed
-      const uint64_t* X = xpow_table(c, st, 1u << j);
-      HIP_TRY(c->ops->ks_mac_intt(st, c->mode, c->dp, k, dig, key, nodes, prod, c->pack40, k, 1));
-      HIP_TRY(c->ops->ks_last_ntt(st, c->mode, c->dp, k, cur, dig, key, prod, X, g, galois_inverse(g, N), 1u << j, n, B,
-                                  *sel_dst, nodes, c->pack40, sel_f64, c0_in_digit, c0ntt ? (cur40 ? 2 : 1) : 0,
-                                  galois_perm_table(c, st, g)));
-      return nullptr;
-    }
-    HIP_TRY(c->ops->ks_mac_intt(st, c->mode, c->dp, k, dig, key, nodes, prod, c->pack40, 0, k + 1));
-    if (fuse_last && j + 1 == logm) {
-      HIP_TRY(c->ops->ks_last_level(st, c->mode, c->dp, k, cur, prod, g, 1u << j, n, B, *sel_dst, nodes, c->pack40));
-      return nullptr;
-    }
-    // outputs n*B.. of the last level are never read (only the first n results per query are used)
-    const uint32_t hi_limit = j + 1 == logm ? n * B : UINT32_MAX;
-    HIP_TRY(launch_ks_combine(st, c->dp, c->mode, N, k, cur, prod, galois_inverse(g, N), nodes, 1u << j, true, hi_limit,
-                              c->pack40, nxt, c->pack_bytes));
     std::swap(cur, nxt);
-    // the next level is a fused one: this (narrow) level's outputs, in this stream's own buffer, get their c0 transformed
-    if (c0_path && j + 1 < logm && level_fused(j + 1)) {
-      HIP_TRY(c->ops->tree_c0_fwd(st, c->mode, c->dp, k, cur, nodes * 2));
-      c0ntt = true;
+    if (L.c0_after) HIP_TRY(c->ops->tree_c0_fwd(st, c->mode, c->dp, k, cur, nodes * 2));
+    // (picking a tree up from another buffer: after its first level here the ping-pong is res_a <-> res_b)
+    if (from && j == j_begin) {
+      nxt = res_b;
+      if (after_first) after_first();
     }
-    level_done();
   }
   if (to) {
     to->cur = cur;
-    to->cur40 = cur40;
-    to->c0ntt = c0ntt;
+    to->cur40 = plan.out.cur40;
+    to->c0ntt = plan.out.c0ntt;
   }
   return cur;
 }
@@ -2551,6 +2535,36 @@ int pirgpu_scan_info(pirgpu_ctx* c, uint32_t info[8]) {
     info[5] = c->scan_rows;
     info[6] = c->scan_cols;
     info[7] = (c->mfma_on && c->mfma_single ? 1u : 0u) | (c->mfma_on && c->mg.top4 ? 2u : 0u);
+    return PIRGPU_OK;
+  });
+}
+
+int pirgpu_expansion_forms(pirgpu_ctx* c, uint32_t B, uint32_t n, int head_split, uint32_t* out, uint32_t cap, uint32_t* count) {
+  return guarded(c, [&]() -> int {
+    if (!count || (cap && !out)) return fail(c, PIRGPU_INVALID_ARGUMENT, "null output");
+    if (B == 0 || B > (uint32_t)kMaxMfmaQueries) return fail(c, PIRGPU_INVALID_ARGUMENT, "group size out of range");
+    if (n == 0 || n > c->N) return fail(c, PIRGPU_INVALID_ARGUMENT, "slot count out of range");
+    ensure_workspace(c);
+    const ExpandOptions eo = expand_options(c);
+    const bool sel_f64 = c->sel_f64;   // (what the MFMA batch path hands its groups; single queries never take it)
+    // the split expand_group_on_lane takes for this context's queries when HEAD_MODE (or the staging) asks for one
+    const bool use_head = head_split && expansion_uses_head(c->dim_sum / c->N + 1, B, c->head_levels, true,
+                                                            expansion_depth((uint32_t)std::min<uint64_t>(c->dim_sum, c->N)));
+    uint32_t w = 0;
+    auto emit = [&](const ExpandPlan& p, bool on_head) {
+      for (const ExpandLevel& L : p.levels) {
+        if (w < cap) out[w] = pack_expand_level(L, on_head, sel_f64);
+        ++w;
+      }
+    };
+    if (use_head) {
+      const ExpandPlan head = plan_expansion(c->N, c->logN, c->k, B, n, true, eo, 0, c->head_levels);
+      emit(head, true);
+      if (head.valid()) emit(plan_expansion(c->N, c->logN, c->k, B, n, true, eo, c->head_levels, UINT32_MAX, &head.out), false);
+    } else {
+      emit(plan_expansion(c->N, c->logN, c->k, B, n, true, eo), false);
+    }
+    *count = w;
     return PIRGPU_OK;
   });
 }
@@ -4386,8 +4400,8 @@ static void expand_group_on_lane(pirgpu_ctx* c, BatchLane& ln, Worker* const* me
   // -- for batches that were staged asynchronously (request windows queued behind one another: +6 % through the wire,
   // 12.0 against 12.9 ms per window of 64 with two callers) or always (head_mode 2); a back-to-back loop over one staged
   // batch gains nothing from it (5 325-5 408 against 5 379-5 433 queries/s, same box) and keeps the plain path
-  const bool use_head = nq == 1 && B > 1 && c->head_levels > 0 && (c->head_mode == 2 || (c->head_mode == 1 && c->bs().st_pieces > 0)) &&
-                        hm::ceil_log2((uint32_t)std::min<uint64_t>(c->dim_sum, N)) >= c->head_levels + 2;
+  const bool use_head = expansion_uses_head(nq, B, c->head_levels, c->head_mode == 2 || (c->head_mode == 1 && c->bs().st_pieces > 0),
+                                            expansion_depth((uint32_t)std::min<uint64_t>(c->dim_sum, N)));
   // (a permuted group's queries may lie in any piece of the upload: it waits for all of them)
   const uint32_t ws_first = qidx ? 0 : first, ws_n = qidx ? c->bs().staged_count : B;
   if (!use_head) wait_staged(c, ln.stream, ws_first, ws_n);

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "device_params.h"
+#include "expansion_plan.h"
 
 namespace pirgpu {
 
@@ -12,8 +13,7 @@ constexpr int kMaxMfmaQueries = 8;   // (query, comp) pairs fill the 16 columns 
 constexpr int kMaxScanGroups = 16;   // groups of <= 8 queries one scan launch can serve (slot-sharded multi-GPU step)
 constexpr int kMaxSlices = 16;       // slot ranges (= ranks) a packed selector buffer / row-sum exchange can be cut into
 
-constexpr uint32_t kKsWideLevel = 256;   // nodes per launch from which the key-switch kernels use the XCD-aware 1-D grid
-inline bool ks_digit_takes_c0(uint32_t nodes) { return nodes >= kKsWideLevel && nodes % 8 == 0; }
+// (kKsWideLevel and ks_digit_takes_c0, which the kernels share with the expansion's plan: expansion_plan.h)
 
 struct MfmaPtrs {                    // one pointer per query of a group (by-value kernel argument)
   const void* p[kMaxMfmaQueries];

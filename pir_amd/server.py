@@ -924,6 +924,23 @@ class PIRServer:
                 "queries_per_pass": info[4], "rows": info[5], "cols": info[6], "single_query_mfma": bool(info[7] & 1),
                 "top_digit_nibble": bool(info[7] & 2)}
 
+    EXPANSION_FORMS = ("unfused", "fused", "last_ntt", "last_coeff")
+
+    def expansion_forms(self, B: int, n: int, head_split: bool = False) -> List[dict]:
+        """The walk the oblivious expansion takes for a group of B queries expanding n slots each
+        (pirgpu_expansion_forms): one record per level, in launch order; read-only.  `word` is the packed level as the
+        library reports it, the other keys are its bits (include/pirgpu.h)."""
+        out = (C.c_uint32 * 32)()
+        cnt = C.c_uint32(0)
+        self._check(self.lib.pirgpu_expansion_forms(self.db.handle, B, n, 1 if head_split else 0, out, 32, C.byref(cnt)))
+        assert cnt.value <= 32, cnt.value
+        return [{"word": w, "level": w >> 16 & 15, "form": self.EXPANSION_FORMS[w & 3], "tin40": bool(w >> 2 & 1),
+                 "tout40": bool(w >> 3 & 1), "c0_in_digit": bool(w >> 4 & 1), "loop_targets": bool(w >> 5 & 1),
+                 "c0ntt": bool(w >> 6 & 1), "c0ntt_out": bool(w >> 7 & 1), "c0_before": bool(w >> 8 & 1),
+                 "c0_after": bool(w >> 9 & 1), "hi_limit": bool(w >> 10 & 1), "mac_special_only": bool(w >> 11 & 1),
+                 "on_head": bool(w >> 12 & 1), "invalid": w >> 13 & 3, "sel_f64": bool(w >> 15 & 1)}
+                for w in (int(out[i]) for i in range(cnt.value))]
+
     # -- test-visible helpers (server.h:66-131) -----------------------------------------
     def substitute_power_x_inplace(self, ct: np.ndarray, power: int) -> np.ndarray:
         """server.cpp:67-76; returns the substituted ciphertext (ct itself is updated too)."""
